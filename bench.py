@@ -6,10 +6,22 @@ workload : BASELINE.json configs[1] = SURVEY.md 8d cfg2: m=4, n=2, nsamples=1024
            resolution=3600, spectrum port wired; per GPU 8 independent synthetic streams of 32,768
            items (262,144 items = one "step" = one pass of the hot path: covariance -> EVD -> scan -> merge),
            device-resident in HBM before the timed region.
-timing   : W warm-up steps, then EXACTLY K steps between barrier + synchronize on both sides, max over ranks.
-           A K-step region is ~25 ms at the driver's K = 20, so the measurement is REPEATED (rounds of exactly K
-           steps, each bracketed the same way) until >= --min-seconds of timed work has accumulated; the line
-           reports the MEDIAN round (ms_per_step, value) and lists every round under "rounds".
+timing   : W warm-up steps, then EXACTLY K steps between barrier + synchronize on both sides, max over ranks; ms_per_step is
+           that region's time / K.  With --full (or an explicit --min-seconds) the K-step region is REPEATED (rounds of exactly
+           K steps, each bracketed the same way) until >= --min-seconds of timed work has accumulated (--full: 0.5 s); the line
+           then reports the MEDIAN round (ms_per_step, value) and lists every round under "rounds".
+plain    : `python bench.py --gpus N --steps K --warmup W` does only what the headline needs: set up, warm up, time the K
+           steps, write the outputs (--dump-outputs), print the line (metric, value, unit, ms_per_step, ...).  It measures in
+           this process and checks nothing against the oracle.
+--full   : everything else as well: hipEvents around the dominant kernel inside the timed rounds (roofline), a separate
+           per-stage pass, the oracle check of the last timed step's outputs (and an exit code that speaks for it), the plain
+           fill ceiling, cpu_baseline and the secondary legs (extras) -- all described below.
+outputs  : --dump-outputs DIR writes what the LAST timed step left in the output buffers, as a caller of process_device()
+           receives them: DIR/ang.npy and DIR/lvl.npy (float32, items x n, every item of the rank) and DIR/spectrum_sample.npy
+           (float32, rows x resolution) for a fixed sample of items: the rows
+           sorted(numpy.random.default_rng([DUMP_SEED, rank]).choice(items, DUMP_SPECTRUM_ROWS // N, replace=False)) -- the whole
+           spectrum is 3.8 GB per GPU.  N > 1: one set of files per rank, suffix _rank<r>.  The inputs are seeded (1002 + stream),
+           so the same arguments give the same inputs in every run; the files of two builds compare output for output.
 N GPUs   : one process per GPU, streams dealt s mod N, NO data-path collective; torch.distributed (RCCL) only
            provides the barrier and the max-over-ranks clock.  --scaling weak (default; per-GPU work fixed: 8 streams per
            GPU) or --scaling strong = BASELINE configs[3] as written: the SAME 64 streams (seed 1002 + s) at every N,
@@ -25,10 +37,10 @@ roofline : dominant kernel = the scan (scan_mfma_kernel); achieved = its algorit
            bytes per launch from the rocprofv3 PMC passes kept under profiles/ -- used ONLY when that profile was
            taken on the kernel sources this run executes (sha256 over gr_baz_amd/csrc + include), else null and
            "traffic_stale": true.
-output   : exactly ONE JSON line on stdout.  Plain `python bench.py` (one GPU) measures in a CHILD of itself (supervise()): the child hands its
-           complete line -- metric, roofline, cpu_baseline, verification -- to the GPU-free parent (and to stderr) BEFORE the secondary legs start and
-           the same line with the legs' figures after them; the parent prints the last one it has got, restarts the child once if a signal killed
-           it before any line existed (config.headline_attempt), and otherwise passes its exit code on.
+output   : exactly ONE JSON line on stdout.  `python bench.py --full` (one GPU) measures in a CHILD of itself (supervise()): the child hands
+           its complete line -- metric, roofline, cpu_baseline, verification -- to the GPU-free parent (and to stderr) BEFORE the secondary legs start
+           and the same line with the legs' figures after them; the parent prints the last one it has got and passes the child's exit code on.  A
+           child that dies is never started again (a device that has just faulted runs nothing more).
 extras   : config.extra carries secondary, clearly labelled measurements (rank 0, N=1), EACH IN ITS OWN PROCESS (python bench.py --extra-leg NAME,
            time limit 150 s): the cost of retunes beside the headline's steps, cfg2 WITHOUT the spectrum port (the GRC default wiring), the
            unfavourable cfg2 cases (an incoherent batch with and without the spectrum port, 60 dB SNR), cfg3 (8 ant, 4096 samp, 36000 bins; and without
@@ -165,6 +177,23 @@ def cpu_baseline(table, seconds_per_thread=2.0):
 
 I8_MFMA_PEAK_TOPS = 5000.0   # dense int8 = 2 x the ~2.5 PF bf16 dense peak (MI355X_MICROARCH.md, matrix cores; ubench >= 3944 TOPS)
 VERIFY_TOL = 1e-5            # north_star's relative tolerance on float outputs
+DUMP_SEED, DUMP_SPECTRUM_ROWS = 1002, 1024   # --dump-outputs: seeded sample of spectrum rows (14.7 MB), shared out over the ranks
+
+
+def dump_outputs(path, torch, np, ang, lvl, spec, rank, world):
+    """--dump-outputs DIR: what the last timed step left in the output buffers (see the module docstring, "outputs").
+    At most 2 x 16 MB (ang, lvl: strong scaling, 2,097,152 items over all ranks) + 14.7 MB (spectrum rows) in all."""
+    os.makedirs(path, exist_ok=True)
+    B = ang.shape[0]
+    rows = np.sort(np.random.default_rng([DUMP_SEED, rank]).choice(B, min(B, max(1, DUMP_SPECTRUM_ROWS // world)), replace=False))
+    arrays = {"ang": ang.cpu().numpy(), "lvl": lvl.cpu().numpy(),
+              "spectrum_sample": spec.index_select(0, torch.from_numpy(rows).to(spec.device)).cpu().numpy()}
+    suffix = "_rank%d" % rank if world > 1 else ""
+    for name, a in arrays.items():
+        assert a.dtype == np.float32, (name, a.dtype)
+        np.save(os.path.join(path, name + suffix + ".npy"), a)
+    return {"dir": path, "files": sorted(n + suffix + ".npy" for n in arrays), "bytes": int(sum(a.nbytes for a in arrays.values())),
+            "spectrum_rows": "sorted(numpy.random.default_rng([%d, rank]).choice(%d, %d, replace=False))" % (DUMP_SEED, B, len(rows))}
 
 
 def verify_against_oracle(torch, np, x, ang, lvl, spec, table, m, n, nsamples, res, count):
@@ -492,6 +521,14 @@ def leg_retune_in_flight(torch, np, capi, synth, dev, stream, emit=None):
 def run_legs_here(names):
     """Child mode (python bench.py --extra-leg a[,b,...]): the named legs one after the other in THIS process; one JSON object per
     line on stdout, {"leg": name, ...}; a leg may print a partial object first -- the parent keeps the last line of each leg."""
+    # test hook (tests/test_bench_driver_cmd.py): "<kind>:<leg>", kind "raise" (an exception) or "hang" (a leg that never returns, cut
+    # off by the parent's time limit); taken before this process touches the GPU
+    kind, _, target = os.environ.get("BAZ_BENCH_INJECT_FAULT", "").partition(":")
+    if target in names:
+        note("INJECTED FAILURE (%s) in leg %s" % (kind, target))
+        if kind == "hang":
+            time.sleep(3600)
+        raise RuntimeError("injected failure (%s)" % kind) if kind == "raise" else SystemExit(3)
     import numpy as np
     import torch
     from gr_baz_amd import capi, synth
@@ -504,21 +541,6 @@ def run_legs_here(names):
     for name in names:
         note("leg %s" % name)
         emit = lambda d, name=name: print(json.dumps(dict(d, leg=name)), flush=True)
-        inject = os.environ.get("BAZ_BENCH_INJECT_FAULT", "")     # test hook (tests/test_bench_driver_cmd.py): "<kind>:<leg>"
-        if inject.endswith(":" + name):
-            kind = inject.split(":")[0]
-            note("INJECTED FAULT (%s) in leg %s" % (kind, name))
-            if kind == "abort":
-                os.abort()                                        # what the runtime does after a GPU memory fault
-            if kind == "hang":
-                time.sleep(3600)
-            if kind == "gpufault":                                # a REAL GPU memory fault: the covariance kernel is handed an unmapped input address
-                arr, table = helper_table(np, synth, M, RES)
-                with capi.Context(M, N_EMIT, NSAMPLES, RES, table, device_id=dev.index) as ctx:
-                    o = torch.zeros(64, N_EMIT, dtype=torch.float32, device=dev)
-                    ctx.process_device(0x10000, 64, o.data_ptr(), o.data_ptr(), None)
-                    ctx.sync()
-            raise RuntimeError("injected failure (%s)" % kind) if kind == "raise" else SystemExit(3)
         try:
             if name in MUSIC_LEGS:
                 m, nsamples, res, batch, with_spec, seconds, scene, snr, labels = MUSIC_LEGS[name]
@@ -602,13 +624,12 @@ def run_leg_subprocess(name, timeout_s=None):
 
 
 def supervise():
-    """Plain `python bench.py` with one GPU: the measurement runs in a CHILD of this process (same command line); this process holds no GPU context and
+    """`python bench.py --full` with one GPU: the measurement runs in a CHILD of this process (same command line); this process holds no GPU context and
     cannot be taken down by a GPU fault.  It passes exactly ONE JSON line on to stdout -- the contract's "rank 0 prints ONE JSON line" --: the LAST one the
     child printed.  The child prints its complete line (metric, roofline, cpu_baseline, verification) before the secondary legs start and the same line with
-    the legs' figures after them; should it die in between, the first is what stdout gets.  If the child is killed by a signal before it has printed any
-    line -- the HIP runtime abort()s a process whose GPU work hits a memory fault, which is what took the driver's round-5 run -- it is
-    started ONCE more, and the line of the second attempt says so (config.headline_attempt = 2, config.headline_previous_failure).  Nothing is retried after
-    an orderly exit (wrong arguments, no GPU, a failed verification) or once a line exists.  BAZ_BENCH_SUPERVISE=0 runs everything in this process."""
+    the legs' figures after them; should it die in between, the first is what stdout gets.  The child is never started again: a process killed by a
+    signal -- the HIP runtime abort()s a process whose GPU work hits a memory fault -- ends the run with its exit status, and the
+    device is left alone.  BAZ_BENCH_SUPERVISE=0 runs everything in this process."""
     import signal
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__)] + sys.argv[1:]
@@ -628,25 +649,19 @@ def supervise():
             signal.signal(sig, on_term)
         except Exception:
             pass
-    previous = ""
-    for attempt in (1, 2):
-        env = dict(os.environ, BAZ_BENCH_CHILD="1", BAZ_BENCH_ATTEMPT=str(attempt), BAZ_BENCH_PREVIOUS_FAILURE=previous)
-        p = subprocess.Popen(cmd, stdout=subprocess.PIPE, text=True, bufsize=1, env=env)        # stderr: inherited
-        for ln in p.stdout:
-            if ln.startswith("{"):
-                state["latest"] = ln if ln.endswith("\n") else ln + "\n"
-            else:
-                sys.stdout.write(ln)
-                sys.stdout.flush()
-        rc = p.wait()
-        if rc >= 0 or state["latest"] is not None or attempt == 2:
-            if rc < 0 and state["latest"] is not None:
-                note("the measuring process was killed by signal %d after its complete line and before the legs' figures: that line is the one printed" % (-rc))
-            put_line()
-            return rc if rc >= 0 else 128 - rc           # (a signal death: the shell's convention, e.g. 134 for SIGABRT)
-        previous = "attempt 1 was killed by signal %d before it printed its line" % (-rc)
-        note("the measuring process was killed by signal %d before it printed anything; starting it once more" % (-rc))
-    return 1
+    p = subprocess.Popen(cmd, stdout=subprocess.PIPE, text=True, bufsize=1, env=dict(os.environ, BAZ_BENCH_CHILD="1"))   # stderr: inherited
+    for ln in p.stdout:
+        if ln.startswith("{"):
+            state["latest"] = ln if ln.endswith("\n") else ln + "\n"
+        else:
+            sys.stdout.write(ln)
+            sys.stdout.flush()
+    rc = p.wait()
+    if rc < 0:
+        note("the measuring process was killed by signal %d %s" % (-rc, "before it printed its line" if state["latest"] is None else
+                                                                     "(the last complete line it printed is the one printed)"))
+    put_line()
+    return rc if rc >= 0 else 128 - rc           # (a signal death: the shell's convention, e.g. 134 for SIGABRT)
 
 
 def self_launch(n):
@@ -745,16 +760,23 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--scaling", choices=("weak", "strong"), default=os.environ.get("BAZ_BENCH_SCALING", "weak"),
                     help="weak: 8 streams per GPU; strong: BASELINE configs[3], the same 64 streams dealt s mod N at every N")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary cfg2-no-spectrum / cfg3 / cfg5 measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, per-stage figures, oracle check, cpu_baseline and secondary legs (default: the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the secondary cfg2-no-spectrum / cfg3 / cfg5 measurements")
     ap.add_argument("--ramp-seconds", type=float, default=0.25, help="untimed steady load before warm-up (clock ramp)")
-    ap.add_argument("--min-seconds", type=float, default=0.5, help="repeat the K-step timed region until this much timed work")
+    ap.add_argument("--min-seconds", type=float, default=None,
+                    help="repeat the K-step timed region until this much timed work (default: 0.5 with --full, else one region)")
     ap.add_argument("--dry-ranks", action="store_true",
                     help="launcher rehearsal without GPU work: N ranks, the dealing, barrier / clock and rank records only")
     ap.add_argument("--extra-leg", default=None, metavar="NAME[,NAME...]",
                     help="child mode: run the named secondary legs in this process (ALL = every leg, in order) and print one JSON object each")
     ap.add_argument("--legs", default=None, metavar="NAME[,NAME...]", help="run only these secondary legs (default: all)")
     args = ap.parse_args()
+    if args.min_seconds is None:
+        args.min_seconds = 0.5 if args.full else 0.0
 
     if args.extra_leg:
         names = LEG_ORDER if args.extra_leg == "ALL" else [n for n in args.extra_leg.split(",") if n]
@@ -764,13 +786,10 @@ def main():
         return self_launch(args.gpus)                        # plain `python bench.py --gpus N`: start the N ranks ourselves
     if args.dry_ranks:
         return dry_ranks_main(args)
-    if (args.gpus <= 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ and os.environ.get("BAZ_BENCH_CHILD") != "1"
+    full = args.full
+    if (full and args.gpus <= 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ and os.environ.get("BAZ_BENCH_CHILD") != "1"
             and os.environ.get("BAZ_BENCH_SUPERVISE", "1") != "0"):
         raise SystemExit(supervise())                        # the measurement in a child of this process (see supervise)
-    inject = os.environ.get("BAZ_BENCH_INJECT_FAULT", "")    # test hook: "abort:headline@1" = the first attempt's measuring process dies
-    if inject == "abort:headline@%s" % os.environ.get("BAZ_BENCH_ATTEMPT", "1"):
-        note("INJECTED FAULT: the measuring process abort()s before its line")
-        os.abort()
 
     import numpy as np
     import torch
@@ -843,8 +862,10 @@ def main():
         step()
     torch.cuda.synchronize()
 
-    # Timed rounds: each is EXACTLY args.steps steps between barrier + synchronize on both sides, max over ranks.
-    ctx.profile(int(os.environ.get("BAZ_BENCH_PROFILE", "2")))   # 2: hipEvents around the dominant kernel only
+    # Timed rounds: each is EXACTLY args.steps steps between barrier + synchronize on both sides, max over ranks; without --full
+    # (and without --min-seconds) there is one.
+    if full:
+        ctx.profile(int(os.environ.get("BAZ_BENCH_PROFILE", "2")))   # 2: hipEvents around the dominant kernel only
     rounds, scan_ms_total, scan_launches, timed_total = [], 0.0, 0, 0.0
     while True:
         sharding.barrier(active, True)
@@ -858,54 +879,60 @@ def main():
         tmax = sharding.max_over_ranks(elapsed, active, True)
         rounds.append(tmax)
         timed_total += tmax
-        sm, sn = ctx.stage_ms(capi.STAGE_SCAN)            # cumulative since profile(): dominant kernel, timed rounds only
-        scan_ms_total, scan_launches = sm, sn
+        if full:
+            sm, sn = ctx.stage_ms(capi.STAGE_SCAN)        # cumulative since profile(): dominant kernel, timed rounds only
+            scan_ms_total, scan_launches = sm, sn
         if timed_total >= args.min_seconds or len(rounds) >= 200:
             break
-    ctx.profile(False)
-    # informational per-stage breakdown from a separate short pass (events around every kernel add launch gaps,
-    # so they stay out of the timed region)
-    ctx.profile(1)
-    for _ in range(3):
-        step()
-    torch.cuda.synchronize()
-    stage = [ctx.stage_ms(s) for s in range(capi.NUM_STAGES)]
-    ctx.profile(False)
-    cov_name = ctx.stage_name(capi.STAGE_COV)
-    scan_name = ctx.stage_name(capi.STAGE_SCAN)
-    bpi = ctx.bytes_per_item(True)
-    # outside the timed region: what the last timed step left in the output buffers against the CPU oracle, then the cost of
-    # a retune (set_array_response) while batches are in flight
-    note("headline timed (%d rounds of %d steps); checking the last step's outputs against the oracle" % (len(rounds), args.steps))
-    verified = verify_against_oracle(torch, np, x, ang, lvl, spec, table, M, N_EMIT, NSAMPLES, RES, 256)
-    # (the cost of a retune beside the headline's steps is measured by the leg cfg2_retune_in_flight, in its own process)
+    # what the last timed step left in the output buffers, before anything below runs the engine again or overwrites them
+    dumped = dump_outputs(args.dump_outputs, torch, np, ang, lvl, spec, rank, world) if args.dump_outputs else None
+    if full:
+        ctx.profile(False)
+        # informational per-stage breakdown from a separate short pass (events around every kernel add launch gaps,
+        # so they stay out of the timed region)
+        ctx.profile(1)
+        for _ in range(3):
+            step()
+        torch.cuda.synchronize()
+        stage = [ctx.stage_ms(s) for s in range(capi.NUM_STAGES)]
+        ctx.profile(False)
+        cov_name = ctx.stage_name(capi.STAGE_COV)
+        scan_name = ctx.stage_name(capi.STAGE_SCAN)
+        bpi = ctx.bytes_per_item(True)
+        # outside the timed region: what the last timed step left in the output buffers against the CPU oracle (the separate pass
+        # above recomputed the same outputs from the same inputs)
+        note("headline timed (%d rounds of %d steps); checking the last step's outputs against the oracle" % (len(rounds), args.steps))
+        verified = verify_against_oracle(torch, np, x, ang, lvl, spec, table, M, N_EMIT, NSAMPLES, RES, 256)
+        # (the cost of a retune beside the headline's steps is measured by the leg cfg2_retune_in_flight, in its own process)
     ctx.set_stream(None)
     ctx.close()
-    # What this box's memory system takes for a plain write of the same 3.78 GB (a torch fill of the spectrum buffer; hipEvents on the bench
-    # stream, outside the timed region, AFTER the outputs have been checked: it overwrites them): the dominant kernel is bound by its spectrum stores, and boxes of this pool differ by 20 % in exactly
-    # that -- the roofline fraction against the 8 TB/s peak does not say how far the kernel is from what can be had.
     write_ceiling_gbs = None
-    try:
-        sp_one = spec[:group_items]
-        with torch.cuda.stream(stream):
-            for _ in range(3):
-                sp_one.fill_(1.0)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            for _ in range(10):
-                sp_one.fill_(1.0)
-            e1.record(stream)
-        stream.synchronize()
-        write_ceiling_gbs = sp_one.numel() * 4 * 10 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-    except Exception:
-        pass
+    if full:
+        # What this box's memory system takes for a plain write of the same 3.78 GB (a torch fill of the spectrum buffer; hipEvents on the bench
+        # stream, outside the timed region, AFTER the outputs have been checked: it overwrites them): the dominant kernel is bound by its spectrum stores, and boxes of this pool differ by 20 % in exactly
+        # that -- the roofline fraction against the 8 TB/s peak does not say how far the kernel is from what can be had.
+        try:
+            sp_one = spec[:group_items]
+            with torch.cuda.stream(stream):
+                for _ in range(3):
+                    sp_one.fill_(1.0)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                for _ in range(10):
+                    sp_one.fill_(1.0)
+                e1.record(stream)
+            stream.synchronize()
+            write_ceiling_gbs = sp_one.numel() * 4 * 10 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+        except Exception:
+            pass
 
     t_med = statistics.median(rounds)
     total_items = sharding.sum_over_ranks(float(batch * args.steps), active, True)
     value = total_items / t_med
-    ranks = [{"rank": rank, "items_per_step": batch, "streams": mine, "device": torch.cuda.get_device_name(local_rank),
-              "verified_items": verified["verified_items"], "verified_max_rel_err": verified["verified_max_rel_err"],
-              "verified_bins_identical": verified["verified_bins_identical"], "verified_ok": verified["verified_ok"]}]
+    ranks = [{"rank": rank, "items_per_step": batch, "streams": mine, "device": torch.cuda.get_device_name(local_rank)}]
+    if full:
+        ranks[0].update({"verified_items": verified["verified_items"], "verified_max_rel_err": verified["verified_max_rel_err"],
+                         "verified_bins_identical": verified["verified_bins_identical"], "verified_ok": verified["verified_ok"]})
     if active:
         import torch.distributed as dist
         gathered = [None] * world
@@ -914,6 +941,30 @@ def main():
     assert len(ranks) == world and sorted(r["rank"] for r in ranks) == list(range(world)), ranks
 
     if rank == 0:
+        per_round = [t / args.steps * 1e3 for t in rounds]
+        line = {
+            "metric": "MUSIC-DoA snapshots/s (4 ant, 1024 samp, 3600 bins)",
+            "value": value, "unit": "snapshots/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": t_med / args.steps * 1e3, "higher_is_better": True, "scaling": args.scaling,
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": full,
+            "rounds": {"count": len(rounds), "steps_each": args.steps, "statistic": "median",
+                       "ms_per_step_min": min(per_round), "ms_per_step_max": max(per_round),
+                       "timed_seconds_total": timed_total},
+            "config": {"workload": "cfg2 (BASELINE.json configs[1]): m=4 n=2 nsamples=1024 (K=256) resolution=3600, "
+                                   "spectrum port wired, %d streams x %d items per GPU per step, device-resident%s"
+                                   % (len(mine), ITEMS_PER_STREAM,
+                                      " (configs[3]: the same %d streams at every GPU count, dealt s mod N)" % STRONG_STREAMS if strong else ""),
+                       "items_per_gpu_per_step": batch, "items_per_step_all_gpus": int(total_items / args.steps + 0.5),
+                       "streams_total": n_streams, "launch_sequences_per_step": n_groups, "items_per_launch_sequence": group_items,
+                       "parallelism": "independent streams, s mod %d, no collective" % world,
+                       "collective_backend_for_barrier_and_clock": backend,
+                       "collective_backend_requested": binfo["requested"], "collective_backend_fell_back": binfo["fell_back"],
+                       "collective_backend_fallback_reason": binfo["fallback_reason"], "ranks": ranks},
+        }
+        if dumped is not None:
+            line["outputs_dumped"] = dumped
+        cfgd = line["config"]
+    if rank == 0 and full:
         scan_avg_s = scan_ms_total / max(scan_launches, 1) * 1e-3
         scan_bytes = (4 * RES + 8 * N_EMIT) * group_items           # spectrum + ang/lvl-equivalent written per launch
         achieved = scan_bytes / scan_avg_s / 1e9 if scan_avg_s > 0 else 0.0
@@ -944,75 +995,57 @@ def main():
                              "instructions; dwordx4 input stream; HBM-read bound while it streams") if x4 else
                             ("16x16x4 fp64 MFMA tiles hold 2 items block-diagonally at m=4 (half the issued flops are "
                              "structural zeros); the kernel is HBM-read bound")}
-        per_round = [t / args.steps * 1e3 for t in rounds]
-        line = {
-            "metric": "MUSIC-DoA snapshots/s (4 ant, 1024 samp, 3600 bins)",
-            "value": value, "unit": "snapshots/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": t_med / args.steps * 1e3, "higher_is_better": True, "scaling": args.scaling,
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "rounds": {"count": len(rounds), "steps_each": args.steps, "statistic": "median",
-                       "ms_per_step_min": min(per_round), "ms_per_step_max": max(per_round),
-                       "timed_seconds_total": timed_total},
-            "kernel_sources_sha": src_sha,
-            "config": {"workload": "cfg2 (BASELINE.json configs[1]): m=4 n=2 nsamples=1024 (K=256) resolution=3600, "
-                                   "spectrum port wired, %d streams x %d items per GPU per step, device-resident%s"
-                                   % (len(mine), ITEMS_PER_STREAM,
-                                      " (configs[3]: the same %d streams at every GPU count, dealt s mod N)" % STRONG_STREAMS if strong else ""),
-                       "items_per_gpu_per_step": batch, "items_per_step_all_gpus": int(total_items / args.steps + 0.5),
-                       "streams_total": n_streams, "launch_sequences_per_step": n_groups, "items_per_launch_sequence": group_items,
-                       "parallelism": "independent streams, s mod %d, no collective" % world,
-                       "collective_backend_for_barrier_and_clock": backend,
-                       "collective_backend_requested": binfo["requested"], "collective_backend_fell_back": binfo["fell_back"],
-                       "collective_backend_fallback_reason": binfo["fallback_reason"], "ranks": ranks,
-                       "algorithmic_bytes_per_item": bpi,
-                       "headline_attempt": int(os.environ.get("BAZ_BENCH_ATTEMPT", "1")),
-                       "headline_previous_failure": os.environ.get("BAZ_BENCH_PREVIOUS_FAILURE") or None,
-                       # every rank checked a sample of what its last timed step wrote against the CPU oracle (outside the timed region)
-                       "verified_items": sum(r["verified_items"] for r in ranks),
-                       "verified_max_rel_err": max(r["verified_max_rel_err"] for r in ranks),
-                       "verified_bins_identical": all(r["verified_bins_identical"] for r in ranks),
-                       "verified_ok": all(r["verified_ok"] for r in ranks),
-                       "verified_tolerance": VERIFY_TOL, "verified_against": verified["verified_against"],
-                       "pipeline_hbm_fraction_of_8TBs": value / world * bpi / 8e12,
-                       "stage_ms_per_launch_separate_pass": {nm: stage[s][0] / max(stage[s][1], 1)
-                                               for s, nm in enumerate(("cov (+ evd when fused)", "evd_proj", "scan_mfma", "topn_merge"))},
-                       # the one dense contraction (north_star): useful fp64 flops 8*m*N per item against the fp64
-                       # matrix peak; rocprofv3 MFMA-busy for the same kernel is in profiles/r04_bench_pmc_summary.txt
-                       "covariance_mfma": cov_mfma},
-            "roofline": {"bound": "hbm", "kernel": scan_name.split("::")[-1].split("<")[0], "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_stale": traffic_stale, "traffic_profile": traffic_src,
-                         "algorithmic_bytes_per_launch": scan_bytes, "avg_launch_ms": scan_avg_s * 1e3,
-                         "launches": scan_launches,
-                         # the same bytes as a plain fill on this box in this run (context, not a peak): see write_ceiling above
-                         "plain_fill_of_the_same_bytes_GBs": write_ceiling_gbs,
-                         "achieved_over_plain_fill": (achieved / write_ceiling_gbs) if write_ceiling_gbs else None},
-        }
-        cfgd = line["config"]
-        if world == 1 and not args.no_cpu_baseline:
+        line["kernel_sources_sha"] = src_sha
+        cfgd.update({
+            "algorithmic_bytes_per_item": bpi,
+            "headline_attempt": 1,                                  # (kept for readers of older lines: the measuring process is never restarted)
+            "headline_previous_failure": None,
+            # every rank checked a sample of what its last timed step wrote against the CPU oracle (outside the timed region)
+            "verified_items": sum(r["verified_items"] for r in ranks),
+            "verified_max_rel_err": max(r["verified_max_rel_err"] for r in ranks),
+            "verified_bins_identical": all(r["verified_bins_identical"] for r in ranks),
+            "verified_ok": all(r["verified_ok"] for r in ranks),
+            "verified_tolerance": VERIFY_TOL, "verified_against": verified["verified_against"],
+            "pipeline_hbm_fraction_of_8TBs": value / world * bpi / 8e12,
+            "stage_ms_per_launch_separate_pass": {nm: stage[s][0] / max(stage[s][1], 1)
+                                                  for s, nm in enumerate(("cov (+ evd when fused)", "evd_proj", "scan_mfma", "topn_merge"))},
+            # the one dense contraction (north_star): useful fp64 flops 8*m*N per item against the fp64
+            # matrix peak; rocprofv3 MFMA-busy for the same kernel is in profiles/r04_bench_pmc_summary.txt
+            "covariance_mfma": cov_mfma})
+        line["roofline"] = {"bound": "hbm", "kernel": scan_name.split("::")[-1].split("<")[0], "achieved": achieved, "peak": HBM_PEAK_GBS,
+                            "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                            "traffic_stale": traffic_stale, "traffic_profile": traffic_src,
+                            "algorithmic_bytes_per_launch": scan_bytes, "avg_launch_ms": scan_avg_s * 1e3,
+                            "launches": scan_launches,
+                            # the same bytes as a plain fill on this box in this run (context, not a peak): see write_ceiling above
+                            "plain_fill_of_the_same_bytes_GBs": write_ceiling_gbs,
+                            "achieved_over_plain_fill": (achieved / write_ceiling_gbs) if write_ceiling_gbs else None}
+    if rank == 0:
+        if full and world == 1 and not args.no_cpu_baseline:
             note("cpu baseline (oracle on the host cores)")
             try:
                 line["cpu_baseline"] = cpu_baseline(table)
             except Exception as e:               # (never seen; the line still goes out, and says why the object is missing)
                 line["cpu_baseline"] = {"value": None, "unit": "snapshots/s", "cores": 0, "kind": "port", "sample": "failed", "error": repr(e)}
         legs = []
-        if world == 1 and not args.no_extras:
+        if full and world == 1 and not args.no_extras:
             legs = [n for n in (args.legs.split(",") if args.legs else LEG_ORDER) if n]
             unknown = [n for n in legs if n not in LEG_ORDER]
             if unknown:
                 raise SystemExit("unknown leg(s) %s (known: %s)" % (unknown, ", ".join(LEG_ORDER)))
-        cfgd["extras_pending"] = len(legs)
+        if full:
+            cfgd["extras_pending"] = len(legs)
         # THE LINE, complete (metric, roofline, cpu_baseline, verified_*), before any secondary leg runs: whatever happens below cannot take it
         # back.  Without legs it is the one line of the contract.  With legs to run, the same line follows once more, enriched with their figures,
-        # and exactly ONE of the two reaches the caller's stdout: supervised (plain `python bench.py`, see supervise()) both go to the parent, which
+        # and exactly ONE of the two reaches the caller's stdout: supervised (`python bench.py --full`, see supervise()) both go to the parent, which
         # prints the last one it has got; unsupervised the early copy goes to stderr only.
         if not legs or os.environ.get("BAZ_BENCH_CHILD") == "1":
             print(json.dumps(line), flush=True)
         if legs:
             print("bench.py: [%.1f s] complete line before the legs: %s" % (time.perf_counter() - T_START, json.dumps(line)), file=sys.stderr, flush=True)
-            if os.environ.get("BAZ_BENCH_INJECT_FAULT", "") == "abort:after_first_line":      # test hook
-                note("INJECTED FAULT: the measuring process abort()s after its complete line, before the legs")
-                os.abort()
+            if os.environ.get("BAZ_BENCH_INJECT_FAULT", "") == "raise:after_first_line":      # test hook
+                note("INJECTED FAILURE: the measuring process raises after its complete line, before the legs")
+                raise RuntimeError("injected failure after the first line")
         if legs:
             # this process keeps nothing on the device while the legs run (they are sized for a whole GPU)
             del x, spec, ang, lvl
@@ -1065,7 +1098,7 @@ def main():
             cfgd["extras_pending"] = 0
             cfgd["extra"] = extra
             print(json.dumps(line), flush=True)
-        failed = not cfgd["verified_ok"]           # the exit code speaks for the HEADLINE only (legs report through extras_failed / extras_all_verified_ok)
+        failed = full and not cfgd["verified_ok"]  # the exit code speaks for the HEADLINE only (legs report through extras_failed / extras_all_verified_ok)
     else:
         failed = False
     if active:

@@ -6,7 +6,7 @@ set -u
 TAG=${1:-r03z}; HEAD=${2:-unknown}; P=${3:-r03}
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --no-cpu-baseline --no-extras"
+B="python $R/bench.py --full --no-cpu-baseline --no-extras"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- $B --steps 20 --warmup 3 > $O/stats_bench_line.json 2> $O/stats_err.txt
 PM="--steps 3 --warmup 1 --ramp-seconds 0 --min-seconds 0"
 rocprofv3 --pmc WRITE_SIZE GRBM_GUI_ACTIVE --output-format csv -d $O/pmc_write -o bench -- $B $PM > /dev/null 2> $O/pmc_write_err.txt
@@ -19,7 +19,7 @@ cp "$K" $O/bench_kernel_stats.csv 2>/dev/null
 python scripts/pmc_summary.py "$W" "$F" "$S" > $O/bench_pmc_summary.txt 2>&1
 python scripts/pmc_traffic.py "$W" "$F" $O/scan_pmc_traffic.json $HEAD > $O/pmc_traffic_out.txt 2>&1
 cp $O/scan_pmc_traffic.json profiles/${P}_scan_pmc_traffic.json      # so that the bench run below reports it
-python bench.py --steps 20 --warmup 3 > $O/bench_line.json 2> $O/bench_err.txt
+python bench.py --full --steps 20 --warmup 3 > $O/bench_line.json 2> $O/bench_err.txt
 # raw counter rows of the product's kernels, kept beside the summaries (tests/test_evidence.py recomputes the traffic from them)
 P=$P python - "$W" "$F" "$S" <<'PY'
 import csv, os, sys

@@ -38,7 +38,7 @@ write_b = w_kib * 1024.0
 fetch_b = 2.0 * f_kib * 1024.0
 info = {
     "source": "rocprofv3 --pmc WRITE_SIZE / --pmc FETCH_SIZE (separate passes, --kernel-trace off) of "
-              "`python bench.py --no-cpu-baseline --no-extras --steps 3 --warmup 1 --ramp-seconds 0 --min-seconds 0`",
+              "`python bench.py --full --no-cpu-baseline --no-extras --steps 3 --warmup 1 --ramp-seconds 0 --min-seconds 0`",
     "kernel": kname.replace("void bazmusic::", ""),
     "items_per_launch": batch,
     "dispatches_averaged": {"write_pass": nw, "fetch_pass": nf},

@@ -124,7 +124,7 @@ def test_rccl_really_initialises_under_the_bench(gpu_device):
     RCCL).  What CAN run on the 1-GPU box is the RCCL side of it with a group of one rank (BAZ_BENCH_FORCE_DIST=1): the communicator is
     created on the device, the barrier (device_ids) and the max / sum all-reduces of the clock run on GPU tensors through RCCL, the rank
     records are gathered -- and the line says nccl, not a fall-back."""
-    r, d = _bench("--gpus", "1", "--steps", "3", "--warmup", "2", "--no-extras", "--no-cpu-baseline", "--min-seconds", "0.2",
+    r, d = _bench("--gpus", "1", "--steps", "3", "--warmup", "2", "--full", "--no-extras", "--no-cpu-baseline", "--min-seconds", "0.2",
                   env={"BAZ_BENCH_FORCE_DIST": "1"})
     assert r.returncode == 0 and d is not None, r.stderr[-2000:]
     c = d["config"]
