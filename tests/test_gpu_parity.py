@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import golden_names, load_golden
-from helpers import assert_doa_match, assert_spectrum_close
+from helpers import assert_doa_match, assert_doa_within_bound, assert_spectrum_close, assert_spectrum_within_bound, oracle_fp64
 from oracle import music_oracle as mo
 from oracle import music_ref as mr
 
@@ -39,6 +39,21 @@ def device_run(ctx, items, gpu_device, want_lvl=True, want_spec=True):
             spec.cpu().numpy() if want_spec else None)
 
 
+def scan_path(ctx):
+    """the error-bound class of the scan the context's last call ran (tests/helpers.py, path_term)"""
+    return "int8" if ctx.stage_name(2).startswith("bazmusic::scan_i8_kernel") else "fp64"
+
+
+def assert_within_bound(items, table, m, n, path, ang, lvl, spec, snr=None):
+    """spectrum, lvl and ang against the fp64 oracle at min(1e-5, path_term + cond_term); at SNR <= 40 dB at least 90 % of
+    the values must be held to <= 2e-6 (the bound is not vacuous)"""
+    ao, _, _, s64, w = oracle_fp64(items, table, m, n)
+    _, tight, _ = assert_spectrum_within_bound(spec, s64, path, m, n, table, w)
+    assert_doa_within_bound(ang, lvl, ao, s64, path, m, n, table, w)
+    if snr is not None and snr <= 40.0:
+        assert tight >= 0.9, tight
+
+
 # ------------------------------------------------------------------ golden vectors
 @pytest.mark.parametrize("name", golden_names())
 def test_hip_matches_golden_device_path(name, gpu_device):
@@ -55,8 +70,10 @@ def test_hip_matches_golden_host_path(name, gpu_device):
     g = load_golden(name)
     with _capi().Context(g["m"], g["n"], g["nsamples"], g["res"], g["table"]) as ctx:
         ang, lvl, spec = ctx.process(g["items"])
+        path = scan_path(ctx)
     assert_spectrum_close(spec, g["spectrum"])
     assert_doa_match(ang, lvl, g["ang"], g["lvl"], g["res"], g["strength64"])
+    assert_within_bound(g["items"], g["table"], g["m"], g["n"], path, ang, lvl, spec)
 
 
 # ------------------------------------------------------------------ seeded inputs vs the oracle
@@ -67,8 +84,10 @@ def test_hip_matches_oracle_on_seeded_batches(cfg, batch, snr, gpu_device):
     ao, lo, so, st = mo.music_doa_work_batch(c["items"], c["table"], c["m"], c["n"])
     with _capi().Context(c["m"], c["n"], c["nsamples"], c["res"], c["table"]) as ctx:
         ang, lvl, spec = device_run(ctx, c["items"], gpu_device)
+        path = scan_path(ctx)
     assert_spectrum_close(spec, so)
     assert_doa_match(ang, lvl, ao, lo, c["res"], st)
+    assert_within_bound(c["items"], c["table"], c["m"], c["n"], path, ang, lvl, spec, snr=snr)
 
 
 def test_stage_taps_covariance_and_projector(gpu_device):
@@ -131,9 +150,11 @@ def test_hip_matches_oracle_on_odd_shapes(m, n, N, res, batch, gpu_device):
     ao, lo, so, st = mo.music_doa_work_batch(items, table, m, n)
     with _capi().Context(m, n, N, res, table) as ctx:
         ang, lvl, spec = device_run(ctx, items, gpu_device)
+        path = scan_path(ctx)
         a2, l2, s2 = ctx.process(items)
     assert_spectrum_close(spec, so)
     assert_doa_match(ang, lvl, ao, lo, res, st)
+    assert_within_bound(items, table, m, n, path, ang, lvl, spec, snr=20.0)
     assert np.array_equal(a2, ang) and np.array_equal(l2, lvl) and np.array_equal(s2, spec)
 
 
@@ -167,6 +188,7 @@ def test_wide_arrays_match_the_oracle(m, n, N, res, batch, gpu_device):
         assert ctx.refined_values() >= 0          # (counted by the matrix-core scan only: n <= 8)
     assert_spectrum_close(spec, so)
     assert_doa_match(ang, lvl, ao, lo, res, st)
+    assert_within_bound(items, table, m, n, "fp64", ang, lvl, spec, snr=20.0)
     assert np.array_equal(a1, ang)
     assert np.array_equal(a2, ang) and np.array_equal(l2, lvl) and np.array_equal(s2, spec)
     xs = items.astype(np.complex128).reshape(batch, N // m, m).transpose(0, 2, 1)
@@ -619,6 +641,7 @@ def test_extreme_snr_spectra_match_the_literal_form(m, n, K, res, batch, snr, se
     ao, lo, so = mr.work_batch(items, table, m, n)
     with _capi().Context(m, n, m * K, res, table) as ctx:
         ang, lvl, spec = device_run(ctx, items, gpu_device)
+        path = scan_path(ctx)
         refined = ctx.refined_items()
         a2, l2, _ = device_run(ctx, items, gpu_device, want_spec=False)
     if float(so.max()) > 2.0 / (m * m * 1e-8):      # some d is clearly below the threshold m*max||a||^2*1e-8
@@ -626,6 +649,7 @@ def test_extreme_snr_spectra_match_the_literal_form(m, n, K, res, batch, snr, se
     assert_spectrum_close(spec, so)
     assert_doa_match(ang, lvl, ao, lo, res, so.astype(np.float64))
     assert_doa_match(a2, l2, ao, lo, res, so.astype(np.float64))
+    assert_within_bound(items, table, m, n, path, ang, lvl, spec)
     bins = np.round(ang * res / 360.0).astype(int) % res
     assert np.array_equal(lvl, np.take_along_axis(spec, bins, axis=1))      # lvl[i] == spectrum[bin_i] also after refinement
 
