@@ -130,6 +130,12 @@ def _retune(h, frequency):
     h.impl.set_array_response(h.array_response)
 
 
+def _set_smoothing(h, subarray, forward_backward):
+    # EXTENSION, no reference counterpart: forward-backward averaging / spatial smoothing of the covariance (coherent
+    # emitters), see include/baz_music_hip.h.  Stays in force across set_frequency(): a retuned ULA is still a ULA.
+    h.impl.set_smoothing(int(subarray), bool(forward_backward))
+
+
 if _HAVE_GR:
 
     class music_doa_helper(gr.hier_block2):
@@ -154,6 +160,11 @@ if _HAVE_GR:
         def set_frequency(self, frequency):
             _retune(self, frequency)
 
+        def set_smoothing(self, subarray, forward_backward=False):
+            """Opt-in (not reference behaviour): FB averaging and/or smoothing over `subarray`-element subarrays;
+            set_smoothing(m) switches it off.  Raises ValueError when the array response does not allow it."""
+            _set_smoothing(self, subarray, forward_backward)
+
 else:
 
     class music_doa_helper(object):
@@ -171,6 +182,11 @@ else:
 
         def set_frequency(self, frequency):
             _retune(self, frequency)
+
+        def set_smoothing(self, subarray, forward_backward=False):
+            """Opt-in (not reference behaviour): FB averaging and/or smoothing over `subarray`-element subarrays;
+            set_smoothing(m) switches it off.  Raises ValueError when the array response does not allow it."""
+            _set_smoothing(self, subarray, forward_backward)
 
         def work(self, items):
             """Runs the wrapped block on (k, nsamples) complex64 items: returns (ang, lvl[, spectrum])."""

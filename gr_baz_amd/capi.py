@@ -35,7 +35,9 @@ SYMBOLS = [
     "baz_music_debug_i8_margin", "baz_music_debug_i8_stats", "baz_music_uses_i8_scan", "baz_music_debug_i8_image",
     "baz_music_debug_i8_nsplit", "baz_music_debug_sort_state", "baz_music_last_retune_ms", "baz_music_debug_table_image", "baz_music_debug_host_table_image",
     "baz_music_debug_guard_check", "baz_music_debug_guard_active",
+    "baz_music_set_smoothing", "baz_music_get_smoothing", "baz_music_smoothing_check",
 ]
+SMOOTH_WORKSPACE_BYTES = 128 << 20  # BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES: re-stacked items per chunk while smoothing is on
 
 _vp = ctypes.c_void_p
 _u32 = ctypes.c_uint32
@@ -162,6 +164,12 @@ def _bind(L):
     L.baz_music_debug_table_image.argtypes = [_vp, ctypes.c_int, _vp, ctypes.c_size_t]
     L.baz_music_debug_host_table_image.restype = ctypes.c_size_t
     L.baz_music_debug_host_table_image.argtypes = [_u32, _u32, _u32, _f32p, ctypes.c_int, _vp, ctypes.c_size_t]
+    L.baz_music_set_smoothing.restype = ctypes.c_int
+    L.baz_music_set_smoothing.argtypes = [_vp, _u32, ctypes.c_int]
+    L.baz_music_get_smoothing.restype = ctypes.c_int
+    L.baz_music_get_smoothing.argtypes = [_vp, ctypes.POINTER(_u32), ctypes.POINTER(ctypes.c_int)]
+    L.baz_music_smoothing_check.restype = ctypes.c_int
+    L.baz_music_smoothing_check.argtypes = [_u32, _u32, _f32p, _u32, ctypes.c_int, ctypes.POINTER(ctypes.c_uint8)]
     return L
 
 
@@ -335,6 +343,18 @@ class Context:
         """0: the reference's n strongest bins (default); 1: n strongest local maxima (opt-in extension)."""
         self._chk(self._L.baz_music_set_peak_mode(self._h, int(mode)), "baz_music_set_peak_mode")
 
+    def set_smoothing(self, subarray, forward_backward=False):
+        """Opt-in extension (not reference behaviour): forward-backward averaging and/or spatial smoothing over subarrays of
+        `subarray` elements (include/baz_music_hip.h).  set_smoothing(m, False) switches it off."""
+        self._chk(self._L.baz_music_set_smoothing(self._h, int(subarray), 1 if forward_backward else 0),
+                  "baz_music_set_smoothing")
+
+    def get_smoothing(self):
+        """(subarray, forward_backward) in force; (m, False) while the mode is off."""
+        ms, fb = _u32(0), ctypes.c_int(0)
+        self._chk(self._L.baz_music_get_smoothing(self._h, ctypes.byref(ms), ctypes.byref(fb)), "baz_music_get_smoothing")
+        return int(ms.value), bool(fb.value)
+
     def set_stream(self, hip_stream):
         self._chk(self._L.baz_music_set_stream(self._h, _vp(hip_stream) if hip_stream else None),
                   "baz_music_set_stream")
@@ -387,6 +407,16 @@ def debug_i8_image(m, resolution, table):
                                    par.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
     return img, {"wt": par[:7].copy(), "sq": par[7], "t_acc": par[8], "e_bound": par[9], "e_refined": par[10],
                  "ns": int(par[11]), "nd": int(par[12]), "e4_bound": par[13], "t4": par[14]}
+
+
+def smoothing_check(m, resolution, table, subarray, forward_backward=False):
+    """HOST-ONLY: the structure checks of baz_music_set_smoothing on `table` (needs no device).  Returns the involution of the
+    subarray's elements (uint8 array, the identity without FB) when the table passes, None when it does not."""
+    t = _table_f32(table, int(resolution), int(m))
+    perm = np.zeros(max(int(subarray), 1), np.uint8)
+    r = lib().baz_music_smoothing_check(int(m), int(resolution), t.view(np.float32).ctypes.data_as(_f32p), int(subarray),
+                                        1 if forward_backward else 0, perm.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+    return perm if r == OK else None
 
 
 TABLE_IMAGES = {0: "FB", 1: "TB", 2: "coarse", 3: "i8", 4: "a2p", 5: "TA", 6: "a2", 7: "params", 8: "i8 packed (m <= 4)"}

@@ -14,6 +14,7 @@
 #include "sort_kernels.hip.h"
 #endif
 #include "table_kernels.hip.h"
+#include "smoothing_kernels.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -306,6 +307,22 @@ struct baz_music_ctx {
     char scan_names[4][64] = {{0}, {0}, {0}, {0}};   // baz_music_stage_name(SCAN) by scan_kind, written once by baz_music_create
     int scan_kind = -1;     // the scan kernel the LAST launch took: 0 scan_mfma_kernel, 1 scan_i8_kernel, 2 scan_coarse_kernel, 3 scan_i8p_kernel (-1: none yet)
     char hip_err[256] = {0};
+    // Opt-in forward-backward averaging / spatial smoothing (baz_music_set_smoothing; NOT reference behaviour).  While `inner` is
+    // set, every process* call re-stacks its items (smoothing_kernels.hip.h) into `dY` and runs them through `inner`, a context of
+    // shape (ms, n, ms K', res) on the first ms columns of the table, launching on this context's stream.  Null: off -- none of the
+    // mode's code runs and every other member keeps the reference's behaviour.  Changed under `tab_mtx` + `mtx`.
+    struct Smoothing {
+        baz_music_ctx* inner = nullptr;
+        uint32_t ms = 0, L = 1, Kp = 0;          // subarray size, subarrays, columns of a re-stacked item
+        int fb = 0;
+        bazsmooth::Perm perm = {};
+        float2* dY = nullptr;                    // re-stacked chunk (BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES)
+        size_t y_cap = 0;                        // complex values
+        float* dX = nullptr;                     // host path: the chunk's input ...
+        float* dAl = nullptr;                    // ... its ang | lvl ...
+        float* dSpec = nullptr;                  // ... and its spectrum on the device
+        size_t x_cap = 0, al_cap = 0, spec_cap = 0;   // floats
+    } sm;
 };
 
 namespace {
@@ -2109,6 +2126,220 @@ int create_tables(baz_music_ctx* c, const float* table_ri)
     return r;
 }
 
+// ---- opt-in forward-backward averaging / spatial smoothing (baz_music_set_smoothing) ------------------------------------------
+// Structure checks on the fp32 table (include/baz_music_hip.h documents them).  Every product is formed in fp64 from the fp32
+// entries; a relation holds at a bin when its residual is at most SMOOTH_TOL times the bin's scale s = max_k |a_k|^2.
+constexpr double SMOOTH_TOL = 1e-5;
+constexpr uint32_t SMOOTH_SCREEN_BINS = 32;   // bins the FB involution is screened on before it is verified on every bin
+
+struct Cd { double re, im; };
+inline Cd tab_at(const float* t, uint32_t m, uint32_t b, uint32_t i) { return {t[2 * ((size_t)b * m + i)], t[2 * ((size_t)b * m + i) + 1]}; }
+inline Cd cmul(Cd a, Cd b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
+inline Cd cmulc(Cd a, Cd b) { return {a.re * b.re + a.im * b.im, a.re * b.im - a.im * b.re}; }   // conj(a) b
+inline double dist2(Cd a, Cd b) { const double x = a.re - b.re, y = a.im - b.im; return x * x + y * y; }
+inline double abs2(Cd a) { return a.re * a.re + a.im * a.im; }
+
+double bin_scale(const float* t, uint32_t m, uint32_t cols, uint32_t b)
+{
+    double s = 0.0;
+    for (uint32_t k = 0; k < cols; ++k) s = std::max(s, abs2(tab_at(t, m, b, k)));
+    return s;
+}
+
+// SS: a_{i+l} a_0 == a_i a_l for i < ms, 1 <= l < L, every bin (O(res ms L))
+bool shift_invariant(const float* t, uint32_t m, uint32_t res, uint32_t ms)
+{
+    const uint32_t L = m - ms + 1;
+    for (uint32_t b = 0; b < res; ++b) {
+        const double s = bin_scale(t, m, m, b), lim = SMOOTH_TOL * SMOOTH_TOL * s * s;
+        if (!(s < INFINITY)) return false;
+        const Cd a0 = tab_at(t, m, b, 0);
+        for (uint32_t l = 1; l < L; ++l) {
+            const Cd al = tab_at(t, m, b, l);
+            for (uint32_t i = 1; i < ms; ++i)
+                if (!(dist2(cmul(tab_at(t, m, b, i + l), a0), cmul(tab_at(t, m, b, i), al)) <= lim)) return false;
+        }
+    }
+    return true;
+}
+
+// FB with the candidate involution p, at bin b: conj(a_i) a_p(k) == conj(a_k) a_p(i) for every i, k the bin's largest
+// element -- i.e. conj(a_i) = c a_p(i) with c = conj(a_k) / a_p(k) (i = p(k) makes |a_p(k)| = |a_k|, so c exists)
+bool fb_holds_at(const float* t, uint32_t m, uint32_t ms, const uint8_t* p, uint32_t b)
+{
+    uint32_t k = 0;
+    double s = -1.0;
+    for (uint32_t i = 0; i < ms; ++i) { const double v = abs2(tab_at(t, m, b, i)); if (v > s) { s = v; k = i; } }
+    if (!(s < INFINITY)) return false;
+    const double lim = SMOOTH_TOL * SMOOTH_TOL * s * s;
+    const Cd ak = tab_at(t, m, b, k), apk = tab_at(t, m, b, p[k]);
+    for (uint32_t i = 0; i < ms; ++i)
+        if (!(dist2(cmulc(tab_at(t, m, b, i), apk), cmulc(ak, tab_at(t, m, b, p[i]))) <= lim)) return false;
+    return true;
+}
+
+// FB: derive the involution p of the ms subarray elements from the table.  Screen: with k0 the element whose smallest modulus over
+// the screen bins is largest, every candidate p(k0) = j0 fixes p(i) as the first j with conj(a_i) a_j0 == conj(a_k0) a_j on every
+// screen bin (O(ms^3) pair tests, most of them rejected at the first bin).  A candidate that is an involution is then verified on
+// every bin (fb_holds_at: O(ms res)).
+bool derive_involution(const float* t, uint32_t m, uint32_t res, uint32_t ms, uint8_t* perm)
+{
+    const uint32_t S = std::min(res, SMOOTH_SCREEN_BINS);
+    std::vector<uint32_t> sb(S);
+    std::vector<double> lim(S);
+    for (uint32_t s = 0; s < S; ++s) {
+        sb[s] = (uint32_t)(((uint64_t)s * res) / S);
+        const double sc = bin_scale(t, m, ms, sb[s]);
+        if (!(sc < INFINITY)) return false;
+        lim[s] = SMOOTH_TOL * SMOOTH_TOL * sc * sc;
+    }
+    uint32_t k0 = 0;
+    double best = -1.0;
+    for (uint32_t k = 0; k < ms; ++k) {
+        double lo = INFINITY;
+        for (uint32_t s = 0; s < S; ++s) lo = std::min(lo, abs2(tab_at(t, m, sb[s], k)));
+        if (lo > best) { best = lo; k0 = k; }
+    }
+    auto pair_ok = [&](uint32_t i, uint32_t j, uint32_t j0) {
+        for (uint32_t s = 0; s < S; ++s) {
+            const uint32_t b = sb[s];
+            if (!(dist2(cmulc(tab_at(t, m, b, i), tab_at(t, m, b, j0)), cmulc(tab_at(t, m, b, k0), tab_at(t, m, b, j))) <= lim[s]))
+                return false;
+        }
+        return true;
+    };
+    uint8_t p[64];
+    for (uint32_t j0 = 0; j0 < ms; ++j0) {
+        bool ok = true;
+        for (uint32_t i = 0; i < ms && ok; ++i) {
+            uint32_t j = 0;
+            while (j < ms && !pair_ok(i, j, j0)) ++j;
+            ok = j < ms;
+            if (ok) p[i] = (uint8_t)j;
+        }
+        for (uint32_t i = 0; i < ms && ok; ++i) ok = p[p[i]] == i;
+        for (uint32_t b = 0; b < res && ok; ++b) ok = fb_holds_at(t, m, ms, p, b);
+        if (ok) {
+            std::memcpy(perm, p, ms);
+            return true;
+        }
+    }
+    return false;
+}
+
+int smoothing_check(uint32_t m, uint32_t res, const float* table_ri, uint32_t ms, int fb, uint8_t* perm_out)
+{
+    if (!table_ri || m < 2 || m > BAZ_MUSIC_MAX_M || res == 0 || ms < 2 || ms > m) return BAZ_MUSIC_E_INVALID;
+    uint8_t p[64];
+    for (uint32_t i = 0; i < ms; ++i) p[i] = (uint8_t)i;
+    if (ms < m && !shift_invariant(table_ri, m, res, ms)) return BAZ_MUSIC_E_INVALID;
+    if (fb && !derive_involution(table_ri, m, res, ms, p)) return BAZ_MUSIC_E_INVALID;
+    if (perm_out) std::memcpy(perm_out, p, ms);
+    return BAZ_MUSIC_OK;
+}
+
+// the first ms columns of a resolution x m table
+std::vector<float> sub_table(const float* table_ri, uint32_t m, uint32_t res, uint32_t ms)
+{
+    std::vector<float> sub((size_t)res * ms * 2);
+    for (uint32_t b = 0; b < res; ++b)
+        std::memcpy(&sub[(size_t)b * ms * 2], table_ri + (size_t)b * m * 2, (size_t)ms * 2 * sizeof(float));
+    return sub;
+}
+
+void free_smoothing_buffers(baz_music_ctx* c)
+{
+    auto& S = c->sm;
+    if (S.dY) (void)dev_free(S.dY);
+    if (S.dX) (void)dev_free(S.dX);
+    if (S.dAl) (void)dev_free(S.dAl);
+    if (S.dSpec) (void)dev_free(S.dSpec);
+    S.dY = nullptr; S.dX = nullptr; S.dAl = nullptr; S.dSpec = nullptr;
+    S.y_cap = S.x_cap = S.al_cap = S.spec_cap = 0;
+}
+
+// items per chunk: the re-stacked chunk stays within BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES (at least one item)
+uint32_t smooth_chunk(const baz_music_ctx* c, uint32_t batch)
+{
+    const size_t per_item = (size_t)c->sm.Kp * c->sm.ms * sizeof(float2);
+    return (uint32_t)std::max<size_t>(1, std::min<size_t>(batch, (size_t)BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES / per_item));
+}
+
+// grows one device buffer of the mode (the stream is drained first: a batch in flight may still read the old one)
+template <typename T>
+int grow(baz_music_ctx* c, T*& p, size_t& cap, size_t need)
+{
+    if (need <= cap) return BAZ_MUSIC_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (p) (void)dev_free(p);
+    p = nullptr; cap = 0;
+    HIP_TRY(c, dev_malloc((void**)&p, need * sizeof(T)));
+    cap = need;
+    return BAZ_MUSIC_OK;
+}
+
+int launch_restack(baz_music_ctx* c, const void* d_in, uint32_t nb)
+{
+    auto& S = c->sm;
+    bazsmooth::RestackGeom g;
+    g.m = c->m; g.ms = S.ms; g.K = c->K; g.L = S.L; g.per_item = S.Kp * S.ms; g.fb = (uint32_t)S.fb;
+    const uint32_t total = nb * g.per_item;     // <= BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES / 8 (or one item, < 2^31: set_smoothing)
+    const uint32_t pairs = (total + 1u) / 2u;
+    const uint32_t blocks = (pairs + bazsmooth::RESTACK_THREADS - 1u) / bazsmooth::RESTACK_THREADS;
+    bazsmooth::restack_kernel<<<blocks, bazsmooth::RESTACK_THREADS, 0, c->stream>>>(static_cast<const float2*>(d_in), S.dY, g,
+                                                                                     S.perm, total);
+    HIP_TRY(c, hipGetLastError());
+    return BAZ_MUSIC_OK;
+}
+
+// process_device with the mode on (c->mtx held): per chunk, re-stack into dY and run the inner context on the same stream
+int smooth_device_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, void* d_ang, void* d_lvl, void* d_spec)
+{
+    auto& S = c->sm;
+    const uint32_t chunk = smooth_chunk(c, batch);
+    int r = grow(c, S.dY, S.y_cap, (size_t)chunk * S.Kp * S.ms);
+    for (uint32_t done = 0; done < batch && r == BAZ_MUSIC_OK; done += chunk) {
+        const uint32_t nb = std::min(chunk, batch - done);
+        r = launch_restack(c, static_cast<const float2*>(d_in) + (size_t)done * c->nsamples, nb);
+        if (r == BAZ_MUSIC_OK)
+            r = baz_music_process_device(S.inner, S.dY, nb, static_cast<float*>(d_ang) + (size_t)done * c->n,
+                                         d_lvl ? static_cast<float*>(d_lvl) + (size_t)done * c->n : nullptr,
+                                         d_spec ? static_cast<float*>(d_spec) + (size_t)done * c->res : nullptr);
+    }
+    if (r == BAZ_MUSIC_E_HIP && S.inner)
+        snprintf(c->hip_err, sizeof(c->hip_err), "%s", baz_music_last_hip_error(S.inner));
+    return r;
+}
+
+// baz_music_process with the mode on (c->mtx held): the SAME chunks as the device path, staged through device buffers, so the
+// two give the same bits
+int smooth_host_locked(baz_music_ctx* c, const float* in_ri, uint32_t batch, float* ang, float* lvl, float* spectrum)
+{
+    auto& S = c->sm;
+    const uint32_t chunk = smooth_chunk(c, batch);
+    int r = grow(c, S.dX, S.x_cap, (size_t)chunk * c->nsamples * 2);
+    if (r == BAZ_MUSIC_OK) r = grow(c, S.dAl, S.al_cap, (size_t)chunk * c->n * 2);
+    if (r == BAZ_MUSIC_OK && spectrum) r = grow(c, S.dSpec, S.spec_cap, (size_t)chunk * c->res);
+    if (r) return r;
+    for (uint32_t done = 0; done < batch && r == BAZ_MUSIC_OK; done += chunk) {
+        const uint32_t nb = std::min(chunk, batch - done);
+        const size_t cnt = (size_t)nb * c->n;
+        hipError_t e = copy_host_range(S.dX, in_ri + (size_t)done * c->nsamples * 2, (size_t)nb * c->nsamples * 8,
+                                       hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) { r = hip_fail(c, e, "hipMemcpyAsync(in)"); break; }
+        r = smooth_device_locked(c, S.dX, nb, S.dAl, lvl ? S.dAl + cnt : nullptr, spectrum ? S.dSpec : nullptr);
+        if (r == BAZ_MUSIC_OK) e = hipMemcpyAsync(ang + (size_t)done * c->n, S.dAl, cnt * 4, hipMemcpyDeviceToHost, c->stream);
+        if (r == BAZ_MUSIC_OK && e == hipSuccess && lvl)
+            e = hipMemcpyAsync(lvl + (size_t)done * c->n, S.dAl + cnt, cnt * 4, hipMemcpyDeviceToHost, c->stream);
+        if (r == BAZ_MUSIC_OK && e == hipSuccess && spectrum)
+            e = copy_host_range(spectrum + (size_t)done * c->res, S.dSpec, (size_t)nb * c->res * 4, hipMemcpyDeviceToHost, c->stream);
+        const hipError_t es = hipStreamSynchronize(c->stream);   // (also after a failure: no copy may still target the caller)
+        if (r == BAZ_MUSIC_OK && e != hipSuccess) r = hip_fail(c, e, "hipMemcpyAsync(out)");
+        if (r == BAZ_MUSIC_OK && es != hipSuccess) r = hip_fail(c, es, "hipStreamSynchronize");
+    }
+    return r ? r : (int)batch;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2298,7 +2529,10 @@ void baz_music_destroy(baz_music_ctx* c)
     if (!c) return;
     {
         DeviceGuard guard(c->device);
+        if (c->sm.inner) baz_music_destroy(c->sm.inner);   // (drains this context's stream: the inner one launches on it)
+        c->sm.inner = nullptr;
         if (c->stream) (void)hipStreamSynchronize(c->stream);
+        free_smoothing_buffers(c);
         for (auto& p : c->prof)
             for (auto e : p.ev) (void)hipEventDestroy(e);
         if (c->h_al_big) (void)hipHostFree(c->h_al_big);
@@ -2352,7 +2586,17 @@ int baz_music_set_table(baz_music_ctx* c, const float* table_ri)
     if (!c || !table_ri) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> tl(c->tab_mtx);   // one retune at a time; work() is held up for the pointer exchange only (retune())
     DeviceGuard guard(c->device);
-    return retune(c, table_ri, false);
+    if (!c->sm.inner) return retune(c, table_ri, false);
+    // smoothing on: the new table must keep the mode's premise, else nothing changes
+    bazsmooth::Perm perm = {};
+    if (smoothing_check(c->m, c->res, table_ri, c->sm.ms, c->sm.fb, perm.p) != BAZ_MUSIC_OK) return BAZ_MUSIC_E_INVALID;
+    int r = retune(c, table_ri, false);
+    if (r != BAZ_MUSIC_OK) return r;
+    const std::vector<float> sub = sub_table(table_ri, c->m, c->res, c->sm.ms);
+    std::lock_guard<std::mutex> lk(c->mtx);      // the inner table and the involution change between two batches
+    r = baz_music_set_table(c->sm.inner, sub.data());
+    if (r == BAZ_MUSIC_OK) c->sm.perm = perm;
+    return r;
 }
 
 int baz_music_last_retune_ms(baz_music_ctx* c, double* total_ms, double* swap_ms)
@@ -2371,7 +2615,7 @@ int baz_music_set_stream(baz_music_ctx* c, void* hip_stream)
     DeviceGuard guard(c->device);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->own_stream;
-    return BAZ_MUSIC_OK;
+    return c->sm.inner ? baz_music_set_stream(c->sm.inner, c->stream) : BAZ_MUSIC_OK;
 }
 
 int baz_music_sync(baz_music_ctx* c)
@@ -2388,6 +2632,11 @@ int baz_music_reserve(baz_music_ctx* c, uint32_t max_batch)
     std::lock_guard<std::mutex> lk(c->mtx);
     DeviceGuard guard(c->device);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->sm.inner) {   // smoothing on: the inner context's workspace for one chunk, and the re-stacked chunk
+        const uint32_t chunk = smooth_chunk(c, max_batch);
+        const int rs = grow(c, c->sm.dY, c->sm.y_cap, (size_t)chunk * c->sm.Kp * c->sm.ms);
+        return rs ? rs : baz_music_reserve(c->sm.inner, chunk);
+    }
     if (c->wide) {
         const uint32_t pass = std::min(max_batch, wide_pass_items(c));
         const int rw = ensure_wide_workspace(c, pass);
@@ -2411,6 +2660,7 @@ int baz_music_process_device(baz_music_ctx* c, const void* d_in, uint32_t batch,
     std::lock_guard<std::mutex> lk(c->mtx);   // .cc:101
     DeviceGuard guard(c->device);
     (void)hipGetLastError();                  // launches below are checked with hipGetLastError(): start from a clean slate
+    if (c->sm.inner) return smooth_device_locked(c, d_in, batch, d_ang, d_lvl, d_spec);
     int r = begin_statistic(c);
     return r ? r : process_device_locked(c, d_in, batch, d_ang, d_lvl, d_spec);
 }
@@ -2431,8 +2681,13 @@ int baz_music_process_device_on(baz_music_ctx* c, void* caller_stream, const voi
         HIP_TRY(c, hipEventRecord(c->ev_in, cs));
         HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_in, 0));
     }
-    int r = begin_statistic(c);
-    if (r == BAZ_MUSIC_OK) r = process_device_locked(c, d_in, batch, d_ang, d_lvl, d_spec);
+    int r = BAZ_MUSIC_OK;
+    if (c->sm.inner) {
+        r = smooth_device_locked(c, d_in, batch, d_ang, d_lvl, d_spec);
+    } else {
+        r = begin_statistic(c);
+        if (r == BAZ_MUSIC_OK) r = process_device_locked(c, d_in, batch, d_ang, d_lvl, d_spec);
+    }
     if (foreign) {   // also after a failed launch: whatever was enqueued is ordered before the caller's next work
         hipError_t e = hipEventRecord(c->ev_out, c->stream);
         if (e == hipSuccess) e = hipStreamWaitEvent(cs, c->ev_out, 0);
@@ -2455,6 +2710,7 @@ int baz_music_process(baz_music_ctx* c, const float* in_ri, uint32_t batch, floa
         (void)host_register_locked(c, in_ri, (size_t)batch * c->nsamples * 8);
         if (spectrum) (void)host_register_locked(c, spectrum, (size_t)batch * c->res * 4);
     }
+    if (c->sm.inner) return smooth_host_locked(c, in_ri, batch, ang, lvl, spectrum);
     // Cutting a call into chunks (H2D of chunk i+1, the kernels of chunk i and D2H of chunk i-1 overlap on three
     // streams) only pays when a chunk carries enough bytes to hide what the extra copies, events and stream hops cost.
     // Measured under the scheduler model (profiles/r02_flowgraph_model_rates.txt): a 128-item config-2 call (2.9 MB) cut
@@ -2663,6 +2919,7 @@ int baz_music_profile(baz_music_ctx* c, int enable)
 {
     if (!c) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
+    if (c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;
     DeviceGuard guard(c->device);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (enable) {
@@ -2679,6 +2936,7 @@ int baz_music_stage_ms(baz_music_ctx* c, int stage, double* total_ms, uint64_t* 
 {
     if (!c || stage < 0 || stage >= BAZ_MUSIC_NUM_STAGES) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
+    if (c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;
     DeviceGuard guard(c->device);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     prof_collect(c);
@@ -2690,6 +2948,10 @@ int baz_music_stage_ms(baz_music_ctx* c, int stage, double* total_ms, uint64_t* 
 const char* baz_music_stage_name(baz_music_ctx* c, int stage)
 {
     if (!c || stage < 0 || stage >= BAZ_MUSIC_NUM_STAGES) return "";
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);
+        if (c->sm.inner) return "";   // smoothing on: no stage of this context runs (baz_music_set_smoothing)
+    }
     if (stage == BAZ_MUSIC_STAGE_SCAN && !c->wide) {
         // the kernel the LAST scan launch took (it depends on the wiring of the call and on the table in force: ADVICE r4);
         // before the first launch: what a call with the spectrum port would take
@@ -2706,6 +2968,7 @@ int baz_music_debug_cov(baz_music_ctx* c, const void* d_in, uint32_t batch, void
     if (!c || !d_in || !d_R || batch == 0) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
     DeviceGuard guard(c->device);
+    if (c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;
     if (c->wide) return launch_cov_wide(c, static_cast<const float*>(d_in), batch, static_cast<double2*>(d_R));
     if (c->fused_covevd) {   // the product's covariance lives inside the fused kernel: run THAT with its R tap
         int r = ensure_workspace(c, batch);
@@ -2721,7 +2984,7 @@ int baz_music_debug_q(baz_music_ctx* c, const void* d_in, uint32_t batch, void* 
     if (!c || !d_in || !d_Q || batch == 0) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
     DeviceGuard guard(c->device);
-    if (c->wide) return BAZ_MUSIC_E_UNSUPPORTED;   // the wide path forms no projector (literal form straight from G)
+    if (c->wide || c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;   // the wide path forms no projector (literal form straight from G)
     int r = ensure_workspace(c, batch);
     if (r) return r;
     const uint32_t qstride = baz_music_q_stride(batch);
@@ -2739,7 +3002,7 @@ int baz_music_debug_coarse_margin(baz_music_ctx* c, const void* d_in, uint32_t b
     if (!c || !d_in || !worst || batch == 0) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
     DeviceGuard guard(c->device);
-    if (c->wide || c->m > 8 || c->n > 4 || !c->cs_ok) return BAZ_MUSIC_E_UNSUPPORTED;
+    if (c->wide || c->m > 8 || c->n > 4 || !c->cs_ok || c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;
     int r = ensure_workspace(c, batch);
     if (r) return r;
     r = reserve_candidates(c, batch);
@@ -2801,6 +3064,7 @@ int64_t baz_music_debug_coarse_fired(baz_music_ctx* c)
     if (!c || !c->coarse_stats || !c->dMargin) return -1;
     std::lock_guard<std::mutex> lk(c->mtx);
     DeviceGuard guard(c->device);
+    if (c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;
     unsigned long long v = 0;
     if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(&v, c->dMargin, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemsetAsync(c->dMargin, 0, sizeof(v), c->stream) != hipSuccess) return -1;
@@ -2815,6 +3079,7 @@ int baz_music_debug_i8_margin(baz_music_ctx* c, const void* d_in, uint32_t batch
     if (!c || !d_in || !worst || batch == 0) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
     DeviceGuard guard(c->device);
+    if (c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;
 #ifdef BAZ_MUSIC_LAB
     if (!c->wide && c->m <= 4 && c->m >= 2 && c->n <= 4 && c->dIP && c->i8_ok) {
         // 2 .. 4 antennas: the level-packed form (scan_i8p_kernels.hip.h), VAL instantiation, one bin range per row
@@ -2902,7 +3167,7 @@ int baz_music_debug_i8_stats(baz_music_ctx* c, uint64_t* refined_tiles, uint64_t
     if (!c) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
     DeviceGuard guard(c->device);
-    if (!c->dI8Stat) return BAZ_MUSIC_E_UNSUPPORTED;
+    if (!c->dI8Stat || c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;
     unsigned long long v[2] = {0, 0};
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipMemcpy(v, c->dI8Stat, sizeof(v), hipMemcpyDeviceToHost));
@@ -2929,8 +3194,12 @@ extern "C" __attribute__((visibility("default"))) int baz_music_debug_i8_times(b
 #endif
 
 // 1 when this context's scan runs on the int8 matrix core (6 <= m <= 16, n <= 4, a table whose digit image exists, not
-// BAZ_MUSIC_EXACT=1), else 0.
-int baz_music_uses_i8_scan(const baz_music_ctx* c) { return (c && !c->wide && (i8_active(c) || i8p_active(c))) ? 1 : 0; }
+// BAZ_MUSIC_EXACT=1), else 0.  With smoothing on: the answer of the inner context, whose scan runs.
+int baz_music_uses_i8_scan(const baz_music_ctx* c)
+{
+    if (c && c->sm.inner) return baz_music_uses_i8_scan(c->sm.inner);
+    return (c && !c->wide && (i8_active(c) || i8p_active(c))) ? 1 : 0;
+}
 
 // HOST-ONLY tap (no device needed): the bin ranges per item i8_nsplit() chooses for a launch of `batch` items over `nsteps`
 // 64-bin steps on a device with `slots` resident workgroups (CUs x workgroups per CU).
@@ -3152,7 +3421,7 @@ int baz_music_debug_evd(baz_music_ctx* c, const void* d_R, uint32_t batch, void*
     if (!c || !d_R || !d_Q || batch == 0) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
     DeviceGuard guard(c->device);
-    if (c->wide) return BAZ_MUSIC_E_UNSUPPORTED;
+    if (c->wide || c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;
     return launch_evd(c, static_cast<const double2*>(d_R), batch, static_cast<double*>(d_Q), baz_music_q_stride(batch), nullptr);
 }
 
@@ -3225,6 +3494,10 @@ int baz_music_set_peak_mode(baz_music_ctx* c, int mode)
     if (!c || (mode != 0 && mode != 1)) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
     if (mode && c->wide) return BAZ_MUSIC_E_UNSUPPORTED;   // the opt-in picker exists for the specialised kernels only
+    if (c->sm.inner) {   // (the inner context is never wider than this one)
+        const int r = baz_music_set_peak_mode(c->sm.inner, mode);
+        if (r != BAZ_MUSIC_OK) return r;
+    }
     c->peak_mode = mode;
     return BAZ_MUSIC_OK;
 }
@@ -3236,6 +3509,7 @@ int64_t baz_music_refined_values(baz_music_ctx* c)
     if (!c) return -1;
     std::lock_guard<std::mutex> lk(c->mtx);
     DeviceGuard guard(c->device);
+    if (c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;
     if (!c->dRefined) return 0;
     unsigned long long n = 0;
     if (hipStreamSynchronize(c->stream) != hipSuccess ||
@@ -3244,5 +3518,63 @@ int64_t baz_music_refined_values(baz_music_ctx* c)
 }
 
 int baz_music_device(const baz_music_ctx* c) { return c ? c->device : BAZ_MUSIC_E_INVALID; }
+
+int baz_music_smoothing_check(uint32_t m, uint32_t resolution, const float* table_ri, uint32_t subarray, int forward_backward,
+                              uint8_t* perm_out)
+{
+    return smoothing_check(m, resolution, table_ri, subarray, forward_backward ? 1 : 0, perm_out);
+}
+
+int baz_music_set_smoothing(baz_music_ctx* c, uint32_t subarray, int forward_backward)
+{
+    if (!c || subarray < 2 || subarray > c->m || subarray <= c->n) return BAZ_MUSIC_E_INVALID;
+    const int fb = forward_backward ? 1 : 0;
+    std::lock_guard<std::mutex> tl(c->tab_mtx);   // against set_table: c->hRaw is the table in force while it is held
+    DeviceGuard guard(c->device);
+    baz_music_ctx* old = nullptr;
+    if (subarray == c->m && !fb) {                // off: the reference
+        {
+            std::lock_guard<std::mutex> lk(c->mtx);
+            old = c->sm.inner;
+            c->sm.inner = nullptr;
+            c->sm.ms = 0; c->sm.L = 1; c->sm.Kp = 0; c->sm.fb = 0;
+        }
+        baz_music_destroy(old);                   // (drains the stream first: batches in flight may still use it)
+        return BAZ_MUSIC_OK;
+    }
+    bazsmooth::Perm perm = {};
+    if (smoothing_check(c->m, c->res, c->hRaw, subarray, fb, perm.p) != BAZ_MUSIC_OK) return BAZ_MUSIC_E_INVALID;
+    const uint32_t L = c->m - subarray + 1;
+    const uint64_t Kp = (uint64_t)L * c->K * (fb ? 2u : 1u);
+    if (Kp * subarray > (1ull << 31)) return BAZ_MUSIC_E_UNSUPPORTED;   // the re-stacked item's length must fit its 32-bit indexing
+    const std::vector<float> sub = sub_table(c->hRaw, c->m, c->res, subarray);
+    baz_music_ctx* inner = nullptr;
+    int r = baz_music_create(&inner, subarray, c->n, (uint32_t)(Kp * subarray), c->res, sub.data(), c->device);
+    if (r != BAZ_MUSIC_OK) return r;
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);   // a batch sees the old mode or the new one
+        r = baz_music_set_stream(inner, c->stream);
+        if (r == BAZ_MUSIC_OK) r = baz_music_set_peak_mode(inner, c->peak_mode);
+        if (r == BAZ_MUSIC_OK) {
+            old = c->sm.inner;
+            c->sm.inner = inner;
+            c->sm.ms = subarray; c->sm.L = L; c->sm.Kp = (uint32_t)Kp; c->sm.fb = fb;
+            c->sm.perm = perm;
+            inner = nullptr;
+        }
+    }
+    baz_music_destroy(inner);                     // (only after a failure)
+    baz_music_destroy(old);
+    return r;
+}
+
+int baz_music_get_smoothing(const baz_music_ctx* c, uint32_t* subarray, int* forward_backward)
+{
+    if (!c) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(const_cast<baz_music_ctx*>(c)->mtx);
+    if (subarray) *subarray = c->sm.inner ? c->sm.ms : c->m;
+    if (forward_backward) *forward_backward = c->sm.inner ? c->sm.fb : 0;
+    return BAZ_MUSIC_OK;
+}
 
 }  // extern "C"

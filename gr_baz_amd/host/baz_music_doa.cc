@@ -166,6 +166,15 @@ void baz_music_doa::set_peak_mode(bool local_maxima)
     if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: set_peak_mode: ") + baz_music_strerror(rc));
 }
 
+void baz_music_doa::set_smoothing(unsigned int subarray, bool forward_backward)
+{
+    const int rc = baz_music_set_smoothing(d_ctx, subarray, forward_backward ? 1 : 0);
+    if (rc == BAZ_MUSIC_E_INVALID)
+        throw std::invalid_argument("music_doa: set_smoothing: subarray must satisfy n < subarray <= m, and the array response "
+                                    "must be shift invariant (subarray < m) / centro-symmetric (forward_backward)");
+    if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: set_smoothing: ") + baz_music_strerror(rc));
+}
+
 void baz_music_doa::set_array_response(const array_response_t& array_response)
 {
     const std::vector<float> flat = flatten_response(array_response, d_m, d_resolution);

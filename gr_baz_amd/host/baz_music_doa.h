@@ -60,6 +60,10 @@ public:
     /* Extension, off by default (not in the reference): emit the n strongest local maxima of the pseudo-spectrum
      * instead of the n strongest bins (baz_music_set_peak_mode, include/baz_music_hip.h). */
     void set_peak_mode(bool local_maxima);
+    /* Extension, off by default (not in the reference): forward-backward averaging and/or spatial smoothing over subarrays
+     * of `subarray` antennas, for coherent emitters (baz_music_set_smoothing, include/baz_music_hip.h); (m, false) is off.
+     * Throws std::invalid_argument when the arguments or the array response do not allow the mode. */
+    void set_smoothing(unsigned int subarray, bool forward_backward);
 
     /* Page-locking of the scheduler's stream buffers (baz_music_set_host_pinning, include/baz_music_hip.h): work()
      * registers the ranges it is handed the first time it sees them, stop() and the destructor release them.  On by

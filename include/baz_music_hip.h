@@ -224,6 +224,44 @@ BAZ_MUSIC_API const char* baz_music_version(void);
  * descending strength, (0, 0) for missing peaks.  Mode 0 (default) is the reference.  Mode 1 is offered up to
  * BAZ_MUSIC_FAST_M antennas (BAZ_MUSIC_E_UNSUPPORTED beyond). */
 BAZ_MUSIC_API int baz_music_set_peak_mode(baz_music_ctx* ctx, int mode);
+/* OPT-IN extension, NOT reference behaviour: forward-backward averaging (FB) and/or spatial smoothing (SS) of the
+ * covariance, the standard fixes for coherent emitters (multipath, repeaters), whose rank-1 signal covariance leaves a signal
+ * direction in the reference's noise subspace.  subarray = m_s with n < m_s <= m and m_s >= 2, L = m - m_s + 1 subarrays;
+ * (subarray == m, forward_backward == 0) switches the mode off.
+ *   DEFINITION  with X one item (m x K, x(r,c) = in[c*m + r]) and X_l = rows l .. l+m_s-1 of X:
+ *                 R_ss = (1/L) sum_l X_l X_l^H / K;   FB: R = (R_ss + P conj(R_ss) P^T) / 2
+ *               with P the centro-symmetry involution of the m_s subarray elements.  R is exactly the plain covariance of the
+ *               re-stacked item Y = [X_0 .. X_{L-1} (, P conj(X_0) .. P conj(X_{L-1}))], m_s x K', K' = L K (FB ? 2 : 1), so
+ *               the context runs an inner context of shape (m_s, n, m_s K', resolution) on the FIRST m_s COLUMNS of the table
+ *               (gr_baz_amd/csrc/smoothing_kernels.hip.h re-stacks).  Every numeric statement above holds for that inner
+ *               problem; the angle grid and the output ports do not change.
+ *   CHECKS      on the fp32 table, each relation to a relative tolerance of 1e-5 of the bin's max_k |a_k(theta)|^2 (products
+ *               in fp64; steering tables of the helper satisfy them to ~1e-7):
+ *                 SS (m_s < m): shift invariance a_{i+l}(theta) a_0(theta) = a_i(theta) a_l(theta), i < m_s, l < L, every bin;
+ *                 FB: an involution P of the m_s elements and a per-bin scalar c(theta) with conj(a_i) = c a_P(i), every bin.
+ *               P is derived from the table: screened on 32 bins (O(m_s^3)), then verified on every bin (O(m_s res)).
+ *               A ULA passes both, the unit square and an even-m uniform circle FB only, an odd circle or a random table neither.
+ *   ERRORS      BAZ_MUSIC_E_INVALID for a failed check, m_s <= n, m_s > m or m_s < 2; BAZ_MUSIC_E_UNSUPPORTED when m_s K'
+ *               exceeds 2^31; the previous mode stays in force after any error.
+ *   OFF         is the reference bit for bit: a context that never called this, one set to (m, 0) and one switched on and off
+ *               again run the same kernels with the same geometry.
+ *   WHILE ON    mode changes and set_table take effect for items submitted after they return and are serialised against
+ *               process*() (a batch sees the old mode / table or the new one).  set_table must pass the mode's checks, else it
+ *               returns BAZ_MUSIC_E_INVALID and keeps the old table and mode.  process, process_device, process_device_on,
+ *               reserve, sync, set_stream (forwarded), set_peak_mode (forwarded), host_register / set_host_pinning work; every call
+ *               is cut into chunks whose re-stacked items fit BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES (at least one item per chunk), and
+ *               the host path stages its chunks through device buffers: its results equal the device path's bit for bit.
+ *               uses_i8_scan answers for the inner context.  profile, stage_ms, refined_values / refined_items and the debug_
+ *               taps that run stages (cov, evd, q, coarse_margin, coarse_fired, i8_margin, i8_stats) return
+ *               BAZ_MUSIC_E_UNSUPPORTED, stage_name returns "".  table_image, bytes_per_item describe the full m-antenna table.
+ * get_smoothing returns (m, 0) while off.  smoothing_check runs the checks on a table without a device: 0 or BAZ_MUSIC_E_INVALID
+ * (also for m > BAZ_MUSIC_MAX_M, a NULL table, resolution 0); perm_out (m_s bytes, may be NULL) receives P (the identity without
+ * FB).  set_smoothing and set_table use the same code. */
+#define BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES (128u << 20)
+BAZ_MUSIC_API int baz_music_set_smoothing(baz_music_ctx* ctx, uint32_t subarray, int forward_backward);
+BAZ_MUSIC_API int baz_music_get_smoothing(const baz_music_ctx* ctx, uint32_t* subarray, int* forward_backward);
+BAZ_MUSIC_API int baz_music_smoothing_check(uint32_t m, uint32_t resolution, const float* table_ri, uint32_t subarray,
+                                            int forward_backward, uint8_t* perm_out);
 /* Statistic: how many (item, bin) values of the LAST process call were recomputed in the reference's literal form
  * ||G^H a||^2 because the projector form a^H Q a put them at or below ~m 1e-8 max||a||^2 (near-nulls of the noise
  * subspace, SNR >~ 55 dB); blocks until that call is done (a host-fed call cut into chunks reports their sum).
