@@ -136,6 +136,15 @@ def _set_smoothing(h, subarray, forward_backward):
     h.impl.set_smoothing(int(subarray), bool(forward_backward))
 
 
+def _set_order_mode(h, criterion):
+    # EXTENSION, no reference counterpart: per-item emitter count ("mdl" / "aic" / None), see include/baz_music_hip.h.
+    # n becomes the largest count; an output row holds the item's own count of pairs, then (0, 0).
+    modes = {None: 0, "mdl": 1, "aic": 2}
+    if criterion not in modes:
+        raise ValueError("order mode must be 'mdl', 'aic' or None, not %r" % (criterion,))
+    h.impl.set_order_mode(modes[criterion])
+
+
 if _HAVE_GR:
 
     class music_doa_helper(gr.hier_block2):
@@ -165,6 +174,10 @@ if _HAVE_GR:
             set_smoothing(m) switches it off.  Raises ValueError when the array response does not allow it."""
             _set_smoothing(self, subarray, forward_backward)
 
+        def set_order_mode(self, criterion):
+            """Opt-in (not reference behaviour): the number of emitters per item by "mdl" or "aic" (None: the fixed n)."""
+            _set_order_mode(self, criterion)
+
 else:
 
     class music_doa_helper(object):
@@ -187,6 +200,10 @@ else:
             """Opt-in (not reference behaviour): FB averaging and/or smoothing over `subarray`-element subarrays;
             set_smoothing(m) switches it off.  Raises ValueError when the array response does not allow it."""
             _set_smoothing(self, subarray, forward_backward)
+
+        def set_order_mode(self, criterion):
+            """Opt-in (not reference behaviour): the number of emitters per item by "mdl" or "aic" (None: the fixed n)."""
+            _set_order_mode(self, criterion)
 
         def work(self, items):
             """Runs the wrapped block on (k, nsamples) complex64 items: returns (ang, lvl[, spectrum])."""

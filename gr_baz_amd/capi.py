@@ -36,7 +36,10 @@ SYMBOLS = [
     "baz_music_debug_i8_nsplit", "baz_music_debug_sort_state", "baz_music_last_retune_ms", "baz_music_debug_table_image", "baz_music_debug_host_table_image",
     "baz_music_debug_guard_check", "baz_music_debug_guard_active",
     "baz_music_set_smoothing", "baz_music_get_smoothing", "baz_music_smoothing_check",
+    "baz_music_set_order_mode", "baz_music_get_order_mode", "baz_music_last_orders", "baz_music_last_orders_device",
+    "baz_music_order_estimate",
 ]
+ORDER_MODES = {None: 0, "mdl": 1, "aic": 2}   # baz_music_set_order_mode: criterion by name
 SMOOTH_WORKSPACE_BYTES = 128 << 20  # BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES: re-stacked items per chunk while smoothing is on
 
 _vp = ctypes.c_void_p
@@ -169,6 +172,17 @@ def _bind(L):
     L.baz_music_get_smoothing.restype = ctypes.c_int
     L.baz_music_get_smoothing.argtypes = [_vp, ctypes.POINTER(_u32), ctypes.POINTER(ctypes.c_int)]
     L.baz_music_smoothing_check.restype = ctypes.c_int
+    L.baz_music_set_order_mode.restype = ctypes.c_int
+    L.baz_music_set_order_mode.argtypes = [_vp, ctypes.c_int]
+    L.baz_music_get_order_mode.restype = ctypes.c_int
+    L.baz_music_get_order_mode.argtypes = [_vp, ctypes.POINTER(ctypes.c_int)]
+    L.baz_music_last_orders.restype = ctypes.c_int
+    L.baz_music_last_orders.argtypes = [_vp, ctypes.POINTER(ctypes.c_uint8), _u32]
+    L.baz_music_last_orders_device.restype = _vp
+    L.baz_music_last_orders_device.argtypes = [_vp]
+    L.baz_music_order_estimate.restype = ctypes.c_int
+    L.baz_music_order_estimate.argtypes = [_u32, _u32, _u32, ctypes.c_int, ctypes.POINTER(ctypes.c_double), _u32,
+                                           ctypes.POINTER(ctypes.c_uint8)]
     L.baz_music_smoothing_check.argtypes = [_u32, _u32, _f32p, _u32, ctypes.c_int, ctypes.POINTER(ctypes.c_uint8)]
     return L
 
@@ -355,6 +369,31 @@ class Context:
         self._chk(self._L.baz_music_get_smoothing(self._h, ctypes.byref(ms), ctypes.byref(fb)), "baz_music_get_smoothing")
         return int(ms.value), bool(fb.value)
 
+    def set_order_mode(self, criterion):
+        """Opt-in extension (not reference behaviour): per-item emitter count by "mdl" or "aic"; the context's n becomes the
+        largest count and every item reports its own count of pairs, then (0, 0) (include/baz_music_hip.h).  None: off."""
+        if criterion not in ORDER_MODES:
+            raise ValueError("order mode must be 'mdl', 'aic' or None, not %r" % (criterion,))
+        self._chk(self._L.baz_music_set_order_mode(self._h, ORDER_MODES[criterion]), "baz_music_set_order_mode")
+
+    def get_order_mode(self):
+        """"mdl", "aic" or None (off)."""
+        crit = ctypes.c_int(0)
+        self._chk(self._L.baz_music_get_order_mode(self._h, ctypes.byref(crit)), "baz_music_get_order_mode")
+        return {v: k for k, v in ORDER_MODES.items()}[int(crit.value)]
+
+    def last_orders(self, count):
+        """Emitter counts (uint8) of the first `count` items of the last process*() call; n for a call made with the mode off."""
+        out = np.zeros(max(int(count), 1), np.uint8)
+        r = self._L.baz_music_last_orders(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), int(count))
+        if r < 0:
+            self._chk(r, "baz_music_last_orders")
+        return out[:r].copy()
+
+    def last_orders_device(self):
+        """Device address of the same bytes (0 before the first call); valid until the next process*() call."""
+        return int(self._L.baz_music_last_orders_device(self._h) or 0)
+
     def set_stream(self, hip_stream):
         self._chk(self._L.baz_music_set_stream(self._h, _vp(hip_stream) if hip_stream else None),
                   "baz_music_set_stream")
@@ -417,6 +456,20 @@ def smoothing_check(m, resolution, table, subarray, forward_backward=False):
     r = lib().baz_music_smoothing_check(int(m), int(resolution), t.view(np.float32).ctypes.data_as(_f32p), int(subarray),
                                         1 if forward_backward else 0, perm.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
     return perm if r == OK else None
+
+
+def order_estimate(m, nsnap, n_max, criterion, eigvals_ascending):
+    """HOST-ONLY: the emitter counts the kernels' decision routine gives for rows of m ascending eigenvalues (needs no
+    device).  criterion "mdl" / "aic"; returns a uint8 array, one count per row."""
+    ev = np.ascontiguousarray(eigvals_ascending, dtype=np.float64).reshape(-1, int(m))
+    out = np.zeros(max(ev.shape[0], 1), np.uint8)
+    crit = ORDER_MODES.get(criterion, criterion) if not isinstance(criterion, int) else criterion
+    r = lib().baz_music_order_estimate(int(m), int(nsnap), int(n_max), int(crit or 0),
+                                       ev.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ev.shape[0],
+                                       out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+    if r != OK:
+        raise ValueError("baz_music_order_estimate: %s" % lib().baz_music_strerror(r).decode())
+    return out[:ev.shape[0]].copy()
 
 
 TABLE_IMAGES = {0: "FB", 1: "TB", 2: "coarse", 3: "i8", 4: "a2p", 5: "TA", 6: "a2", 7: "params", 8: "i8 packed (m <= 4)"}

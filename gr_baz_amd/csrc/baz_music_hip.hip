@@ -292,6 +292,19 @@ struct baz_music_ctx {
     int peak_mode = 0;      // 0: the reference's n strongest bins; 1 (opt-in extension): n strongest local maxima
     float* dPeakSpec = nullptr;   // internal spectrum when peak mode runs without the spectrum port
     size_t peak_spec_cap = 0;     // floats
+    // Opt-in per-item emitter count (baz_music_set_order_mode; NOT reference behaviour; order_kernels.hip.h).  While
+    // order_mode is 0 none of the mode's kernels is launched and nothing below is allocated on the process path.
+    int order_mode = 0;             // 0: the fixed n of the reference; 1 MDL, 2 AIC: n is the largest count
+    uint32_t order_nsnap = 0;       // snapshots N of the criterion; 0: K (the smoothing mode hands its inner context the outer K)
+    uint8_t* dOrd = nullptr;        // counts of the items of the last process*() call, in call order (all chunks)
+    size_t ord_cap = 0;
+    uint32_t ord_count = 0;         // items of the call in flight / the last call recorded so far (the next chunk's offset)
+    uint32_t ord_items = 0;         // items of the last process*() call
+    bool ord_on = false;            // ... and whether it ran with the mode on (else every count is n)
+    bool ord_driven = false;        // an inner context of the smoothing mode: the outer context opens the call (order_begin)
+    uint8_t* ord_cur = nullptr;     // where the EVD launched next writes its counts (null: a debug tap -> dOrdTap)
+    uint8_t* dOrdTap = nullptr;     // counts of the debug taps' EVD launches (never read back)
+    size_t ord_tap_cap = 0;
     size_t chunk_bytes = 0;   // host-fed path: traffic per pipelined chunk (BAZ_MUSIC_CHUNK_MIB); 0 = by buffer kind
     // host-fed path: page ranges of the caller's buffers this context has page-locked (baz_music_host_register)
     struct HostPin { uintptr_t lo, hi; uint32_t asked; };   // [lo, hi): the caller's exact bytes
@@ -712,6 +725,47 @@ void prof_collect(baz_music_ctx* c)
     }
 }
 
+// ---- emitter-count mode: bookkeeping --------------------------------------------------------------------------------------------
+int grow_bytes(baz_music_ctx* c, uint8_t*& p, size_t& cap, size_t need)
+{
+    if (need <= cap) return BAZ_MUSIC_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));     // a batch in flight may still write the old buffer
+    if (p) (void)dev_free(p);
+    p = nullptr; cap = 0;
+    const size_t bytes = (need + 255) / 256 * 256;
+    HIP_TRY(c, dev_malloc((void**)&p, bytes));
+    cap = bytes;
+    return BAZ_MUSIC_OK;
+}
+
+// Opens a process*() call of `items` items for baz_music_last_orders: the counts of all its chunks land in dOrd in call order.
+// With the mode off this is three stores.
+int order_begin(baz_music_ctx* c, uint32_t items)
+{
+    c->ord_count = 0;
+    c->ord_items = items;
+    c->ord_on = c->order_mode != 0;
+    return c->ord_on ? grow_bytes(c, c->dOrd, c->ord_cap, items) : BAZ_MUSIC_OK;
+}
+
+// the ORDER kernels' extra arguments for an EVD launch over `batch` items
+int order_args(baz_music_ctx* c, uint32_t batch, OrderArgs& oa)
+{
+    oa.ord = c->ord_cur;
+    if (!oa.ord) {
+        const int r = grow_bytes(c, c->dOrdTap, c->ord_tap_cap, batch);
+        if (r) return r;
+        oa.ord = c->dOrdTap;
+    }
+    oa.crit = c->order_mode;
+    oa.nsnap = (double)(c->order_nsnap ? c->order_nsnap : c->K);
+    return BAZ_MUSIC_OK;
+}
+
+// The `n` the scans hand to their literal form (rows = m - n noise eigenvectors per item).  Mode on: the uniform row count the
+// ORDER epilogues pad with zero rows -- m from 5 antennas on, m - 1 below (all literal_tile carries there).
+uint32_t scan_n(const baz_music_ctx* c) { return c->order_mode ? (c->m <= 4 ? 1u : 0u) : c->n; }
+
 // ---- kernel dispatch -------------------------------------------------------------------
 
 template <int M>
@@ -763,6 +817,22 @@ int launch_cov(baz_music_ctx* c, const float* d_in, uint32_t batch, double2* dR)
 template <int M>
 int launch_evd_t(baz_music_ctx* c, const double2* dR, uint32_t batch, double* dQ, uint32_t qstride, double* dG)
 {
+    if (c->order_mode) {      // opt-in emitter count: the ORDER twins; every item takes the Jacobi (evd_sub_kernel has no noise eigenvalues)
+        OrderArgs oa;
+        const int ro = order_args(c, batch, oa);
+        if (ro) return ro;
+        if constexpr (M <= 4) {
+            hipLaunchKernelGGL((evd_proj_order_kernel<M>), dim3((batch + 63) / 64), dim3(64), 0, c->stream, dR, dQ, batch, c->n, qstride, dG, oa);
+        } else {
+            constexpr uint32_t IPW = 64 / M;
+            double* ss = (dQ == c->dQ && batch <= c->cap) ? c->dSs : nullptr;
+            double* const dQw = (ss && short_form_in_use(c)) ? nullptr : dQ;
+            hipLaunchKernelGGL((evd_proj_lds_order_kernel<M>), dim3((batch + IPW - 1) / IPW), dim3(64), 0, c->stream, dR, dQw, batch, c->n,
+                               qstride, dG, ss, oa);
+        }
+        HIP_TRY(c, hipGetLastError());
+        return BAZ_MUSIC_OK;
+    }
     if constexpr (M <= 4) {   // one item per lane, register resident
         const uint32_t blocks = (batch + 63) / 64;
         hipLaunchKernelGGL((evd_proj_kernel<M>), dim3(blocks), dim3(64), 0, c->stream, dR, dQ, batch, c->n, qstride, dG);
@@ -802,6 +872,15 @@ int launch_covevd(baz_music_ctx* c, const float* d_in, uint32_t batch, double* d
     const uint32_t ti = c->covevd_task_items ? (uint32_t)c->covevd_task_items : (batch >= 16384u ? 64u : (batch >= 8192u ? 32u : 16u));
     const uint32_t ntasks = (batch + ti - 1) / ti;
     const uint32_t blocks = std::min<uint32_t>((ntasks + 3) / 4, c->covevd_blocks);
+    if (c->order_mode) {
+        OrderArgs oa;
+        const int ro = order_args(c, batch, oa);
+        if (ro) return ro;
+        hipLaunchKernelGGL(cov4_evd_order_kernel, dim3(blocks), dim3(256), 0, c->stream, d_in, dQ, dG, d_R_dbg, batch, c->K, c->n,
+                           qstride, ti, oa);
+        HIP_TRY(c, hipGetLastError());
+        return BAZ_MUSIC_OK;
+    }
     hipLaunchKernelGGL(cov4_evd_kernel, dim3(blocks), dim3(256), 0, c->stream, d_in, dQ, dG, d_R_dbg, batch, c->K, c->n,
                        qstride, ti);
     HIP_TRY(c, hipGetLastError());
@@ -1014,7 +1093,9 @@ int launch_scan_t(baz_music_ctx* c, const double* dQ, uint32_t qstride, uint32_t
                   float* d_lvl, float* d_spec)
 {
     if constexpr (M <= 8 && NMAX <= 4) {
-        if (!d_spec && coarse_applies(c) && dQ == c->dQ) {
+        // (emitter-count mode: the gate reads n both as list length and as the literal form's row count, and its list-length bound
+        // is what prunes tiles -- such contexts take the full scans below, whose n is the row count alone)
+        if (!d_spec && coarse_applies(c) && dQ == c->dQ && !c->order_mode) {
             const CoarseGeom CG = coarse_geometry(c, batch);
             if ((size_t)batch * CG.nsplit * NMAX > c->cand_cap) return BAZ_MUSIC_E_INVALID;
             ScanRefine rf;
@@ -1138,7 +1219,7 @@ int launch_scan_t(baz_music_ctx* c, const double* dQ, uint32_t qstride, uint32_t
             if ((size_t)batch * G.nsplit * NMAX > c->cand_cap) return BAZ_MUSIC_E_INVALID;
 #define BAZ_I8_LAUNCH(SPEC, VEC4)                                                                                       \
     hipLaunchKernelGGL((scan_i8_kernel<M, NMAX, SPEC, VEC4>), dim3(G.blocks), dim3(256), 0, c->stream, dQ, c->dIB,      \
-                       c->dIB + i8_image_bytes5(c->m, c->fb_steps) / 16, c->dFB + c->fb_step_elems, d_spec, cand, batch, c->res, qstride, G.nsplit, c->keep_mask, c->n, rf, \
+                       c->dIB + i8_image_bytes5(c->m, c->fb_steps) / 16, c->dFB + c->fb_step_elems, d_spec, cand, batch, c->res, qstride, G.nsplit, c->keep_mask, scan_n(c), rf, \
                        c->i8, c->dI8Stat, nullptr)
 #ifdef BAZ_MUSIC_LAB
             if constexpr ((M == 8 || M == 16) && NMAX == 2) {        // lab: ablations of the bulk loop (timing only, wrong results)
@@ -1187,7 +1268,7 @@ int launch_scan_t(baz_music_ctx* c, const double* dQ, uint32_t qstride, uint32_t
             const double2* tb0 = c->dTB + c->tb_step_elems;
 #define BAZ_SIG_LAUNCH(SPEC, VEC4, SIGV)                                                                                    \
     hipLaunchKernelGGL((scan_mfma_kernel<M, NMAX, SPEC, VEC4, 0, (1 | 2 | 16), SIGV>), dim3(G.blocks), dim3(256), 0, c->stream, \
-                       c->dSs, tb0, d_spec, cand, batch, c->res, qstride, G.nsplit, c->nclass, G.rows_per_class, c->keep_mask, c->n, rf, (uint32_t)c->seq_walk)
+                       c->dSs, tb0, d_spec, cand, batch, c->res, qstride, G.nsplit, c->nclass, G.rows_per_class, c->keep_mask, scan_n(c), rf, (uint32_t)c->seq_walk)
             if (c->n == 2) {
                 if constexpr (M >= 9) {
                     if (spec && vec4) BAZ_SIG_LAUNCH(true, true, 2);
@@ -1204,7 +1285,7 @@ int launch_scan_t(baz_music_ctx* c, const double* dQ, uint32_t qstride, uint32_t
             return BAZ_MUSIC_OK;
         }
     }
-#define BAZ_SCAN_ARGS dQ, fb0, d_spec, cand, batch, c->res, qstride, G.nsplit, c->nclass, G.rows_per_class, c->keep_mask, c->n, rf, (uint32_t)c->seq_walk
+#define BAZ_SCAN_ARGS dQ, fb0, d_spec, cand, batch, c->res, qstride, G.nsplit, c->nclass, G.rows_per_class, c->keep_mask, scan_n(c), rf, (uint32_t)c->seq_walk
 #define BAZ_SCAN_LAUNCH(SPEC, VEC4, ABLV, AUXV)                                                                    \
     hipLaunchKernelGGL((scan_mfma_kernel<M, NMAX, SPEC, VEC4, ABLV, AUXV>), dim3(G.blocks), dim3(256), (size_t)c->scan_lds_pad, c->stream, \
                        BAZ_SCAN_ARGS)
@@ -2057,15 +2138,20 @@ int process_device_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, vo
     r = check_launch_pointers(c);
     if (r) return r;
     const uint32_t qstride = baz_music_q_stride(batch);
+    // emitter-count mode: this chunk's counts go behind those of the call's earlier chunks (order_begin sized dOrd for the call)
+    uint8_t* const ord = c->order_mode ? c->dOrd + c->ord_count : nullptr;
+    if (c->order_mode) {
+        if (!c->ord_on || !c->dOrd || (size_t)c->ord_count + batch > c->ord_cap) return refuse_null(c, nullptr, "dOrd (order_begin)");
+        c->ord_cur = ord;
+    }
     if (c->fused_covevd) {
         r = launch_covevd(c, static_cast<const float*>(d_in), batch, c->dQ, qstride, c->dG);
-        if (r) return r;
     } else {
         r = launch_cov(c, static_cast<const float*>(d_in), batch, c->dR);
-        if (r) return r;
-        r = launch_evd(c, c->dR, batch, c->dQ, qstride, c->dG);
-        if (r) return r;
+        if (r == BAZ_MUSIC_OK) r = launch_evd(c, c->dR, batch, c->dQ, qstride, c->dG);
     }
+    c->ord_cur = nullptr;
+    if (r) return r;
     float* spec = static_cast<float*>(d_spec);
     if (c->peak_mode && !spec) {   // the peak picker reads the spectrum: keep a private one when port 2 is not wired
         const size_t need = (size_t)batch * c->res;
@@ -2083,7 +2169,18 @@ int process_device_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, vo
     r = launch_merge(c, batch, static_cast<float*>(d_ang), static_cast<float*>(d_lvl), spec);
     if (r) return r;
     c->stat_next_clean = true;     // the merge cleared the next call's statistic counter
-    if (c->peak_mode) return launch_peaks(c, batch, static_cast<float*>(d_ang), static_cast<float*>(d_lvl), spec);
+    if (c->peak_mode) {
+        r = launch_peaks(c, batch, static_cast<float*>(d_ang), static_cast<float*>(d_lvl), spec);
+        if (r) return r;
+    }
+    if (ord) {                     // (0, 0) at and beyond every item's own count: the n - k weakest entries of either picker
+        ProfScope ps(c, BAZ_MUSIC_STAGE_MERGE);
+        const uint64_t entries = (uint64_t)batch * c->n;
+        hipLaunchKernelGGL(bazorder::order_truncate_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, c->stream,
+                           static_cast<float*>(d_ang), static_cast<float*>(d_lvl), ord, batch, c->n);
+        HIP_TRY(c, hipGetLastError());
+        c->ord_count += batch;
+    }
     return BAZ_MUSIC_OK;
 }
 
@@ -2557,6 +2654,8 @@ void baz_music_destroy(baz_music_ctx* c)
         if (c->dFire) (void)dev_free(c->dFire);
         if (c->hFire) (void)hipHostFree(c->hFire);
 #endif
+        if (c->dOrd) (void)dev_free(c->dOrd);
+        if (c->dOrdTap) (void)dev_free(c->dOrdTap);
         if (c->dCand) (void)dev_free(c->dCand);
         if (c->dR) (void)dev_free(c->dR);
         if (c->dQ) (void)dev_free(c->dQ);
@@ -2632,6 +2731,11 @@ int baz_music_reserve(baz_music_ctx* c, uint32_t max_batch)
     std::lock_guard<std::mutex> lk(c->mtx);
     DeviceGuard guard(c->device);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->order_mode && !c->ord_driven) {   // emitter-count mode: one byte per item of a whole call (kept by the context that runs the kernels)
+        baz_music_ctx* const oc = c->sm.inner ? c->sm.inner : c;
+        const int ro = grow_bytes(oc, oc->dOrd, oc->ord_cap, max_batch);
+        if (ro) return ro;
+    }
     if (c->sm.inner) {   // smoothing on: the inner context's workspace for one chunk, and the re-stacked chunk
         const uint32_t chunk = smooth_chunk(c, max_batch);
         const int rs = grow(c, c->sm.dY, c->sm.y_cap, (size_t)chunk * c->sm.Kp * c->sm.ms);
@@ -2660,6 +2764,10 @@ int baz_music_process_device(baz_music_ctx* c, const void* d_in, uint32_t batch,
     std::lock_guard<std::mutex> lk(c->mtx);   // .cc:101
     DeviceGuard guard(c->device);
     (void)hipGetLastError();                  // launches below are checked with hipGetLastError(): start from a clean slate
+    if (!c->ord_driven) {                     // (an inner context of the smoothing mode: its outer context has opened the call)
+        const int ro = order_begin(c->sm.inner ? c->sm.inner : c, batch);
+        if (ro) return ro;
+    }
     if (c->sm.inner) return smooth_device_locked(c, d_in, batch, d_ang, d_lvl, d_spec);
     int r = begin_statistic(c);
     return r ? r : process_device_locked(c, d_in, batch, d_ang, d_lvl, d_spec);
@@ -2681,8 +2789,9 @@ int baz_music_process_device_on(baz_music_ctx* c, void* caller_stream, const voi
         HIP_TRY(c, hipEventRecord(c->ev_in, cs));
         HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_in, 0));
     }
-    int r = BAZ_MUSIC_OK;
-    if (c->sm.inner) {
+    int r = order_begin(c->sm.inner ? c->sm.inner : c, batch);
+    if (r != BAZ_MUSIC_OK) {
+    } else if (c->sm.inner) {
         r = smooth_device_locked(c, d_in, batch, d_ang, d_lvl, d_spec);
     } else {
         r = begin_statistic(c);
@@ -2710,6 +2819,7 @@ int baz_music_process(baz_music_ctx* c, const float* in_ri, uint32_t batch, floa
         (void)host_register_locked(c, in_ri, (size_t)batch * c->nsamples * 8);
         if (spectrum) (void)host_register_locked(c, spectrum, (size_t)batch * c->res * 4);
     }
+    if (const int ro = order_begin(c->sm.inner ? c->sm.inner : c, batch)) return ro;   // (all chunks of this call: baz_music_last_orders)
     if (c->sm.inner) return smooth_host_locked(c, in_ri, batch, ang, lvl, spectrum);
     // Cutting a call into chunks (H2D of chunk i+1, the kernels of chunk i and D2H of chunk i-1 overlap on three
     // streams) only pays when a chunk carries enough bytes to hide what the extra copies, events and stream hops cost.
@@ -3555,7 +3665,10 @@ int baz_music_set_smoothing(baz_music_ctx* c, uint32_t subarray, int forward_bac
         std::lock_guard<std::mutex> lk(c->mtx);   // a batch sees the old mode or the new one
         r = baz_music_set_stream(inner, c->stream);
         if (r == BAZ_MUSIC_OK) r = baz_music_set_peak_mode(inner, c->peak_mode);
+        if (r == BAZ_MUSIC_OK) r = baz_music_set_order_mode(inner, c->order_mode);
         if (r == BAZ_MUSIC_OK) {
+            inner->order_nsnap = c->K;            // N of the criterion: this context's snapshots, not the K' re-stacked columns
+            inner->ord_driven = true;
             old = c->sm.inner;
             c->sm.inner = inner;
             c->sm.ms = subarray; c->sm.L = L; c->sm.Kp = (uint32_t)Kp; c->sm.fb = fb;
@@ -3566,6 +3679,70 @@ int baz_music_set_smoothing(baz_music_ctx* c, uint32_t subarray, int forward_bac
     baz_music_destroy(inner);                     // (only after a failure)
     baz_music_destroy(old);
     return r;
+}
+
+int baz_music_set_order_mode(baz_music_ctx* c, int criterion)
+{
+    if (!c || criterion < 0 || criterion > 2) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    if (criterion && c->wide) return BAZ_MUSIC_E_UNSUPPORTED;   // the ORDER epilogues exist for the specialised kernels only
+    if (c->sm.inner) {   // (the inner context is never wider than this one)
+        const int r = baz_music_set_order_mode(c->sm.inner, criterion);
+        if (r != BAZ_MUSIC_OK) return r;
+    }
+    c->order_mode = criterion;
+    return BAZ_MUSIC_OK;
+}
+
+int baz_music_get_order_mode(const baz_music_ctx* c, int* criterion)
+{
+    if (!c || !criterion) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(const_cast<baz_music_ctx*>(c)->mtx);
+    *criterion = c->order_mode;
+    return BAZ_MUSIC_OK;
+}
+
+int baz_music_last_orders(baz_music_ctx* c, uint8_t* out, uint32_t count)
+{
+    if (!c || (!out && count)) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    if (c->sm.inner) return baz_music_last_orders(c->sm.inner, out, count);
+    DeviceGuard guard(c->device);
+    const uint32_t have = std::min(count, c->ord_on ? c->ord_count : c->ord_items);
+    if (!c->ord_on) {                              // the call ran with the mode off: every item used the context's n
+        if (have) memset(out, (int)c->n, have);
+        return (int)have;
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (have) HIP_TRY(c, hipMemcpy(out, c->dOrd, have, hipMemcpyDeviceToHost));
+    return (int)have;
+}
+
+const void* baz_music_last_orders_device(baz_music_ctx* c)
+{
+    if (!c) return nullptr;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    if (c->sm.inner) return baz_music_last_orders_device(c->sm.inner);
+    DeviceGuard guard(c->device);
+    if (c->ord_on) return c->ord_count ? c->dOrd : nullptr;
+    if (!c->ord_items) return nullptr;
+    // the call ran with the mode off: the same bytes as baz_music_last_orders, filled here (nothing on the process path)
+    if (grow_bytes(c, c->dOrd, c->ord_cap, c->ord_items) != BAZ_MUSIC_OK) return nullptr;
+    if (hipMemsetAsync(c->dOrd, (int)c->n, c->ord_items, c->stream) != hipSuccess) return nullptr;
+    return c->dOrd;
+}
+
+int baz_music_order_estimate(uint32_t m, uint32_t nsnap, uint32_t n_max, int criterion, const double* eigvals_ascending,
+                             uint32_t count, uint8_t* out)
+{
+    if (m == 0 || m > BAZ_MUSIC_MAX_M || n_max >= m || nsnap == 0 || (criterion != 1 && criterion != 2) ||
+        (count && (!eigvals_ascending || !out)))
+        return BAZ_MUSIC_E_INVALID;
+    for (uint32_t it = 0; it < count; ++it) {
+        const double* l = eigvals_ascending + (size_t)it * m;
+        out[it] = (uint8_t)bazorder::order_decide<0>((int)m, (int)n_max, (double)nsnap, criterion, [&](int i) { return l[i]; });
+    }
+    return BAZ_MUSIC_OK;
 }
 
 int baz_music_get_smoothing(const baz_music_ctx* c, uint32_t* subarray, int* forward_backward)

@@ -18,6 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "order_kernels.hip.h"
+
 namespace bazmusic {
 
 typedef double v4f64 __attribute__((ext_vector_type(4)));
@@ -489,9 +491,20 @@ __device__ __forceinline__ bool evd_check(EvdState<M>& st)
     return __all(st.done);
 }
 
-template <int M>
+// Opt-in emitter-count estimate (order_kernels.hip.h; baz_music_set_order_mode): what the ORDER forms of the Jacobi epilogues
+// take on top of their arguments.  ord[item] receives the item's count k, and the noise set becomes the m - k smallest
+// eigenvalues instead of the uniform m - n (n is then the LARGEST count an item may get).
+struct OrderArgs {
+    uint8_t* ord;      // [batch] counts
+    int crit;          // bazorder::CRIT_MDL / CRIT_AIC
+    double nsnap;      // snapshots N of the criterion
+};
+
+// ORDER = false is the reference (the only form a context launches unless the mode is on): `oa` is not read.
+template <int M, bool ORDER = false>
 __device__ __forceinline__ void evd_finish(const EvdState<M>& st, const bool valid, const uint32_t item, const uint32_t n,
-                                           const uint32_t qstride, double* __restrict__ Qs, double* __restrict__ Gs)
+                                           const uint32_t qstride, double* __restrict__ Qs, double* __restrict__ Gs,
+                                           const OrderArgs oa = OrderArgs{nullptr, 0, 0.0})
 {
     const Herm<M>& h = st.h;
     const double poison = st.poison;
@@ -500,7 +513,26 @@ __device__ __forceinline__ void evd_finish(const EvdState<M>& st, const bool val
 #pragma unroll
     for (int k = 0; k < M; ++k) wk[k] = h.D[k];
     double msk[M];
-    const int nnoise = (int)M - (int)n;
+    int nnoise = (int)M - (int)n;
+    if constexpr (ORDER) {
+        // the eigenvalues in ascending order (selects on the ranks: statically indexed), then this lane's own count; a
+        // non-finite covariance counts no emitter (its projector is poisoned below as ever)
+        double ls[M];
+#pragma unroll
+        for (int r = 0; r < M; ++r) ls[r] = 0.0;
+#pragma unroll
+        for (int k = 0; k < M; ++k) {
+            int rank = 0;
+#pragma unroll
+            for (int j = 0; j < M; ++j) rank += (wk[j] < wk[k] || (wk[j] == wk[k] && j < k)) ? 1 : 0;
+#pragma unroll
+            for (int r = 0; r < M; ++r) ls[r] = (rank == r) ? wk[k] : ls[r];
+        }
+        int khat = bazorder::order_decide<M>(M, (int)n, oa.nsnap, oa.crit, [&](int i) { return ls[i]; });
+        khat = (poison == poison) ? khat : 0;
+        nnoise = (int)M - khat;
+        if (valid) oa.ord[item] = (uint8_t)khat;
+    }
 #pragma unroll
     for (int k = 0; k < M; ++k) {
         int rank = 0;
@@ -509,11 +541,14 @@ __device__ __forceinline__ void evd_finish(const EvdState<M>& st, const bool val
         msk[k] = (rank < nnoise) ? 1.0 : 0.0;
         // the noise eigenvectors themselves, for the literal-form refinement of near-null tiles (literal_tile() in the scan):
         // Gs[((rank*M + i)*2 + {re,im}) * qstride + item] = V[i][k]
-        if (valid && Gs && rank < nnoise) {
+        // (ORDER: the scan's literal form runs over the uniform m - 1 rows -- all that literal_tile carries up to 4 antennas --
+        // and the rows at or beyond this item's m - k are zeros: they add exact zeros to ||G^H a||^2)
+        if (valid && Gs && (ORDER ? rank < (int)M - 1 : rank < nnoise)) {
+            const bool live = rank < nnoise;
 #pragma unroll
             for (int i = 0; i < M; ++i) {
-                Gs[(size_t)((rank * M + i) * 2) * qstride + item] = h.Vr[i][k];
-                Gs[(size_t)((rank * M + i) * 2 + 1) * qstride + item] = h.Vi[i][k];
+                Gs[(size_t)((rank * M + i) * 2) * qstride + item] = live ? h.Vr[i][k] : 0.0;
+                Gs[(size_t)((rank * M + i) * 2 + 1) * qstride + item] = live ? h.Vi[i][k] : 0.0;
             }
         }
     }
@@ -543,9 +578,10 @@ __device__ __forceinline__ void evd_finish(const EvdState<M>& st, const bool val
 // was built and measured: 7 steps of ~380 instructions instead of ~4,900 at cfg2 / 20 dB, yet only 1.127 -> 1.120 ms per
 // step, because its inner products are dependent fp64 chains where the rotations have 4-way ILP, and 1.3 % slower at
 // 0 dB where the iteration is abandoned after 3 steps.  Not shipped; profiles/r02_subspace_iteration.txt.)
-template <int M, class GetR>
+template <int M, class GetR, bool ORDER = false>
 __device__ __forceinline__ void evd_project_lane(GetR getR, const bool valid, const uint32_t item, const uint32_t n,
-                                                 const uint32_t qstride, double* __restrict__ Qs, double* __restrict__ Gs)
+                                                 const uint32_t qstride, double* __restrict__ Qs, double* __restrict__ Gs,
+                                                 const OrderArgs oa = OrderArgs{nullptr, 0, 0.0})
 {
     EvdState<M> st;
     evd_begin<M>(getR, st);
@@ -553,7 +589,7 @@ __device__ __forceinline__ void evd_project_lane(GetR getR, const bool valid, co
         if (evd_check<M>(st)) break;
         jacobi_sweep<M>(st.h, !st.done);
     }
-    evd_finish<M>(st, valid, item, n, qstride, Qs, Gs);
+    evd_finish<M, ORDER>(st, valid, item, n, qstride, Qs, Gs, oa);
 }
 
 template <int M>
@@ -570,6 +606,22 @@ __global__ __launch_bounds__(64) void evd_proj_kernel(const double2* __restrict_
     evd_project_lane<M>([&](int i, int j) { return Rp[i * M + j]; }, valid, item, n, qstride, Qs, Gs);
 }
 
+// ... with the per-item emitter count (OrderArgs above); n = the largest count
+template <int M>
+__global__ __launch_bounds__(64) void evd_proj_order_kernel(const double2* __restrict__ R,
+                                                             double* __restrict__ Qs,
+                                                             uint32_t batch, uint32_t n, uint32_t qstride,
+                                                             double* __restrict__ Gs, OrderArgs oa)
+{
+    constexpr int MM = M * M;
+    const uint32_t item = blockIdx.x * 64 + threadIdx.x;
+    const bool valid = item < batch;
+    const uint32_t itc = valid ? item : (batch - 1);
+    const double2* Rp = R + (size_t)itc * MM;
+    auto getR = [&](int i, int j) { return Rp[i * M + j]; };
+    evd_project_lane<M, decltype(getR), true>(getR, valid, item, n, qstride, Qs, Gs, oa);
+}
+
 // -------------------------------------------------------------------------------------
 // 2a. Covariance AND EVD in one kernel for m = 4, K % 256 == 0: a wave streams 64 consecutive items through the
 //     covariance of cov4_x4_kernel (1c), parks each R (upper triangle, 16 doubles) in LDS, then runs the lane-per-item
@@ -582,114 +634,12 @@ __global__ __launch_bounds__(64) void evd_proj_kernel(const double2* __restrict_
 //     A streaming wave runs at s_setprio 3, an EVD phase at 0 (worth 0.04 ms against equal priorities once the waves
 //     drift apart).
 // -------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void cov4_evd_kernel(const float* __restrict__ in, double* __restrict__ Qs,
-                                                       double* __restrict__ Gs, double2* __restrict__ Rdbg,
-                                                       uint32_t batch, uint32_t K, uint32_t n, uint32_t qstride,
-                                                       uint32_t task_items = 64)
-{
-    // task_items (64, 32 or 16; round 5): items per wave task.  64 fills the lane-per-item EVD; a SMALL batch -- a host-fed work() call of
-    // 1,024 items is 16 tasks of 64 = 16 waves with 8 KiB in flight each, too little to keep a PCIe link (or HBM) busy -- is cut into more,
-    // shorter tasks (the EVD then runs on fewer lanes: its latency is what it was).  Items are independent: no result depends on it.
-    constexpr int RSD = 34;                       // see cov4_x4_kernel
-    constexpr int RING = 8;                       // chunk loads in flight per wave (8 KiB)
-    __shared__ double stage[4][2][8 * RSD];       // per wave, double-buffered
-    __shared__ double gram[4][2][64];             // per wave: D1, D2
-    __shared__ double rtab[4][16][64];            // per wave: R of 64 items, [slot][item]: 4 diagonals, 6 x (re, im)
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t chunks = K >> 5;               // 1-KiB chunks per item (multiple of 8)
-    const int wcol = lane >> 1, wrow = 4 * (lane & 1);
-    const int ri = lane & 3, rh = (lane >> 2) & 1, rw = (lane >> 3) & 1, rk = lane >> 4;
-    const int p_off = (4 * rh + ri) * RSD + 8 * rk + 4 * rw;
-    const int q_off = (4 * (1 - rh) + ri) * RSD + 8 * rk + 4 * rw;
-    double* const g1 = gram[wave][0];
-    double* const g2 = gram[wave][1];
-    double(*const rt)[64] = rtab[wave];
-    const double dK = (double)K;
-    const uint32_t ntasks = (batch + task_items - 1) / task_items;
-    const uint32_t tstride = gridDim.x * 4;
-    // slot of the upper-triangle entry this lane (< 16: a = lane>>2, b = lane&3) produces: diagonal a -> a;
-    // pair (a < b) -> 4 + 2p (re), 5 + 2p (im), p = index of (a, b) in (0,1)(0,2)(0,3)(1,2)(1,3)(2,3)
-    const int ea = (lane >> 2) & 3, eb = lane & 3;
-    const int pidx = (ea == 0) ? eb - 1 : (ea == 1 ? eb + 1 : 5);
-
-    for (uint32_t task = blockIdx.x * 4 + wave; task < ntasks; task += tstride) {
-        __builtin_amdgcn_s_setprio(3);
-        const uint32_t item0 = task * task_items;
-        const uint32_t nit = (batch - item0 < task_items) ? batch - item0 : task_items;
-        // the stream of this task: nit items x chunks, contiguous in HBM; ring slot u holds the chunks q = u (mod 8)
-        const v4f32* __restrict__ src = reinterpret_cast<const v4f32*>(in + (size_t)item0 * K * 8) + lane;
-        const uint32_t total = nit * chunks;                 // multiple of 8
-        v4f32 pf[RING];
-#pragma unroll
-        for (int u = 0; u < RING; ++u) pf[u] = __builtin_nontemporal_load(src + (size_t)u * 64);
-        uint32_t q = 0;                                      // chunk index inside the task
-        for (uint32_t it = 0; it < nit; ++it) {
-            double a1 = 0.0, b1 = 0.0, a2 = 0.0, b2 = 0.0;
-            for (uint32_t cg = 0; cg < chunks; cg += 8) {
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    double* __restrict__ T = stage[wave][u & 1];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) T[(wrow + j) * RSD + wcol] = (double)pf[u][j];   // exact widening (.cc:77)
-                    // re-arm the slot only after its values are consumed (see cov4_x4_kernel); past the end of the
-                    // task the loads repeat its last chunk, so that they stay unconditional
-                    asm volatile("" ::: "memory");
-                    const uint32_t qn = q + u + RING;
-                    pf[u] = __builtin_nontemporal_load(src + (size_t)(qn < total ? qn : total - 1) * 64);
-                    wave_lds_fence();
-                    const v4f64 P = *reinterpret_cast<const v4f64*>(T + p_off);
-                    const v4f64 Q = *reinterpret_cast<const v4f64*>(T + q_off);
-                    a1 = __builtin_amdgcn_mfma_f64_4x4x4f64(P[0], P[0], a1, 0, 0, 0);
-                    a2 = __builtin_amdgcn_mfma_f64_4x4x4f64(P[0], Q[0], a2, 0, 0, 0);
-                    b1 = __builtin_amdgcn_mfma_f64_4x4x4f64(P[1], P[1], b1, 0, 0, 0);
-                    b2 = __builtin_amdgcn_mfma_f64_4x4x4f64(P[1], Q[1], b2, 0, 0, 0);
-                    a1 = __builtin_amdgcn_mfma_f64_4x4x4f64(P[2], P[2], a1, 0, 0, 0);
-                    a2 = __builtin_amdgcn_mfma_f64_4x4x4f64(P[2], Q[2], a2, 0, 0, 0);
-                    b1 = __builtin_amdgcn_mfma_f64_4x4x4f64(P[3], P[3], b1, 0, 0, 0);
-                    b2 = __builtin_amdgcn_mfma_f64_4x4x4f64(P[3], Q[3], b2, 0, 0, 0);
-                    wave_lds_fence();
-                }
-                q += 8;
-            }
-            // Gram blocks -> R (see cov4_x4_kernel), upper triangle into the wave's table
-            g1[lane] = a1 + b1;
-            g2[lane] = a2 + b2;
-            wave_lds_fence();
-            if (lane < 16) {
-                auto G = [&](int x, int y) -> double {
-                    if ((x >> 2) == (y >> 2)) {
-                        const int hh = x >> 2, o = (y & 3) + 4 * hh + 16 * (x & 3);
-                        return g1[o] + g1[o + 8];
-                    }
-                    if (x > y) { const int t = x; x = y; y = t; }
-                    const int o = (y - 4) + 16 * x;
-                    return g2[o] + g2[o + 8];
-                };
-                const double re = (G(2 * ea, 2 * eb) + G(2 * ea + 1, 2 * eb + 1)) / dK;     // .cc:85
-                const double im = (G(2 * ea + 1, 2 * eb) - G(2 * ea, 2 * eb + 1)) / dK;
-                if (ea == eb) rt[ea][it] = re;
-                else if (ea < eb) { rt[4 + 2 * pidx][it] = re; rt[5 + 2 * pidx][it] = im; }
-                if (Rdbg) Rdbg[(size_t)(item0 + it) * 16 + lane] = make_double2(re, im);
-            }
-            wave_lds_fence();
-        }
-        // EVD of the task's items, one per lane (lanes beyond nit redo the last item and write nothing), at low priority
-        __builtin_amdgcn_s_setprio(0);
-        {
-            const int li = ((uint32_t)lane < nit) ? lane : (int)nit - 1;
-            auto getR = [&](int i, int j) -> double2 {
-                if (i == j) return make_double2(rt[i][li], 0.0);
-                const int lo = i < j ? i : j, hi2 = i < j ? j : i;
-                const int p = (lo == 0) ? hi2 - 1 : (lo == 1 ? hi2 + 1 : 5);
-                const double re = rt[4 + 2 * p][li], im = rt[5 + 2 * p][li];
-                return make_double2(re, i < j ? im : -im);
-            };
-            evd_project_lane<4>(getR, (uint32_t)lane < nit, item0 + lane, n, qstride, Qs, Gs);
-        }
-        wave_lds_fence();
-    }
-}
+#define BAZ_EVD_ORDER 0
+#include "cov4_evd_kernel.inc.h"     // cov4_evd_kernel
+#undef BAZ_EVD_ORDER
+#define BAZ_EVD_ORDER 1
+#include "cov4_evd_kernel.inc.h"     // cov4_evd_order_kernel: the same text with the per-item emitter count (OrderArgs, section 2)
+#undef BAZ_EVD_ORDER
 
 // -------------------------------------------------------------------------------------
 // 2b. The same EVD for m >= 5: M lanes per item, A lives in LDS (complex128), V in registers (one row per lane).
@@ -725,265 +675,12 @@ __device__ __forceinline__ int tour_idx(int r, int pos)
     return t == 0 ? 1 : (t <= ME / 2 - 1 ? 2 * t : 2 * (P - t) + 1);
 }
 
-template <int M>
-__global__ __launch_bounds__(64) void evd_proj_lds_kernel(const double2* __restrict__ R,
-                                                           double* __restrict__ Qs,
-                                                           uint32_t batch, uint32_t n, uint32_t qstride,
-                                                           double* __restrict__ Gs,
-                                                           const uint8_t* __restrict__ only = nullptr,
-                                                           double* __restrict__ Ss = nullptr)
-{
-    constexpr int MM = M * M;
-    constexpr int IPW = 64 / M;           // items per wave
-    constexpr int MAX_SWEEPS = 24;
-    constexpr int ME = M + (M & 1);       // even size of the round-robin schedule (odd M: one phantom index)
-    // A lives in LDS (index space, dynamically addressed); V stays in REGISTERS: lane j holds row j of V with its
-    // columns kept in tournament-position order, so the column pair of round-pair k is always registers 2k, 2k+1
-    // (static), and is re-ordered between rounds by register moves.  V enters LDS only for the final projector
-    // (it reuses A's storage).  Halving the LDS footprint doubles the resident waves at m >= 9.
-    __shared__ double2 sA[IPW][M][M + 1]; // +1: rows of different lanes start on different banks
-    __shared__ double sPart[IPW][M];
-    __shared__ double sPar[IPW][ME / 2][6];
-    __shared__ int sSel[IPW][M];          // eigenvalue index by ascending rank
-
-    const int lane = threadIdx.x;
-    const int slot = lane / M;            // item within the wave
-    const int j = lane - slot * M;        // this lane's row (phase 1) / column (phase 2)
-    const bool lane_used = slot < IPW;
-    const int sl = lane_used ? slot : 0;
-    const uint32_t item = blockIdx.x * IPW + sl;
-    const uint32_t itc = (item < batch) ? item : (batch - 1);
-    // `only` (the pass behind evd_sub_kernel): just the items that kernel handed back; a wave with none of them leaves
-    const bool wanted = !only || only[itc] != 0;
-    if (only && !__any(wanted && lane_used && item < batch)) return;
-    const bool valid = lane_used && item < batch && wanted;
-    double2(*A)[M + 1] = sA[sl];
-
-    double2 Vrow[ME];
-#pragma unroll
-    for (int k = 0; k < ME; ++k) Vrow[k] = make_double2(k == j ? 1.0 : 0.0, 0.0);
-    if (lane_used) {
-        const double2* Rp = R + (size_t)itc * MM + j * M;
-        double rsum = 0.0;
-#pragma unroll
-        for (int k = 0; k < M; ++k) {
-            double2 v = Rp[k];
-            rsum += v.x + v.y;
-            if (k == j) v.y = 0.0;
-            A[j][k] = v;
-        }
-        sPart[sl][j] = rsum * 0.0;      // NaN iff this row holds a NaN / Inf
-    }
-    wave_lds_fence();
-    // non-finite covariance -> poisoned projector (see evd_proj_kernel)
-    double poison = 0.0;
-#pragma unroll
-    for (int k = 0; k < M; ++k) poison += sPart[sl][k];
-    // exact power-of-two normalisation (see evd_proj_kernel)
-    double dmax = 0.0;
-#pragma unroll
-    for (int k = 0; k < M; ++k) dmax = fmax(dmax, fabs(A[k][k].x));
-    int ex = 0;
-    (void)frexp(dmax, &ex);
-    const double scl = (dmax > 0.0 && dmax < __builtin_huge_val()) ? ldexp(1.0, -ex) : 1.0;
-    wave_lds_fence();
-    if (lane_used) {
-#pragma unroll
-        for (int k = 0; k < M; ++k) {
-            double2 v = A[j][k];
-            v.x *= scl; v.y *= scl;
-            A[j][k] = v;
-        }
-    }
-    wave_lds_fence();
-
-    for (int sweep = 0; sweep < MAX_SWEEPS; ++sweep) {
-        double off = 0.0;
-        if (lane_used) {
-#pragma unroll
-            for (int k = 0; k < M; ++k) {
-                const double2 v = A[j][k];
-                if (k != j) off += v.x * v.x + v.y * v.y;
-            }
-            sPart[sl][j] = off;
-        }
-        wave_lds_fence();
-        double offsum = 0.0, dia = 0.0;
-#pragma unroll
-        for (int k = 0; k < M; ++k) { offsum += sPart[sl][k]; const double a = A[k][k].x; dia += a * a; }
-        const bool done = !(offsum > 2e-33 * dia);   // offsum counts every off-diagonal twice
-        wave_lds_fence();
-        if (__all(done || !lane_used)) break;
-
-        // One sweep = ME-1 rounds of the round-robin (tournament) ordering; the <= ME/2 pairs of a round are disjoint,
-        // so their rotations commute and read only their own 2x2 block: parameters of all pairs are computed at once
-        // (lane k of the item takes pair k), then every lane applies ALL column operations of the round to its row
-        // of A (LDS) and V (registers), then ALL row operations to its column of A.  3 LDS hand-overs per round
-        // instead of 2 per rotation, one parameter evaluation per lane per round instead of one per lane per
-        // rotation.  (Row-cyclic form: 2.05 ms per 16,384 16x16 items, 57 % of the config-5 step.)
-        for (int r = 0; r < ME - 1; ++r) {
-            if (lane_used && j < ME / 2) {
-                const int k = j;
-                const int pp = tour_idx<ME>(r, 2 * k), qq = tour_idx<ME>(r, 2 * k + 1);
-                double c = 1.0, sn = 0.0, ur = 1.0, ui = 0.0;
-                if (pp < M && qq < M) {                  // (a pair with the phantom index of an odd M idles)
-                    const double2 apq = A[pp][qq];
-                    const double app = A[pp][pp].x, aqq = A[qq][qq].x;
-                    const double g2 = apq.x * apq.x + apq.y * apq.y;
-                    const bool rot = !done && g2 > 1e-40;   // a converged item freezes (exact identity) while wave-mates sweep
-                    const double gg = sqrt(g2);
-                    const double ig = rot ? 1.0 / gg : 0.0;
-                    ur = rot ? apq.x * ig : 1.0;
-                    ui = rot ? apq.y * ig : 0.0;
-                    const double tau = (aqq - app) * 0.5 * ig;
-                    double t = copysign(1.0, tau) / (fabs(tau) + sqrt(1.0 + tau * tau));
-                    t = rot ? t : 0.0;
-                    c = 1.0 / sqrt(1.0 + t * t);
-                    sn = t * c;
-                }
-                double* par = sPar[sl][k];
-                par[0] = c; par[1] = sn; par[2] = sn * ur; par[3] = sn * ui; par[4] = c * ur; par[5] = c * ui;
-            }
-            wave_lds_fence();
-            // phase 1: this lane's row j of A and V, columns p_k and q_k of every pair  (A J, V J).  All operands of
-            // the round are fetched before the first result is stored (the pairs touch disjoint columns, which the
-            // compiler cannot know): one LDS round trip per phase instead of one per pair.
-            if (lane_used) {
-                constexpr int HB = (ME / 2 + 1) / 2;          // two operand batches: bounds the live registers
-#pragma unroll
-                for (int h = 0; h < ME / 2; h += HB) {
-                    double2 ax[HB], ay[HB];
-#pragma unroll
-                    for (int kk = 0; kk < HB; ++kk) {
-                        const int k = h + kk;
-                        if (k < ME / 2) {
-                            const int pp = tour_idx<ME>(r, 2 * k), qq = tour_idx<ME>(r, 2 * k + 1);
-                            if (pp < M && qq < M) { ax[kk] = A[j][pp]; ay[kk] = A[j][qq]; }
-                        }
-                    }
-#pragma unroll
-                    for (int kk = 0; kk < HB; ++kk) {
-                        const int k = h + kk;
-                        if (k >= ME / 2) continue;
-                        const int pp = tour_idx<ME>(r, 2 * k), qq = tour_idx<ME>(r, 2 * k + 1);
-                        if (pp >= M || qq >= M) continue;
-                        const double* par = sPar[sl][k];
-                        const double c = par[0], s = par[1], sur = par[2], sui = par[3], cur = par[4], cui = par[5];
-                        const double2 x = ax[kk], y = ay[kk], vx = Vrow[2 * k], vy = Vrow[2 * k + 1];
-                        A[j][pp] = make_double2(c * x.x - (sur * y.x + sui * y.y), c * x.y - (sur * y.y - sui * y.x));
-                        A[j][qq] = make_double2(s * x.x + (cur * y.x + cui * y.y), s * x.y + (cur * y.y - cui * y.x));
-                        Vrow[2 * k] = make_double2(c * vx.x - (sur * vy.x + sui * vy.y), c * vx.y - (sur * vy.y - sui * vy.x));
-                        Vrow[2 * k + 1] = make_double2(s * vx.x + (cur * vy.x + cui * vy.y), s * vx.y + (cur * vy.y - cui * vy.x));
-                    }
-                }
-            }
-            wave_lds_fence();
-            // phase 2: this lane's column j of A, rows p_k and q_k of every pair  (J^H (A J))
-            if (lane_used) {
-                double2 ax[ME / 2], ay[ME / 2];
-#pragma unroll
-                for (int k = 0; k < ME / 2; ++k) {
-                    const int pp = tour_idx<ME>(r, 2 * k), qq = tour_idx<ME>(r, 2 * k + 1);
-                    if (pp < M && qq < M) { ax[k] = A[pp][j]; ay[k] = A[qq][j]; }
-                }
-#pragma unroll
-                for (int k = 0; k < ME / 2; ++k) {
-                    const int pp = tour_idx<ME>(r, 2 * k), qq = tour_idx<ME>(r, 2 * k + 1);
-                    if (pp >= M || qq >= M) continue;
-                    const double* par = sPar[sl][k];
-                    const double c = par[0], s = par[1], sur = par[2], sui = par[3], cur = par[4], cui = par[5];
-                    const double2 x = ax[k], y = ay[k];
-                    double2 np = make_double2(c * x.x - (sur * y.x - sui * y.y), c * x.y - (sur * y.y + sui * y.x));
-                    double2 nq = make_double2(s * x.x + (cur * y.x - cui * y.y), s * x.y + (cur * y.y + cui * y.x));
-                    if (j == qq) np = make_double2(0.0, 0.0);                    // a_pq := 0
-                    if (j == pp) { nq = make_double2(0.0, 0.0); np.y = 0.0; }    // a_qp := 0, real diagonal
-                    if (j == qq) nq.y = 0.0;
-                    A[pp][j] = np;
-                    A[qq][j] = nq;
-                }
-            }
-            wave_lds_fence();
-            // tournament movement of V's columns (registers): position pos now holds what tour_src(pos) held
-            {
-                double2 t[ME];
-#pragma unroll
-                for (int k = 0; k < ME; ++k) t[k] = Vrow[tour_src<ME>(k)];
-#pragma unroll
-                for (int k = 0; k < ME; ++k) Vrow[k] = t[k];
-            }
-        }
-    }
-    // (sweeps are whole periods of the tournament: position == original index again)
-
-    // Ascending rank of the eigenvalues (ties -> lower column first; the noise space is rank < m-n, .cc:93): lane j
-    // ranks eigenvalue j and publishes sSel[rank] = j.  The projector is then summed over the SMALLER of the two sets:
-    // Q = sum_noise v v^H  or  Q = I - sum_signal v v^H  (V is unitary) -- n = 2 of 16 columns at config 5, which
-    // takes the epilogue from ~m^3/2 to ~m^2 n complex MACs per item.
-    if (lane_used) sSel[sl][j] = j;
-    wave_lds_fence();
-    if (lane_used) {
-        const double wj = A[j][j].x;
-        int rank = 0;
-#pragma unroll
-        for (int l = 0; l < M; ++l) {
-            const double wl = A[l][l].x;
-            rank += (wl < wj || (wl == wj && l < j)) ? 1 : 0;
-        }
-        sSel[sl][rank] = j;                    // (NaN eigenvalues: every rank is 0; the projector is poisoned anyway)
-    }
-    const int nnoise = (int)M - (int)n;
-    const bool use_noise = nnoise <= (int)n;
-    const int cnt = use_noise ? nnoise : (int)n;
-    const int base = use_noise ? 0 : nnoise;
-    // V rows go to LDS (A's storage) for the cross-lane projector
-    wave_lds_fence();
-    double2(*V)[M + 1] = sA[sl];
-    if (lane_used) {
-#pragma unroll
-        for (int k = 0; k < M; ++k) V[j][k] = Vrow[k];
-    }
-    wave_lds_fence();
-    // the noise eigenvectors themselves (see evd_proj_kernel): lane j writes component j of every noise vector
-    if (valid && Gs) {
-        for (int r = 0; r < nnoise; ++r) {
-            const double2 v = V[j][sSel[sl][r] & 15];
-            Gs[(size_t)((r * M + j) * 2) * qstride + item] = v.x;
-            Gs[(size_t)((r * M + j) * 2 + 1) * qstride + item] = v.y;
-        }
-    }
-    // the two signal eigenvectors as the coefficient vectors of the scan's short form (scan_mfma_kernel, SIG): output
-    // 2c = Re s_c^H a, 2c+1 = Im s_c^H a over the real coordinates (re a_0, im a_0, re a_1, ...)
-    if (valid && Ss && n <= 2) {
-        for (int cI = 0; cI < (int)n; ++cI) {
-            const double2 v = V[j][sSel[sl][nnoise + cI] & 15];
-            const double vr = v.x + poison, vi = v.y + poison;
-            Ss[(size_t)((2 * cI) * 2 * M + 2 * j) * qstride + item] = vr;
-            Ss[(size_t)((2 * cI) * 2 * M + 2 * j + 1) * qstride + item] = vi;
-            Ss[(size_t)((2 * cI + 1) * 2 * M + 2 * j) * qstride + item] = -vi;
-            Ss[(size_t)((2 * cI + 1) * 2 * M + 2 * j + 1) * qstride + item] = vr;
-        }
-    }
-    // lane j emits row j of Q (upper part): Q_jl = sum_{k in set} V[j][k] conj(V[l][k])
-    // (Qs == nullptr: the scan runs the short form from Ss and never reads the projector)
-    if (valid && Qs) {
-        for (int l = j; l < M; ++l) {
-            double re = 0.0, im = 0.0;
-            for (int i = 0; i < cnt; ++i) {
-                const int k = sSel[sl][base + i] & 15;
-                const double2 vj = V[j][k], vl = V[l][k];
-                re += vj.x * vl.x + vj.y * vl.y;
-                im += vj.y * vl.x - vj.x * vl.y;
-            }
-            if (!use_noise) { re = ((l == j) ? 1.0 : 0.0) - re; im = -im; }
-            if (l == j) {
-                Qs[(size_t)(j * M + j) * qstride + item] = re + poison;
-            } else {
-                Qs[(size_t)(j * M + l) * qstride + item] = 2.0 * re + poison;
-                Qs[(size_t)(l * M + j) * qstride + item] = -2.0 * im + poison;
-            }
-        }
-    }
-}
+#define BAZ_EVD_ORDER 0
+#include "evd_lds_kernel.inc.h"      // evd_proj_lds_kernel
+#undef BAZ_EVD_ORDER
+#define BAZ_EVD_ORDER 1
+#include "evd_lds_kernel.inc.h"      // evd_proj_lds_order_kernel: the same text with the per-item emitter count (OrderArgs, section 2)
+#undef BAZ_EVD_ORDER
 
 // -------------------------------------------------------------------------------------
 // 2c. The projector WITHOUT the full eigen-decomposition, for m >= 5 and few emitters (n = P <= 4, 2P <= m).

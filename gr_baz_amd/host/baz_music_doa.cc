@@ -175,6 +175,22 @@ void baz_music_doa::set_smoothing(unsigned int subarray, bool forward_backward)
     if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: set_smoothing: ") + baz_music_strerror(rc));
 }
 
+void baz_music_doa::set_order_mode(int criterion)
+{
+    const int rc = baz_music_set_order_mode(d_ctx, criterion);
+    if (rc == BAZ_MUSIC_E_INVALID) throw std::invalid_argument("music_doa: set_order_mode: criterion must be 0 (fixed n), 1 (MDL) or 2 (AIC)");
+    if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: set_order_mode: ") + baz_music_strerror(rc));
+}
+
+std::vector<unsigned char> baz_music_doa::last_orders(unsigned int count)
+{
+    std::vector<unsigned char> out(count);
+    const int rc = baz_music_last_orders(d_ctx, out.data(), count);
+    if (rc < 0) throw std::runtime_error(std::string("music_doa: last_orders: ") + baz_music_strerror(rc));
+    out.resize((size_t)rc);
+    return out;
+}
+
 void baz_music_doa::set_array_response(const array_response_t& array_response)
 {
     const std::vector<float> flat = flatten_response(array_response, d_m, d_resolution);

@@ -64,6 +64,11 @@ public:
      * of `subarray` antennas, for coherent emitters (baz_music_set_smoothing, include/baz_music_hip.h); (m, false) is off.
      * Throws std::invalid_argument when the arguments or the array response do not allow the mode. */
     void set_smoothing(unsigned int subarray, bool forward_backward);
+    /* Extension, off by default (not in the reference): per-item emitter count, 1 = MDL, 2 = AIC, 0 = the fixed n
+     * (baz_music_set_order_mode, include/baz_music_hip.h): n becomes the largest count, an item with count k emits k pairs and
+     * then (0, 0).  last_orders: the counts of the first `count` items of the last work() call. */
+    void set_order_mode(int criterion);
+    std::vector<unsigned char> last_orders(unsigned int count);
 
     /* Page-locking of the scheduler's stream buffers (baz_music_set_host_pinning, include/baz_music_hip.h): work()
      * registers the ranges it is handed the first time it sees them, stop() and the destructor release them.  On by

@@ -241,6 +241,13 @@ PYBIND11_MODULE(_baz_music, mod)
         .def("set_peak_mode", [](music_doa_handle& h, bool on) { h.blk->set_peak_mode(on); }, py::arg("local_maxima"))
         .def("set_smoothing", [](music_doa_handle& h, unsigned int subarray, bool fb) { h.blk->set_smoothing(subarray, fb); },
              py::arg("subarray"), py::arg("forward_backward") = false)
+        .def("set_order_mode", [](music_doa_handle& h, int criterion) { h.blk->set_order_mode(criterion); }, py::arg("criterion"))
+        .def("last_orders",
+             [](music_doa_handle& h, unsigned int count) {
+                 const std::vector<unsigned char> v = h.blk->last_orders(count);
+                 return std::vector<int>(v.begin(), v.end());
+             },
+             py::arg("count"))
         .def("array_response", [](music_doa_handle& h) { return h.blk->array_response(); })
         .def("name", [](music_doa_handle& h) { return h.blk->name(); })
         .def("unique_id", [](music_doa_handle& h) { return h.blk->unique_id(); })

@@ -248,7 +248,7 @@ BAZ_MUSIC_API int baz_music_set_peak_mode(baz_music_ctx* ctx, int mode);
  *   WHILE ON    mode changes and set_table take effect for items submitted after they return and are serialised against
  *               process*() (a batch sees the old mode / table or the new one).  set_table must pass the mode's checks, else it
  *               returns BAZ_MUSIC_E_INVALID and keeps the old table and mode.  process, process_device, process_device_on,
- *               reserve, sync, set_stream (forwarded), set_peak_mode (forwarded), host_register / set_host_pinning work; every call
+ *               reserve, sync, set_stream (forwarded), set_peak_mode, set_order_mode (forwarded), host_register / set_host_pinning work; every call
  *               is cut into chunks whose re-stacked items fit BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES (at least one item per chunk), and
  *               the host path stages its chunks through device buffers: its results equal the device path's bit for bit.
  *               uses_i8_scan answers for the inner context.  profile, stage_ms, refined_values / refined_items and the debug_
@@ -262,6 +262,48 @@ BAZ_MUSIC_API int baz_music_set_smoothing(baz_music_ctx* ctx, uint32_t subarray,
 BAZ_MUSIC_API int baz_music_get_smoothing(const baz_music_ctx* ctx, uint32_t* subarray, int* forward_backward);
 BAZ_MUSIC_API int baz_music_smoothing_check(uint32_t m, uint32_t resolution, const float* table_ri, uint32_t subarray,
                                             int forward_backward, uint8_t* perm_out);
+/* OPT-IN extension, NOT reference behaviour: a per-item estimate of the NUMBER of emitters.  The reference fixes n at
+ * construction (lib/baz_music_doa.cc:35-53, .cc:93); with the mode on the context's n becomes the LARGEST count n_max, each item
+ * estimates its own count k in [0, n] from the eigenvalues of its covariance, uses a noise subspace of m - k eigenvectors and reports
+ * k (ang, lvl) pairs followed by n - k pairs of (0, 0).  Ports and output format do not change; lvl is 1/d > 0 for every real entry,
+ * so lvl == 0 marks a missing one (as in peak mode 1).  criterion: 0 = fixed n (the reference, the default), 1 = MDL, 2 = AIC
+ * (Wax & Kailath 1985); anything else BAZ_MUSIC_E_INVALID.
+ *   DEFINITION  N = nsamples / m snapshots; l_1 <= ... <= l_m the eigenvalues of the item's R (ties in the order of the Jacobi's
+ *               ranking: lower column first), clamped l_i <- max(l_i, 2^-40 l_m).  For k = 0 .. n over the m - k smallest:
+ *                 L(k) = -N (m - k) (mean(ln l) - ln(mean l)),  MDL(k) = L(k) + 1/2 k (2m - k) ln N,  AIC(k) = 2 L(k) + 2 k (2m - k);
+ *               the count is the SMALLEST k that minimises the criterion.  Everything in fp64; the criterion does not change
+ *               under R -> s R.  An item whose R is all zero or holds a NaN / Inf counts 0 and is otherwise treated as ever (a
+ *               non-finite R: NaN spectrum).  Count 0: the projector is I, the spectrum 1 / ||a||^2, no pair is reported.
+ *               tests/order_ref.py restates this in numpy.
+ *   WHAT RUNS   the Jacobi epilogues decide (gr_baz_amd/csrc/order_kernels.hip.h holds the routine, music_kernels.hip.h the ORDER
+ *               twins of evd_proj_kernel, cov4_evd_kernel and evd_proj_lds_kernel).  Orthogonal iteration yields no noise
+ *               eigenvalues: from 5 antennas on EVERY item takes the Jacobi while the mode is on.  The scans run unchanged on
+ *               projectors / signal vectors / noise vectors padded with zeros to a uniform shape; without the spectrum port, up to
+ *               8 antennas run the full fp64 / int8 scan instead of the coarse-gated one (its gate reads n as a list length).  The
+ *               int8 scan's bounds (|q_e| <= 1 + 2^-10, E4, E5) hold for a projector of any rank.  A small kernel then clears the
+ *               entries at or beyond each item's count.  Mode 0 launches exactly the kernels it launched before the mode existed
+ *               and is the reference bit for bit: a context never set, one set to 0, one switched on and off again.
+ *   SCOPE       up to BAZ_MUSIC_FAST_M antennas (BAZ_MUSIC_E_UNSUPPORTED beyond), like peak mode.  Composes with peak mode (the k
+ *               strongest local maxima) and with smoothing: the mode is forwarded to the inner context with N = this context's
+ *               snapshot count K -- the K' re-stacked columns are not independent snapshots; the forward-backward-corrected
+ *               penalty of the literature (Xu et al. 1994) is NOT applied.  profile, stage_ms and the debug_ taps keep working
+ *               (debug_evd / debug_q return the variable-rank projector).  Up to 4 antennas the literal form near nulls carries
+ *               m - 1 noise vectors: a count-0 item at a bin with ||a||^2 <= ~m 1e-8 max ||a||^2 (a table row that all but
+ *               vanishes) gets the sum over the m - 1 smallest eigen-directions there.
+ *   WHEN        set_order_mode takes effect for items submitted after it returns and is serialised against process*() like
+ *               set_peak_mode: a batch sees the old mode or the new one.  The previous mode stays in force after any error.
+ * last_orders: the counts of the items of the LAST process*() call in call order, at most `count` of them (a host-fed call cut into
+ * chunks, or a smoothing call, reports all its items); blocks until that call is done; returns how many were written, or < 0.  A
+ * call that ran with the mode off reports n for every item.  last_orders_device: the same bytes in HBM (one per item), valid until
+ * the next process*() call, ordered on the context's stream; NULL before the first call.  order_estimate needs no device: the same
+ * decision routine the kernels call, on `count` rows of m ascending eigenvalues with N = nsnap; BAZ_MUSIC_E_INVALID for m == 0,
+ * m > BAZ_MUSIC_MAX_M, n_max >= m, nsnap == 0, a criterion other than 1 / 2 or a NULL array. */
+BAZ_MUSIC_API int baz_music_set_order_mode(baz_music_ctx* ctx, int criterion);
+BAZ_MUSIC_API int baz_music_get_order_mode(const baz_music_ctx* ctx, int* criterion);
+BAZ_MUSIC_API int baz_music_last_orders(baz_music_ctx* ctx, uint8_t* out, uint32_t count);
+BAZ_MUSIC_API const void* baz_music_last_orders_device(baz_music_ctx* ctx);
+BAZ_MUSIC_API int baz_music_order_estimate(uint32_t m, uint32_t nsnap, uint32_t n_max, int criterion,
+                                           const double* eigvals_ascending, uint32_t count, uint8_t* out);
 /* Statistic: how many (item, bin) values of the LAST process call were recomputed in the reference's literal form
  * ||G^H a||^2 because the projector form a^H Q a put them at or below ~m 1e-8 max||a||^2 (near-nulls of the noise
  * subspace, SNR >~ 55 dB); blocks until that call is done (a host-fed call cut into chunks reports their sum).
