@@ -146,10 +146,6 @@ struct baz_music_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;      // the stream process_device() launches on (own or caller's)
-    // steering table as the real bilinear-form table F[bin][m*m] (fp64) in MFMA B-operand order:
-    // FB[step][chunk][lane] (double2), see build_FB; one padded step in front of step 0 and one behind the last
-    // (the scan's row classes read shifted windows), dFB points at the allocation, step 0 is dFB + fb_step_elems
-    double2* dFB = nullptr;
     uint32_t fb_steps = 0;   // 64-bin steps
     size_t fb_step_elems = 0;   // double2 elements per step of FB (2 * KS * 64)
     uint32_t nclass = 1;     // row classes of the spectrum port: 64 / gcd(res, 64) when res % 4 == 0, else 1
@@ -177,20 +173,31 @@ struct baz_music_ctx {
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;
     hipEvent_t ev_in = nullptr, ev_out = nullptr;   // baz_music_process_device_on: ordering against the caller's stream
     std::mutex mtx;   // serialises process* against the table SWAP of set_table, like d_mutex (.cc:67,101)
-    // Retune without stalling the stream (round 5): baz_music_set_table builds every image of the new table with the kernels
-    // of table_kernels.hip.h on `s_tab` into the SHADOW set and takes `mtx` only to exchange the two sets (TableSet below)
+    // Every device image of one steering table and the parameters derived from it.  The context holds two: `tab`, the set in force,
+    // which every launch site reads, and `shadow`.  Retune without stalling the stream (round 5): baz_music_set_table builds every
+    // image of the new table with the kernels of table_kernels.hip.h on `s_tab` into the SHADOW set and takes `mtx` only to exchange
+    // the two sets (retune())
     struct TableSet {
-        double2* dFB = nullptr; double2* dTB = nullptr; uint4* dCS = nullptr; uint4* dIB = nullptr; double* dA2p = nullptr;
-        float2* dTA = nullptr; double* dA2 = nullptr;
+        // steering table as the real bilinear-form table F[bin][m*m] (fp64) in MFMA B-operand order:
+        // FB[step][chunk][lane] (double2), see build_FB; one padded step in front of step 0 and one behind the last
+        // (the scan's row classes read shifted windows), dFB points at the allocation, step 0 is dFB + fb_step_elems
+        double2* dFB = nullptr;
+        double2* dTB = nullptr;          // raw steering table as fp64 MFMA B-operand image (build_TB), padded like dFB
+        uint4* dCS = nullptr;            // coarse-gated scan, per 16-bin tile: f16 hi/lo pieces of the scaled table (B32, B16) + the fp64 B operand (X)
+        uint4* dIB = nullptr;            // int8-matrix-core scan: digit image of the table (build_i8_image)
+        double* dA2p = nullptr;          // short_form_applies(): ||a||^2 per bin, padded like dFB (fb_steps + 2 steps of 64)
+        float2* dTA = nullptr;           // wide arrays: steering table transposed, [m][res] complex64
+        double* dA2 = nullptr;           // wide arrays: ||a||^2 per bin
 #ifdef BAZ_MUSIC_LAB
         uint4* dIP = nullptr;            // level-packed int8 operands (m <= 4; shares i8 / i8_ok with dIB: a configuration has one of the two)
         float* dKT = nullptr;            // float32 table at the sort key's sample bins (sort_kernels.hip.h; m <= 8)
 #endif
         CoarseParams cs = {0.0f, 0.0f, 0.0, 0.0, 1};
         I8Params i8 = {};
-        bool cs_ok = false, i8_ok = false;
-        double refine_below = 0.0;
-    } shadow;
+        bool cs_ok = false;              // coarse image built and its scales representable
+        bool i8_ok = false;              // digit image built (finite table, scale representable, size within I8_IMAGE_LIMIT)
+        double refine_below = 0.0;       // literal-form refinement: threshold on d = a^H Q a
+    } tab, shadow;
     std::mutex tab_mtx;              // retunes among themselves (held for a whole baz_music_set_table; never while `mtx` is wanted by work())
     hipStream_t s_tab = nullptr;     // side stream of the table builders (highest priority: they are tiny)
     hipEvent_t ev_swap = nullptr;    // recorded on the launch stream at every swap: batches that still read the retired set
@@ -207,29 +214,24 @@ struct baz_music_ctx {
     int lab_variant = 0;
     // literal-form refinement of near-null tiles (literal_tile() inside the scan)
     double* dG = nullptr;          // noise eigenvectors, item-minor like dQ (cap * m*m * 2 doubles)
-    double2* dTB = nullptr;        // raw steering table as fp64 MFMA B-operand image (build_TB), padded like dFB
     size_t tb_step_elems = 0;      // double2 elements per step of TB (2 * ceil(2m/4) * 64)
     unsigned long long* dRefined = nullptr;   // statistic: (item, bin) values recomputed, [2]: double-buffered by API call
     int stat_parity = 0;                      // the scan adds to dRefined[stat_parity]; the merge clears the other one
     bool stat_next_clean = true;              // false after a call that failed before its merge ran
-    double refine_below = 0.0;     // threshold on d = a^H Q a
     int refine_off = 0;            // lab (BAZ_MUSIC_NO_REFINE=1): projector form everywhere
     int lab_cov_old = 0;           // lab (BAZ_MUSIC_COV_OLD=1): the round-1 covariance kernel at m = 4
     int force_nsplit = 0;          // tests / lab (BAZ_MUSIC_NSPLIT=k): bin ranges per row in the scan, 0 = by batch size
     // wide arrays (17 <= m <= BAZ_MUSIC_MAX_M): the run-time-m kernels of music_wide_kernels.hip.h
     bool wide = false;
-    float2* dTA = nullptr;         // steering table transposed, [m][res] complex64
     double2* dGw = nullptr;        // noise eigenvectors, [items][m - n][m]
     double* dWS = nullptr;         // fp64 strengths, [items][res] (the top-n's input)
     double2* dSw = nullptr;        // signal eigenvectors, [items][n][m] (the scan's short form where 2n <= m)
-    double* dA2 = nullptr;         // ||a||^2 per bin
     int wide_literal_only = 0;     // lab (BAZ_MUSIC_WIDE_LITERAL=1): no short form in scan_wide_kernel
     uint32_t wide_cov_blocks = 512;
     int wide_cov_mfma = 0;         // 17 <= m <= 32: cov_wide_mfma_kernel, 33 <= m <= 64: cov_wide_pairs_kernel (BAZ_MUSIC_WIDE_COV_MFMA=0: lab)
     int wide_mfma = 0;             // 17 <= m <= 64, n <= 8: the scan on the fp64 matrix core (scan_wide_mfma_kernel; BAZ_MUSIC_WIDE_MFMA=0: lab)
     uint32_t wide_cap = 0;         // items the three buffers above (and dR) hold
     double* dSs = nullptr;         // short_form_applies(): coefficient vectors of the scan's short form, [2n * 2m][q_stride]
-    double* dA2p = nullptr;        // ... and ||a||^2 per bin, padded like dFB (fb_steps + 2 steps of 64)
     int sig_scan = 1;              // lab / tests: BAZ_MUSIC_SIG_SCAN=0 keeps the projector GEMM
     uint8_t* dRedo = nullptr;      // [cap] items evd_sub_kernel hands back to the Jacobi
     int sub_evd = 1;               // signal subspace by orthogonal iteration where n <= 4 (run-time-m kernels: n <= 8) (lab: BAZ_MUSIC_SUB_EVD=0)
@@ -238,21 +240,14 @@ struct baz_music_ctx {
     int covevd_task_items = 0;     // lab (BAZ_MUSIC_COVEVD_TASK_ITEMS = 64 / 32 / 16): items per wave task of cov4_evd_kernel, 0 = by batch size
     uint32_t cov4_resident_blocks = 256u;        // grid of cov4_x4_kernel (persistent waves): one workgroup per CU
     // coarse-gated scan (scan_coarse_kernels.hip.h): m <= 8, spectrum port not wired
-    uint4* dCS = nullptr;          // per 16-bin tile: f16 hi/lo pieces of the scaled table (B32, B16) + the fp64 B operand (X)
     uint32_t cs_tiles = 0;         // tiles in the image (a multiple of 8)
-    CoarseParams cs = {0.0f, 0.0f, 0.0, 0.0, 1};
-    bool cs_ok = false;            // image built and its scales representable
     uint32_t last_nsplit = 1;      // bin ranges per item the last scan launch produced candidates for (the merge folds them)
     int coarse = 1;                // BAZ_MUSIC_COARSE=0: the full fp64 scan also without the spectrum port (A/B, tests)
     int coarse_rg = 4;             // BAZ_MUSIC_COARSE_RG: row groups (x 16 items) per wave, 2 or 4 (lab)
     int coarse_lab = 0;            // BAZ_MUSIC_COARSE_LAB=1: never run an exact tile (cost of the coarse passes alone; wrong results)
     int coarse_stats = 0;          // BAZ_MUSIC_COARSE_STATS=1: count exact tile evaluations (baz_music_debug_coarse_fired)
     unsigned long long* dMargin = nullptr;   // baz_music_debug_coarse_margin: worst error / allowance (float bits << 32 | where)
-    // int8-matrix-core scan (scan_i8_kernels.hip.h): 6 <= m <= 16, n <= 4
-    uint4* dIB = nullptr;          // digit image of the table (build_i8_image)
 #ifdef BAZ_MUSIC_LAB
-    uint4* dIP = nullptr;          // level-packed digit operands, 2 .. 4 antennas (build_i8p_kernel); parameters in `i8` as well
-    float* dKT = nullptr;          // sort-key table (sort_kernels.hip.h)
     // Sorting the items of a batch by their nulls in front of the gated scan (sort_kernels.hip.h), while that scan reports many fired tiles
     uint16_t* dKeys = nullptr;
     uint32_t* dHist = nullptr;     // items per key (KEY_BUCKETS)
@@ -281,8 +276,7 @@ struct baz_music_ctx {
                                    // (profiles/r05_i8p_negative.txt): its arithmetic is 0.31 ms against the fp64 scan's 0.56, but the spectrum
                                    // stores alone take what the fp64 scan takes (0.59 - 0.73 ms by box), and incoherent batches run 2.4 x slower
 #endif
-    I8Params i8 = {};
-    bool i8_ok = false;            // image built (finite table, scale representable, size within I8_IMAGE_LIMIT)
+    // int8-matrix-core scan (scan_i8_kernels.hip.h): 6 <= m <= 16, n <= 4
     int i8_on = 1;                 // BAZ_MUSIC_EXACT=1: every value on the fp64 matrix core (A/B; the round-3 scan)
     int i8_abl = 0;                // lab (BAZ_MUSIC_I8_ABL): ablation mask of scan_i8_kernel (timing only)
     int refine_nocount = 0;        // lab (BAZ_MUSIC_NO_REFINE_COUNT): the scans do not count the values they recompute
@@ -643,13 +637,13 @@ bool short_form_applies(uint32_t m, uint32_t n) { return (n == 2 && m >= 9 && m 
 // The int8-matrix-core scan applies: 6 .. 16 antennas (row classes below, run-time-m kernels above), lists of <= 4 keys.
 bool i8_active(const baz_music_ctx* c)
 {
-    return c->i8_on && c->i8_ok && c->dIB && c->m >= 6 && c->m <= 16 && c->n <= 4 && !c->lab_variant;
+    return c->i8_on && c->tab.i8_ok && c->tab.dIB && c->m >= 6 && c->m <= 16 && c->n <= 4 && !c->lab_variant;
 }
 // ... and its level-packed form for 2 .. 4 antennas (scan_i8p_kernels.hip.h), with the spectrum port: lab builds only
 #ifdef BAZ_MUSIC_LAB
 bool i8p_active(const baz_music_ctx* c)
 {
-    return c->i8_on && c->i8p_on && c->i8_ok && c->dIP && c->m <= 4 && c->n <= 4 && !c->lab_variant;
+    return c->i8_on && c->i8p_on && c->tab.i8_ok && c->tab.dIP && c->m <= 4 && c->n <= 4 && !c->lab_variant;
 }
 #else
 constexpr bool i8p_active(const baz_music_ctx*) { return false; }
@@ -657,7 +651,7 @@ constexpr bool i8p_active(const baz_music_ctx*) { return false; }
 bool short_form_in_use(const baz_music_ctx* c)
 {
     // (the integer form evaluates the projector form: the EVD must write its coefficients)
-    return short_form_applies(c->m, c->n) && c->sig_scan && c->dSs && c->dA2p && !c->lab_variant && !i8_active(c);
+    return short_form_applies(c->m, c->n) && c->sig_scan && c->dSs && c->tab.dA2p && !c->lab_variant && !i8_active(c);
 }
 
 int ensure_workspace(baz_music_ctx* c, uint32_t batch)
@@ -677,9 +671,7 @@ int ensure_workspace(baz_music_ctx* c, uint32_t batch)
     HIP_TRY(c, dev_malloc((void**)&c->dR, (size_t)cap * mm * sizeof(double2)));
     HIP_TRY(c, dev_malloc((void**)&c->dQ, (size_t)cap * mm * sizeof(double)));
     HIP_TRY(c, dev_malloc((void**)&c->dG, (size_t)cap * mm * 2 * sizeof(double)));
-    if (c->dRedo) { (void)dev_free(c->dRedo); c->dRedo = nullptr; }
     HIP_TRY(c, dev_malloc((void**)&c->dRedo, (size_t)cap));
-    if (c->dSs) { (void)dev_free(c->dSs); c->dSs = nullptr; }
     if (short_form_applies(c->m, c->n)) HIP_TRY(c, dev_malloc((void**)&c->dSs, (size_t)cap * 4 * c->n * c->m * sizeof(double)));
     c->cap = cap;
     return BAZ_MUSIC_OK;
@@ -725,18 +717,26 @@ void prof_collect(baz_music_ctx* c)
     }
 }
 
-// ---- emitter-count mode: bookkeeping --------------------------------------------------------------------------------------------
-int grow_bytes(baz_music_ctx* c, uint8_t*& p, size_t& cap, size_t need)
+// Grows one device buffer to `need` elements (contents are not kept).  A buffer that exists is freed behind a drain of the stream:
+// a batch in flight may still read or write it (hipFree happens to synchronise the device today; nothing here relies on it).
+// Nothing in flight can reference a buffer that does not exist yet: the first allocation does not wait.
+template <typename T>
+int grow(baz_music_ctx* c, T*& p, size_t& cap, size_t need)
 {
     if (need <= cap) return BAZ_MUSIC_OK;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));     // a batch in flight may still write the old buffer
-    if (p) (void)dev_free(p);
-    p = nullptr; cap = 0;
-    const size_t bytes = (need + 255) / 256 * 256;
-    HIP_TRY(c, dev_malloc((void**)&p, bytes));
-    cap = bytes;
+    if (p) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        (void)dev_free(p);
+        p = nullptr;
+    }
+    cap = 0;
+    HIP_TRY(c, dev_malloc((void**)&p, need * sizeof(T)));
+    cap = need;
     return BAZ_MUSIC_OK;
 }
+
+// ---- emitter-count mode: bookkeeping --------------------------------------------------------------------------------------------
+int grow_bytes(baz_music_ctx* c, uint8_t*& p, size_t& cap, size_t need) { return grow(c, p, cap, (need + 255) / 256 * 256); }
 
 // Opens a process*() call of `items` items for baz_music_last_orders: the counts of all its chunks land in dOrd in call order.
 // With the mode off this is three stores.
@@ -898,6 +898,16 @@ int launch_evd(baz_music_ctx* c, const double2* dR, uint32_t batch, double* dQ, 
 #undef BAZ_CALL
 }
 
+// Covariance + EVD of `batch` items: the projector coefficients into `dQ` (the workspace's c->dQ, or a debug tap's own buffer), the
+// noise eigenvectors into c->dG.  The fused kernel where it applies, else two kernels through c->dR.  ensure_workspace() came first.
+int launch_frontend(baz_music_ctx* c, const void* d_in, uint32_t batch, double* dQ, uint32_t qstride)
+{
+    const float* in = static_cast<const float*>(d_in);
+    if (c->fused_covevd) return launch_covevd(c, in, batch, dQ, qstride, c->dG);
+    const int r = launch_cov(c, in, batch, c->dR);
+    return r ? r : launch_evd(c, c->dR, batch, dQ, qstride, c->dG);
+}
+
 // Launch geometry of the scan: rows are taken class by class (class k = items nclass*j + k, see the kernel's ROW
 // CLASSES note), every class padded to a multiple of 64 rows (one block = 4 waves x 16 rows of ONE class), times
 // `nsplit` ranges of 64-bin steps, chosen so that a launch has >= ~8 waves/SIMD worth of wave tasks even for small
@@ -953,26 +963,14 @@ uint32_t i8_nsplit(uint32_t batch, uint32_t nsteps, uint32_t slots, int force_ns
     return best;
 }
 
-int ensure_candidates(baz_music_ctx* c, size_t entries)
-{
-    if (entries <= c->cand_cap) return BAZ_MUSIC_OK;
-    if (c->dCand) {                                        // (see ensure_workspace: drain what may still write the old lists)
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        (void)dev_free(c->dCand);
-        c->dCand = nullptr;
-    }
-    c->cand_cap = 0;
-    HIP_TRY(c, dev_malloc((void**)&c->dCand, entries * sizeof(double)));
-    c->cand_cap = entries;
-    return BAZ_MUSIC_OK;
-}
+int ensure_candidates(baz_music_ctx* c, size_t entries) { return grow(c, c->dCand, c->cand_cap, entries); }
 
 // The coarse-gated scan applies: spectrum port not wired, m <= 8, n <= 4, the table's scale representable.
 bool coarse_applies(const baz_music_ctx* c)
 {
     // (one emitter from 6 antennas on: the full scan is the SHORT form, a quarter of the projector GEMM's work, and the
     // gated scan's exact tiles are the projector form -- not the same bits; that case keeps the full scan)
-    return c->coarse && c->cs_ok && c->dCS && c->m <= 8 && c->n <= 4 && !c->lab_variant && !short_form_applies(c->m, c->n);
+    return c->coarse && c->tab.cs_ok && c->tab.dCS && c->m <= 8 && c->n <= 4 && !c->lab_variant && !short_form_applies(c->m, c->n);
 }
 
 constexpr int coarse_rg_wide(int m, int nmax) { return (cs_groups(m) == 4 && nmax > 2) ? 1 : 2; }   // (what the register file holds without spilling)
@@ -1014,7 +1012,7 @@ int ensure_sort_workspace(baz_music_ctx* c, uint32_t batch)
         std::memset(c->hFire, 0, 4 * sizeof(unsigned long long));
         HIP_TRY(c, hipHostGetDevicePointer((void**)&c->hFireDev, c->hFire, 0));
     }
-    if (!c->dKT) return BAZ_MUSIC_OK;
+    if (!c->tab.dKT) return BAZ_MUSIC_OK;
     if (!c->dHist) {
         HIP_TRY(c, dev_malloc((void**)&c->dHist, bazsort::KEY_BUCKETS * sizeof(uint32_t)));
         HIP_TRY(c, dev_malloc((void**)&c->dCursor, bazsort::KEY_BUCKETS * sizeof(uint32_t)));
@@ -1042,7 +1040,7 @@ int ensure_sort_workspace(baz_music_ctx* c, uint32_t batch)
 // Up to 4 antennas (the rows' coefficients sit in registers; from 5 on the exact tiles fetch them from L2, where an index list costs gathers).
 bool sort_decide(baz_music_ctx* c, uint32_t batch)
 {
-    if (batch < SORT_MIN_BATCH || !c->dKT || !c->hFire || c->m > 4 || c->n > 2 || c->coarse_rg == 2 || c->coarse_lab) return false;
+    if (batch < SORT_MIN_BATCH || !c->tab.dKT || !c->hFire || c->m > 4 || c->n > 2 || c->coarse_rg == 2 || c->coarse_lab) return false;
     if (c->sort_mode >= 0) return c->sort_mode != 0;
     ++c->sort_clock;
     const unsigned long long tag = reinterpret_cast<volatile unsigned long long*>(c->hFire)[2];
@@ -1075,7 +1073,7 @@ int launch_sort_t(baz_music_ctx* c, const double* dQ, uint32_t qstride, uint32_t
     if constexpr (M <= 8) {
         const uint32_t ns = bazsort::key_samples(c->res);
         const uint32_t padded = round_up(batch, 256);          // whole workgroups of the key kernel = whole 8-key loads of the sweeps
-        hipLaunchKernelGGL((bazsort::coarse_key_kernel<M>), dim3(padded / 256), dim3(256), 0, c->stream, dQ, c->dKT, ns, batch, qstride, c->dKeys);
+        hipLaunchKernelGGL((bazsort::coarse_key_kernel<M>), dim3(padded / 256), dim3(256), 0, c->stream, dQ, c->tab.dKT, ns, batch, qstride, c->dKeys);
         HIP_TRY(c, hipGetLastError());
         hipLaunchKernelGGL((bazsort::key_sweep_kernel<false>), dim3(bazsort::KEY_BLOCKS), dim3(256), 0, c->stream, c->dKeys, padded / 8, c->dHist,
                            c->dCursor, c->dPerm);
@@ -1088,6 +1086,30 @@ int launch_sort_t(baz_music_ctx* c, const double* dQ, uint32_t qstride, uint32_t
 }
 #endif   // BAZ_MUSIC_LAB
 
+// The refinement arguments of a product scan launch (literal_tile()): the noise eigenvectors of the workspace, the raw-table image in
+// force and its threshold, the statistic counter of the call in flight; `a2`: with ||a||^2 per bin, which the fp64 scan's short form reads.
+ScanRefine scan_refine(const baz_music_ctx* c, bool a2)
+{
+    ScanRefine rf;
+    rf.Gs = c->refine_off ? nullptr : c->dG;
+    rf.TB = c->tab.dTB + c->tb_step_elems;
+    rf.below = c->tab.refine_below;
+    rf.count = c->refine_nocount ? nullptr : c->dRefined + c->stat_parity;
+    rf.A2 = (a2 && c->tab.dA2p) ? c->tab.dA2p + 64 : nullptr;
+    return rf;
+}
+// ... and of the debug taps' validation launches: nothing refined, nothing counted
+ScanRefine scan_refine_validation(const baz_music_ctx* c)
+{
+    ScanRefine rf;
+    rf.Gs = nullptr;
+    rf.TB = c->tab.dTB + c->tb_step_elems;
+    rf.below = 0.0;
+    rf.count = nullptr;
+    rf.A2 = nullptr;
+    return rf;
+}
+
 template <int M, int NMAX>
 int launch_scan_t(baz_music_ctx* c, const double* dQ, uint32_t qstride, uint32_t batch, float* d_ang,
                   float* d_lvl, float* d_spec)
@@ -1098,12 +1120,7 @@ int launch_scan_t(baz_music_ctx* c, const double* dQ, uint32_t qstride, uint32_t
         if (!d_spec && coarse_applies(c) && dQ == c->dQ && !c->order_mode) {
             const CoarseGeom CG = coarse_geometry(c, batch);
             if ((size_t)batch * CG.nsplit * NMAX > c->cand_cap) return BAZ_MUSIC_E_INVALID;
-            ScanRefine rf;
-            rf.Gs = c->refine_off ? nullptr : c->dG;
-            rf.TB = c->dTB + c->tb_step_elems;
-            rf.below = c->refine_below;
-            rf.count = c->refine_nocount ? nullptr : c->dRefined + c->stat_parity;
-            rf.A2 = nullptr;
+            const ScanRefine rf = scan_refine(c, false);
             unsigned long long* stats = c->coarse_stats ? c->dMargin : nullptr;     // lab: exact tile evaluations, summed over launches
 #ifdef BAZ_MUSIC_LAB
             // lab (BAZ_MUSIC_SORT): the items in an order in which neighbours share their nulls, while the scan's own statistic says that pays
@@ -1124,8 +1141,8 @@ int launch_scan_t(baz_music_ctx* c, const double* dQ, uint32_t qstride, uint32_t
             const uint32_t* perm = nullptr;                 // the product walks the items in their own order and keeps no fire statistic
             unsigned long long* fstat = nullptr;
 #endif
-#define BAZ_COARSE_ARGS dim3(CG.groups * CG.nsplit), dim3(256), 0, c->stream, dQ, c->dCS, c->dCS + (size_t)(c->cs_tiles + 1) * cs_c_units(M), \
-                        c->dCand, batch, c->res, qstride, CG.nphases, CG.nsplit, c->keep_mask, c->n, rf, c->cs, stats, nullptr, perm, fstat
+#define BAZ_COARSE_ARGS dim3(CG.groups * CG.nsplit), dim3(256), 0, c->stream, dQ, c->tab.dCS, c->tab.dCS + (size_t)(c->cs_tiles + 1) * cs_c_units(M), \
+                        c->dCand, batch, c->res, qstride, CG.nphases, CG.nsplit, c->keep_mask, c->n, rf, c->tab.cs, stats, nullptr, perm, fstat
 #ifdef BAZ_MUSIC_LAB
             if (c->sort_mode != 0 && M <= 4 && CG.tpp != 4 && !c->coarse_lab) {        // lab (BAZ_MUSIC_SORT): the index list and the fire statistic
                 if constexpr (M <= 4) hipLaunchKernelGGL((scan_coarse_kernel<M, NMAX, 4, 8, false, 0, true>), BAZ_COARSE_ARGS);
@@ -1156,16 +1173,11 @@ int launch_scan_t(baz_music_ctx* c, const double* dQ, uint32_t qstride, uint32_t
         // LAB (BAZ_MUSIC_I8P=1): 2 .. 4 antennas with the spectrum port: the int8 matrix core with level-packed operands (scan_i8p_kernels.hip.h); same
         // geometry (row classes, bin ranges) and candidate lists as the fp64 scan below.  Without the port the coarse-gated scan above.
         if (spec && i8p_active(c) && dQ == c->dQ) {
-            ScanRefine rf;
-            rf.Gs = c->refine_off ? nullptr : c->dG;
-            rf.TB = c->dTB + c->tb_step_elems;
-            rf.below = c->refine_below;
-            rf.count = c->refine_nocount ? nullptr : c->dRefined + c->stat_parity;
-            rf.A2 = nullptr;
-            const uint4* p1 = c->dIP + I8P_STEP_UNITS;                            // step 0 (a padded step lies in front)
+            const ScanRefine rf = scan_refine(c, false);
+            const uint4* p1 = c->tab.dIP + I8P_STEP_UNITS;                            // step 0 (a padded step lies in front)
             const uint4* p2 = p1 + i8p_operand_units(c->fb_steps);
-#define BAZ_I8P_ARGS dim3(G.blocks), dim3(256), 0, c->stream, dQ, p1, p2, c->dFB + c->fb_step_elems, d_spec, cand, batch, c->res, qstride, \
-                     G.nsplit, c->nclass, G.rows_per_class, c->keep_mask, c->n, rf, c->i8, c->dI8Stat, nullptr
+#define BAZ_I8P_ARGS dim3(G.blocks), dim3(256), 0, c->stream, dQ, p1, p2, c->tab.dFB + c->fb_step_elems, d_spec, cand, batch, c->res, qstride, \
+                     G.nsplit, c->nclass, G.rows_per_class, c->keep_mask, c->n, rf, c->tab.i8, c->dI8Stat, nullptr
 #ifdef BAZ_MUSIC_LAB
             if constexpr (M == 4 && NMAX == 2) {       // lab: timing ablations (wrong results)
                 if (vec4 && c->i8_abl) {
@@ -1196,12 +1208,7 @@ int launch_scan_t(baz_music_ctx* c, const double* dQ, uint32_t qstride, uint32_t
         // must stay bit-identical to it: the fp64 scan below.  One emitter from 6 antennas on has no gated scan: here.)
         const bool gated_shape = M <= 8 && NMAX <= 4 && !short_form_applies(c->m, c->n);
         if (i8_active(c) && dQ == c->dQ && (spec || !gated_shape)) {
-            ScanRefine rf;
-            rf.Gs = c->refine_off ? nullptr : c->dG;
-            rf.TB = c->dTB + c->tb_step_elems;
-            rf.below = c->refine_below;
-            rf.count = c->refine_nocount ? nullptr : c->dRefined + c->stat_parity;
-            rf.A2 = nullptr;
+            const ScanRefine rf = scan_refine(c, false);
             // its own bin ranges: whole rounds of the resident workgroup slots (i8_nsplit)
             int& per_cu = c->i8_wgs_per_cu[NMAX > 2 ? 1 : 0][spec ? 1 : 0][vec4 ? 1 : 0];
             if (per_cu == 0) {
@@ -1218,16 +1225,16 @@ int launch_scan_t(baz_music_ctx* c, const double* dQ, uint32_t qstride, uint32_t
             c->last_nsplit = G.nsplit;
             if ((size_t)batch * G.nsplit * NMAX > c->cand_cap) return BAZ_MUSIC_E_INVALID;
 #define BAZ_I8_LAUNCH(SPEC, VEC4)                                                                                       \
-    hipLaunchKernelGGL((scan_i8_kernel<M, NMAX, SPEC, VEC4>), dim3(G.blocks), dim3(256), 0, c->stream, dQ, c->dIB,      \
-                       c->dIB + i8_image_bytes5(c->m, c->fb_steps) / 16, c->dFB + c->fb_step_elems, d_spec, cand, batch, c->res, qstride, G.nsplit, c->keep_mask, scan_n(c), rf, \
-                       c->i8, c->dI8Stat, nullptr)
+    hipLaunchKernelGGL((scan_i8_kernel<M, NMAX, SPEC, VEC4>), dim3(G.blocks), dim3(256), 0, c->stream, dQ, c->tab.dIB,      \
+                       c->tab.dIB + i8_image_bytes5(c->m, c->fb_steps) / 16, c->tab.dFB + c->fb_step_elems, d_spec, cand, batch, c->res, qstride, G.nsplit, c->keep_mask, scan_n(c), rf, \
+                       c->tab.i8, c->dI8Stat, nullptr)
 #ifdef BAZ_MUSIC_LAB
             if constexpr ((M == 8 || M == 16) && NMAX == 2) {        // lab: ablations of the bulk loop (timing only, wrong results)
                 if (spec && vec4 && c->i8_abl) {
 #define BAZ_I8_ABL(ABLV)                                                                                                  \
-    hipLaunchKernelGGL((scan_i8_kernel<M, NMAX, true, true, false, ABLV>), dim3(G.blocks), dim3(256), 0, c->stream, dQ, c->dIB, \
-                       c->dIB + i8_image_bytes5(c->m, c->fb_steps) / 16, c->dFB + c->fb_step_elems, d_spec, cand, batch, c->res, \
-                       qstride, G.nsplit, c->keep_mask, c->n, rf, c->i8, c->dI8Stat, nullptr)
+    hipLaunchKernelGGL((scan_i8_kernel<M, NMAX, true, true, false, ABLV>), dim3(G.blocks), dim3(256), 0, c->stream, dQ, c->tab.dIB, \
+                       c->tab.dIB + i8_image_bytes5(c->m, c->fb_steps) / 16, c->tab.dFB + c->fb_step_elems, d_spec, cand, batch, c->res, \
+                       qstride, G.nsplit, c->keep_mask, c->n, rf, c->tab.i8, c->dI8Stat, nullptr)
                     switch (c->i8_abl) {
                         case 1: BAZ_I8_ABL(1); break;      // no spectrum stores
                         case 4: BAZ_I8_ABL(4); break;      // no MFMAs
@@ -1254,18 +1261,13 @@ int launch_scan_t(baz_music_ctx* c, const double* dQ, uint32_t qstride, uint32_t
         }
     }
     c->scan_kind = 0;
-    ScanRefine rf;
-    rf.Gs = c->refine_off ? nullptr : c->dG;
-    rf.TB = c->dTB + c->tb_step_elems;
-    rf.below = c->refine_below;
-    rf.count = c->refine_nocount ? nullptr : c->dRefined + c->stat_parity;
-    rf.A2 = c->dA2p ? c->dA2p + 64 : nullptr;
-    const double2* fb0 = c->dFB + c->fb_step_elems;   // step 0 (a padded step lies in front)
+    const ScanRefine rf = scan_refine(c, true);
+    const double2* fb0 = c->tab.dFB + c->fb_step_elems;   // step 0 (a padded step lies in front)
     if constexpr (M >= 6 && NMAX == 2) {
         // one or two emitters: the short form ||a||^2 - sum_c |s_c^H a|^2 (scan_mfma_kernel, SIG) where it needs fewer
         // MFMAs than the projector GEMM: n = 2 from 9 antennas, n = 1 from 6
         if (short_form_in_use(c) && dQ == c->dQ) {
-            const double2* tb0 = c->dTB + c->tb_step_elems;
+            const double2* tb0 = c->tab.dTB + c->tb_step_elems;
 #define BAZ_SIG_LAUNCH(SPEC, VEC4, SIGV)                                                                                    \
     hipLaunchKernelGGL((scan_mfma_kernel<M, NMAX, SPEC, VEC4, 0, (1 | 2 | 16), SIGV>), dim3(G.blocks), dim3(256), 0, c->stream, \
                        c->dSs, tb0, d_spec, cand, batch, c->res, qstride, G.nsplit, c->nclass, G.rows_per_class, c->keep_mask, scan_n(c), rf, (uint32_t)c->seq_walk)
@@ -1363,8 +1365,8 @@ uint32_t topn_list_len(uint32_t n) { return n <= 2 ? 2u : (n <= 4 ? 4u : (n <= 8
 size_t cand_entries(const baz_music_ctx* c, uint32_t nb)
 {
     size_t per_item = scan_geometry(nb, c->fb_steps, c->nclass, c->force_nsplit, c->m).nsplit;
-    if (c->m <= 8 && c->dCS) per_item = std::max<size_t>(per_item, coarse_geometry(c, nb).nsplit);
-    if (c->dIB) per_item = std::max<size_t>(per_item, c->force_nsplit > 0 ? (size_t)std::min<uint32_t>((uint32_t)c->force_nsplit, 64u) : I8_MAX_NSPLIT);
+    if (c->m <= 8 && c->tab.dCS) per_item = std::max<size_t>(per_item, coarse_geometry(c, nb).nsplit);
+    if (c->tab.dIB) per_item = std::max<size_t>(per_item, c->force_nsplit > 0 ? (size_t)std::min<uint32_t>((uint32_t)c->force_nsplit, 64u) : I8_MAX_NSPLIT);
     return (size_t)nb * per_item * topn_list_len(c->n);
 }
 
@@ -1382,7 +1384,7 @@ size_t cand_entries_upto(const baz_music_ctx* c, uint32_t batch)
     // ->  nb * nsplit <= 256 * WANT + nb
     const size_t coarse = (c->m <= 8) ? std::min<size_t>((size_t)batch * 16u, 256u * COARSE_WANT_BLOCKS + (size_t)batch) : 0;
     // the int8 scan: nsplit <= r slots / ceil(nb / 64) with r <= 8 rounds of <= 4 x 256-CU slots, and <= I8_MAX_NSPLIT
-    const size_t i8 = c->dIB ? std::min<size_t>((size_t)batch * I8_MAX_NSPLIT, (size_t)64u * 8u * 4u * c->num_cus + (size_t)batch) : 0;
+    const size_t i8 = c->tab.dIB ? std::min<size_t>((size_t)batch * I8_MAX_NSPLIT, (size_t)64u * 8u * 4u * c->num_cus + (size_t)batch) : 0;
     return std::max(std::max(std::max(std::max(worst, forced), coarse), i8), (size_t)batch) * topn_list_len(c->n);
 }
 
@@ -1480,13 +1482,13 @@ int ensure_wide_workspace(baz_music_ctx* c, uint32_t items)
     if (c->dGw) { (void)dev_free(c->dGw); c->dGw = nullptr; }
     if (c->dWS) { (void)dev_free(c->dWS); c->dWS = nullptr; }
     if (c->dSw) { (void)dev_free(c->dSw); c->dSw = nullptr; }
+    if (c->dRedo) { (void)dev_free(c->dRedo); c->dRedo = nullptr; }
     c->wide_cap = 0;
     const size_t mm = (size_t)c->m * c->m;
     HIP_TRY(c, dev_malloc((void**)&c->dR, (size_t)items * mm * sizeof(double2)));
     HIP_TRY(c, dev_malloc((void**)&c->dGw, (size_t)items * (c->m - c->n) * c->m * sizeof(double2)));
     HIP_TRY(c, dev_malloc((void**)&c->dWS, (size_t)items * c->res * sizeof(double)));
     HIP_TRY(c, dev_malloc((void**)&c->dSw, (size_t)items * c->n * c->m * sizeof(double2)));
-    if (c->dRedo) { (void)dev_free(c->dRedo); c->dRedo = nullptr; }
     HIP_TRY(c, dev_malloc((void**)&c->dRedo, (size_t)items));
     c->wide_cap = items;
     return BAZ_MUSIC_OK;
@@ -1578,8 +1580,8 @@ int process_wide_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, void
             {
                 ProfScope ps(c, BAZ_MUSIC_STAGE_SCAN);
                 const bool vec4 = sp && (c->res % 4u) == 0 && (reinterpret_cast<uintptr_t>(sp) % 16u) == 0;
-#define BAZ_WIDE_ARGS dim3(groups * nsplit), dim3(256), 0, c->stream, c->dSw, c->dGw, c->dTB + c->tb_step_elems, c->dA2p + 64, c->dTA, sp, \
-                      c->dCand, nb, c->m, c->n, c->res, nsplit, c->keep_mask, c->refine_below, c->dRefined + c->stat_parity
+#define BAZ_WIDE_ARGS dim3(groups * nsplit), dim3(256), 0, c->stream, c->dSw, c->dGw, c->tab.dTB + c->tb_step_elems, c->tab.dA2p + 64, c->tab.dTA, sp, \
+                      c->dCand, nb, c->m, c->n, c->res, nsplit, c->keep_mask, c->tab.refine_below, c->dRefined + c->stat_parity
 #define BAZ_WIDE_LAUNCH(PMAX, NOUT)                                                                                       \
     do {                                                                                                                  \
         if (sp && vec4) hipLaunchKernelGGL((bazwide::scan_wide_mfma_kernel<true, true, PMAX, NOUT>), BAZ_WIDE_ARGS);      \
@@ -1623,7 +1625,7 @@ int process_wide_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, void
             const bool short_form = 2 * c->n <= c->m && !c->wide_literal_only;     // few emitters: ||a||^2 - ||S^H a||^2 away from the nulls
             hipLaunchKernelGGL(bazwide::scan_wide_kernel, dim3(nb, (c->res + bpb - 1) / bpb), dim3(bazwide::WB),
                                (size_t)(nn + (short_form ? c->n : 0u)) * c->m * sizeof(double2), c->stream, c->dGw,
-                               short_form ? c->dSw : nullptr, c->dTA, c->dA2, c->refine_below, c->dWS,
+                               short_form ? c->dSw : nullptr, c->tab.dTA, c->tab.dA2, c->tab.refine_below, c->dWS,
                                spec ? spec + (size_t)off * c->res : nullptr, c->m, c->n, c->res, bpb);
             HIP_TRY(c, hipGetLastError());
         }
@@ -1689,28 +1691,6 @@ void free_table_set(TableSet& T)
     if (T.dTA) (void)dev_free(T.dTA);
     if (T.dA2) (void)dev_free(T.dA2);
     T = TableSet();
-}
-
-// the set the kernels are launched with lives in the context's own fields (every launch site reads c->dFB, c->cs, ...)
-TableSet active_table_set(const baz_music_ctx* c)
-{
-    TableSet T;
-    T.dFB = c->dFB; T.dTB = c->dTB; T.dCS = c->dCS; T.dIB = c->dIB; T.dA2p = c->dA2p; T.dTA = c->dTA; T.dA2 = c->dA2;
-#ifdef BAZ_MUSIC_LAB
-    T.dIP = c->dIP;
-    T.dKT = c->dKT;
-#endif
-    T.cs = c->cs; T.i8 = c->i8; T.cs_ok = c->cs_ok; T.i8_ok = c->i8_ok; T.refine_below = c->refine_below;
-    return T;
-}
-void install_table_set(baz_music_ctx* c, const TableSet& T)
-{
-    c->dFB = T.dFB; c->dTB = T.dTB; c->dCS = T.dCS; c->dIB = T.dIB; c->dA2p = T.dA2p; c->dTA = T.dTA; c->dA2 = T.dA2;
-#ifdef BAZ_MUSIC_LAB
-    c->dIP = T.dIP;
-    c->dKT = T.dKT;
-#endif
-    c->cs = T.cs; c->i8 = T.i8; c->cs_ok = T.cs_ok; c->i8_ok = T.i8_ok; c->refine_below = T.refine_below;
 }
 
 inline dim3 grid_for(size_t threads) { return dim3((unsigned)((threads + 255) / 256)); }
@@ -1842,12 +1822,7 @@ int retune(baz_music_ctx* c, const float* table_ri, bool first)
 {
     const auto t0 = std::chrono::steady_clock::now();
     std::memcpy(c->hRaw, table_ri, (size_t)c->res * c->m * 2 * sizeof(float));
-    if (first) {
-        TableSet T = active_table_set(c);
-        const int r = build_tables_device(c, T);
-        install_table_set(c, T);
-        return r;
-    }
+    if (first) return build_tables_device(c, c->tab);
     // the shadow set was the active one until the previous swap: batches launched before that swap may still read it
     if (c->swap_recorded) HIP_TRY(c, hipStreamWaitEvent(c->s_tab, c->ev_swap, 0));
     const int r = build_tables_device(c, c->shadow);
@@ -1855,9 +1830,7 @@ int retune(baz_music_ctx* c, const float* table_ri, bool first)
     const auto t1 = std::chrono::steady_clock::now();
     {
         std::lock_guard<std::mutex> lk(c->mtx);           // .cc:67 -- for the exchange of a few pointers only
-        const TableSet old = active_table_set(c);
-        install_table_set(c, c->shadow);
-        c->shadow = old;
+        std::swap(c->tab, c->shadow);
         c->swap_recorded = hipEventRecord(c->ev_swap, c->stream) == hipSuccess;
         if (!c->swap_recorded) {                          // cannot order the next retune behind the batches in flight: drain them now
             (void)hipGetLastError();
@@ -2106,20 +2079,25 @@ int refuse_null(baz_music_ctx* c, const void* p, const char* name)
         if (const int rn__ = refuse_null((c), (c)->ptr, #ptr)) return rn__; \
     } while (0)
 
+#define BAZ_REQUIRE_TAB(c, ptr)                              \
+    do {                                                     \
+        if (const int rn__ = refuse_null((c), (c)->tab.ptr, #ptr)) return rn__; \
+    } while (0)
+
 int check_launch_pointers(baz_music_ctx* c)
 {
     BAZ_REQUIRE(c, dRefined);
     BAZ_REQUIRE(c, dR);
     BAZ_REQUIRE(c, dRedo);
     if (c->wide) {
-        BAZ_REQUIRE(c, dGw); BAZ_REQUIRE(c, dWS); BAZ_REQUIRE(c, dSw); BAZ_REQUIRE(c, dTA); BAZ_REQUIRE(c, dA2);
-        if (c->wide_mfma) { BAZ_REQUIRE(c, dTB); BAZ_REQUIRE(c, dA2p); }
+        BAZ_REQUIRE(c, dGw); BAZ_REQUIRE(c, dWS); BAZ_REQUIRE(c, dSw); BAZ_REQUIRE_TAB(c, dTA); BAZ_REQUIRE_TAB(c, dA2);
+        if (c->wide_mfma) { BAZ_REQUIRE_TAB(c, dTB); BAZ_REQUIRE_TAB(c, dA2p); }
         return BAZ_MUSIC_OK;
     }
-    BAZ_REQUIRE(c, dQ); BAZ_REQUIRE(c, dG); BAZ_REQUIRE(c, dCand); BAZ_REQUIRE(c, dFB); BAZ_REQUIRE(c, dTB);
-    if (short_form_applies(c->m, c->n)) { BAZ_REQUIRE(c, dSs); BAZ_REQUIRE(c, dA2p); }
-    if (c->cs_ok) BAZ_REQUIRE(c, dCS);
-    if (c->i8_ok && wants_i8_image(c)) BAZ_REQUIRE(c, dIB);
+    BAZ_REQUIRE(c, dQ); BAZ_REQUIRE(c, dG); BAZ_REQUIRE(c, dCand); BAZ_REQUIRE_TAB(c, dFB); BAZ_REQUIRE_TAB(c, dTB);
+    if (short_form_applies(c->m, c->n)) { BAZ_REQUIRE(c, dSs); BAZ_REQUIRE_TAB(c, dA2p); }
+    if (c->tab.cs_ok) BAZ_REQUIRE_TAB(c, dCS);
+    if (c->tab.i8_ok && wants_i8_image(c)) BAZ_REQUIRE_TAB(c, dIB);
     return BAZ_MUSIC_OK;
 }
 
@@ -2144,24 +2122,13 @@ int process_device_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, vo
         if (!c->ord_on || !c->dOrd || (size_t)c->ord_count + batch > c->ord_cap) return refuse_null(c, nullptr, "dOrd (order_begin)");
         c->ord_cur = ord;
     }
-    if (c->fused_covevd) {
-        r = launch_covevd(c, static_cast<const float*>(d_in), batch, c->dQ, qstride, c->dG);
-    } else {
-        r = launch_cov(c, static_cast<const float*>(d_in), batch, c->dR);
-        if (r == BAZ_MUSIC_OK) r = launch_evd(c, c->dR, batch, c->dQ, qstride, c->dG);
-    }
+    r = launch_frontend(c, d_in, batch, c->dQ, qstride);
     c->ord_cur = nullptr;
     if (r) return r;
     float* spec = static_cast<float*>(d_spec);
     if (c->peak_mode && !spec) {   // the peak picker reads the spectrum: keep a private one when port 2 is not wired
-        const size_t need = (size_t)batch * c->res;
-        if (need > c->peak_spec_cap) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            if (c->dPeakSpec) (void)dev_free(c->dPeakSpec);
-            c->dPeakSpec = nullptr; c->peak_spec_cap = 0;
-            HIP_TRY(c, dev_malloc((void**)&c->dPeakSpec, need * sizeof(float)));
-            c->peak_spec_cap = need;
-        }
+        r = grow(c, c->dPeakSpec, c->peak_spec_cap, (size_t)batch * c->res);
+        if (r) return r;
         spec = c->dPeakSpec;
     }
     r = launch_scan(c, c->dQ, qstride, batch, static_cast<float*>(d_ang), static_cast<float*>(d_lvl), spec);
@@ -2209,9 +2176,7 @@ int create_tables(baz_music_ctx* c, const float* table_ri)
     if (hipHostMalloc((void**)&c->hRaw, raw_bytes, hipHostMallocDefault) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
     if (dev_malloc(&c->dTabStats, sizeof(baztab::TableStats)) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
     if (hipHostMalloc(&c->hTabStats, sizeof(baztab::TableStats), hipHostMallocDefault) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
-    TableSet first;
-    int r = alloc_table_set(c, first);
-    install_table_set(c, first);                          // (also after a failed allocation: destroy frees what exists)
+    int r = alloc_table_set(c, c->tab);                   // (a failed allocation leaves what it did allocate in the set: destroy frees it)
     if (r == BAZ_MUSIC_OK) r = alloc_table_set(c, c->shadow);
     if (r != BAZ_MUSIC_OK) return r;
     std::lock_guard<std::mutex> tl(c->tab_mtx);
@@ -2362,19 +2327,6 @@ uint32_t smooth_chunk(const baz_music_ctx* c, uint32_t batch)
     return (uint32_t)std::max<size_t>(1, std::min<size_t>(batch, (size_t)BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES / per_item));
 }
 
-// grows one device buffer of the mode (the stream is drained first: a batch in flight may still read the old one)
-template <typename T>
-int grow(baz_music_ctx* c, T*& p, size_t& cap, size_t need)
-{
-    if (need <= cap) return BAZ_MUSIC_OK;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (p) (void)dev_free(p);
-    p = nullptr; cap = 0;
-    HIP_TRY(c, dev_malloc((void**)&p, need * sizeof(T)));
-    cap = need;
-    return BAZ_MUSIC_OK;
-}
-
 int launch_restack(baz_music_ctx* c, const void* d_in, uint32_t nb)
 {
     auto& S = c->sm;
@@ -2435,6 +2387,19 @@ int smooth_host_locked(baz_music_ctx* c, const float* in_ri, uint32_t batch, flo
         if (r == BAZ_MUSIC_OK && es != hipSuccess) r = hip_fail(c, es, "hipStreamSynchronize");
     }
     return r ? r : (int)batch;
+}
+
+// One device-side call (c->mtx held), the body of both device entry points: opens the call for baz_music_last_orders, then the
+// smoothing mode's chunks or the statistic and one pass of the hot path.
+int process_device_call_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, void* d_ang, void* d_lvl, void* d_spec)
+{
+    if (!c->ord_driven) {                     // (an inner context of the smoothing mode: its outer context has opened the call)
+        const int ro = order_begin(c->sm.inner ? c->sm.inner : c, batch);
+        if (ro) return ro;
+    }
+    if (c->sm.inner) return smooth_device_locked(c, d_in, batch, d_ang, d_lvl, d_spec);
+    const int r = begin_statistic(c);
+    return r ? r : process_device_locked(c, d_in, batch, d_ang, d_lvl, d_spec);
 }
 
 }  // namespace
@@ -2634,12 +2599,8 @@ void baz_music_destroy(baz_music_ctx* c)
             for (auto e : p.ev) (void)hipEventDestroy(e);
         if (c->h_al_big) (void)hipHostFree(c->h_al_big);
         if (c->s_tab) (void)hipStreamSynchronize(c->s_tab);
-        {
-            TableSet act = active_table_set(c);
-            free_table_set(act);
-            install_table_set(c, act);
-            free_table_set(c->shadow);
-        }
+        free_table_set(c->tab);
+        free_table_set(c->shadow);
         if (c->dRaw) (void)dev_free(c->dRaw);
         if (c->hRaw) (void)hipHostFree(c->hRaw);
         if (c->dTabStats) (void)dev_free(c->dTabStats);
@@ -2764,13 +2725,7 @@ int baz_music_process_device(baz_music_ctx* c, const void* d_in, uint32_t batch,
     std::lock_guard<std::mutex> lk(c->mtx);   // .cc:101
     DeviceGuard guard(c->device);
     (void)hipGetLastError();                  // launches below are checked with hipGetLastError(): start from a clean slate
-    if (!c->ord_driven) {                     // (an inner context of the smoothing mode: its outer context has opened the call)
-        const int ro = order_begin(c->sm.inner ? c->sm.inner : c, batch);
-        if (ro) return ro;
-    }
-    if (c->sm.inner) return smooth_device_locked(c, d_in, batch, d_ang, d_lvl, d_spec);
-    int r = begin_statistic(c);
-    return r ? r : process_device_locked(c, d_in, batch, d_ang, d_lvl, d_spec);
+    return process_device_call_locked(c, d_in, batch, d_ang, d_lvl, d_spec);
 }
 
 int baz_music_process_device_on(baz_music_ctx* c, void* caller_stream, const void* d_in, uint32_t batch, void* d_ang,
@@ -2789,14 +2744,7 @@ int baz_music_process_device_on(baz_music_ctx* c, void* caller_stream, const voi
         HIP_TRY(c, hipEventRecord(c->ev_in, cs));
         HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_in, 0));
     }
-    int r = order_begin(c->sm.inner ? c->sm.inner : c, batch);
-    if (r != BAZ_MUSIC_OK) {
-    } else if (c->sm.inner) {
-        r = smooth_device_locked(c, d_in, batch, d_ang, d_lvl, d_spec);
-    } else {
-        r = begin_statistic(c);
-        if (r == BAZ_MUSIC_OK) r = process_device_locked(c, d_in, batch, d_ang, d_lvl, d_spec);
-    }
+    int r = process_device_call_locked(c, d_in, batch, d_ang, d_lvl, d_spec);
     if (foreign) {   // also after a failed launch: whatever was enqueued is ordered before the caller's next work
         hipError_t e = hipEventRecord(c->ev_out, c->stream);
         if (e == hipSuccess) e = hipStreamWaitEvent(cs, c->ev_out, 0);
@@ -2879,13 +2827,8 @@ int baz_music_process(baz_music_ctx* c, const float* in_ri, uint32_t batch, floa
             (void)hipGetLastError();           // not addressable from the device after all: the copy path below
         } else {
             float* z_ang = static_cast<float*>(z_al);
-            int zr = BAZ_MUSIC_OK;
-            if (!c->wide) {
-                zr = ensure_workspace(c, batch);
-                if (zr == BAZ_MUSIC_OK) zr = reserve_candidates(c, batch);
-            }
-            if (zr == BAZ_MUSIC_OK) zr = begin_statistic(c);
-            if (zr == BAZ_MUSIC_OK)
+            int zr = begin_statistic(c);
+            if (zr == BAZ_MUSIC_OK)           // (sizes the workspace and the candidate lists for `batch` itself, before its first launch)
                 zr = process_device_locked(c, z_in, batch, z_ang, z_ang + (size_t)batch * c->n, want_spec ? z_spec : nullptr);
             const hipError_t es = hipStreamSynchronize(c->stream);   // also after a failed launch
             if (zr == BAZ_MUSIC_OK && es != hipSuccess) zr = hip_fail(c, es, "hipStreamSynchronize");
@@ -3097,11 +3040,7 @@ int baz_music_debug_q(baz_music_ctx* c, const void* d_in, uint32_t batch, void* 
     if (c->wide || c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;   // the wide path forms no projector (literal form straight from G)
     int r = ensure_workspace(c, batch);
     if (r) return r;
-    const uint32_t qstride = baz_music_q_stride(batch);
-    if (c->fused_covevd) return launch_covevd(c, static_cast<const float*>(d_in), batch, static_cast<double*>(d_Q), qstride, c->dG);
-    r = launch_cov(c, static_cast<const float*>(d_in), batch, c->dR);
-    if (r) return r;
-    return launch_evd(c, c->dR, batch, static_cast<double*>(d_Q), qstride, c->dG);
+    return launch_frontend(c, d_in, batch, static_cast<double*>(d_Q), baz_music_q_stride(batch));
 }
 
 // Validation of the coarse-gated scan's error bound on this hardware (scan_coarse_kernels.hip.h, VAL): covariance + EVD of
@@ -3112,21 +3051,16 @@ int baz_music_debug_coarse_margin(baz_music_ctx* c, const void* d_in, uint32_t b
     if (!c || !d_in || !worst || batch == 0) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
     DeviceGuard guard(c->device);
-    if (c->wide || c->m > 8 || c->n > 4 || !c->cs_ok || c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;
+    if (c->wide || c->m > 8 || c->n > 4 || !c->tab.cs_ok || c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;
     int r = ensure_workspace(c, batch);
     if (r) return r;
     r = reserve_candidates(c, batch);
     if (r) return r;
     const uint32_t qstride = baz_music_q_stride(batch);
-    if (c->fused_covevd) r = launch_covevd(c, static_cast<const float*>(d_in), batch, c->dQ, qstride, c->dG);
-    else {
-        r = launch_cov(c, static_cast<const float*>(d_in), batch, c->dR);
-        if (!r) r = launch_evd(c, c->dR, batch, c->dQ, qstride, c->dG);
-    }
+    r = launch_frontend(c, d_in, batch, c->dQ, qstride);
     if (r) return r;
     HIP_TRY(c, hipMemsetAsync(c->dMargin, 0, sizeof(unsigned long long), c->stream));
-    ScanRefine rf;
-    rf.Gs = nullptr; rf.TB = c->dTB + c->tb_step_elems; rf.below = 0.0; rf.count = nullptr; rf.A2 = nullptr;
+    const ScanRefine rf = scan_refine_validation(c);
     const bool big = c->m > 4;                   // (m >= 5: the RG = 2, TPP = 4 instantiation, like the scan's)
     const uint32_t per_group = big ? 64u * (uint32_t)coarse_rg_wide((int)c->m, 2) : 256u;
     const uint32_t groups = (batch + per_group - 1) / per_group, nph = c->cs_tiles / (big ? 4 : 8);
@@ -3135,9 +3069,9 @@ int baz_music_debug_coarse_margin(baz_music_ctx* c, const void* d_in, uint32_t b
     if (dump_path && dev_malloc((void**)&d_dump, (size_t)batch * c->res * sizeof(float)) != hipSuccess) d_dump = nullptr;
     if (d_dump) (void)hipMemsetAsync(d_dump, 0, (size_t)batch * c->res * sizeof(float), c->stream);
 #define BAZ_VAL(MV, NV, RGV, TPV)                                                                                           \
-    hipLaunchKernelGGL((scan_coarse_kernel<MV, NV, RGV, TPV, true>), dim3(groups), dim3(256), 0, c->stream, c->dQ, c->dCS, \
-                       c->dCS + (size_t)(c->cs_tiles + 1) * cs_c_units(MV), c->dCand,                                                  \
-                       batch, c->res, qstride, nph, 1u, c->keep_mask, c->n, rf, c->cs, c->dMargin, d_dump)
+    hipLaunchKernelGGL((scan_coarse_kernel<MV, NV, RGV, TPV, true>), dim3(groups), dim3(256), 0, c->stream, c->dQ, c->tab.dCS, \
+                       c->tab.dCS + (size_t)(c->cs_tiles + 1) * cs_c_units(MV), c->dCand,                                                  \
+                       batch, c->res, qstride, nph, 1u, c->keep_mask, c->n, rf, c->tab.cs, c->dMargin, d_dump)
     const bool n2 = c->n <= 2;
     switch (c->m) {
         case 2: BAZ_VAL(2, 2, 4, 8); break;
@@ -3181,6 +3115,21 @@ int64_t baz_music_debug_coarse_fired(baz_music_ctx* c)
     return (int64_t)v;
 }
 
+namespace {
+// the three VAL margins a validation launch of the int8 forms left in dI8Stat[2 .. 4] (float bits), read back behind a drain of the stream
+int read_i8_margins(baz_music_ctx* c, float* worst)
+{
+    unsigned long long packed[3] = {0, 0, 0};
+    HIP_TRY(c, hipMemcpyAsync(packed, c->dI8Stat + 2, sizeof(packed), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 3; ++k) {
+        const unsigned int bits = (unsigned int)packed[k];
+        std::memcpy(worst + k, &bits, sizeof(float));
+    }
+    return BAZ_MUSIC_OK;
+}
+}  // namespace
+
 // Validation of the int8 scan's a-priori bounds on this hardware (scan_i8_kernels.hip.h, VAL): covariance + EVD of the batch,
 // then EVERY (item, bin) in the four-, five-, seven-digit and the fp64 form; worst[0] = max |d5 - d| / E5, worst[1] = max |d7 - d| /
 // allowance, worst[2] = max |d4 - d| / E4 over the items that take the integer forms.
@@ -3191,29 +3140,24 @@ int baz_music_debug_i8_margin(baz_music_ctx* c, const void* d_in, uint32_t batch
     DeviceGuard guard(c->device);
     if (c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;
 #ifdef BAZ_MUSIC_LAB
-    if (!c->wide && c->m <= 4 && c->m >= 2 && c->n <= 4 && c->dIP && c->i8_ok) {
+    if (!c->wide && c->m <= 4 && c->m >= 2 && c->n <= 4 && c->tab.dIP && c->tab.i8_ok) {
         // 2 .. 4 antennas: the level-packed form (scan_i8p_kernels.hip.h), VAL instantiation, one bin range per row
         int r = ensure_workspace(c, batch);
         if (r) return r;
         r = reserve_candidates(c, batch);
         if (r) return r;
         const uint32_t qstride = baz_music_q_stride(batch);
-        if (c->fused_covevd) r = launch_covevd(c, static_cast<const float*>(d_in), batch, c->dQ, qstride, c->dG);
-        else {
-            r = launch_cov(c, static_cast<const float*>(d_in), batch, c->dR);
-            if (!r) r = launch_evd(c, c->dR, batch, c->dQ, qstride, c->dG);
-        }
+        r = launch_frontend(c, d_in, batch, c->dQ, qstride);
         if (r) return r;
         HIP_TRY(c, hipMemsetAsync(c->dI8Stat + 2, 0, 3 * sizeof(unsigned long long), c->stream));
-        ScanRefine rf;
-        rf.Gs = nullptr; rf.TB = c->dTB + c->tb_step_elems; rf.below = 0.0; rf.count = nullptr; rf.A2 = nullptr;
+        const ScanRefine rf = scan_refine_validation(c);
         const ScanGeom G = scan_geometry(batch, c->fb_steps, c->nclass, 1, c->m);
-        const uint4* p1 = c->dIP + I8P_STEP_UNITS;
+        const uint4* p1 = c->tab.dIP + I8P_STEP_UNITS;
         const uint4* p2 = p1 + i8p_operand_units(c->fb_steps);
 #define BAZ_VALP(MV)                                                                                                          \
     case MV: hipLaunchKernelGGL((scan_i8p_kernel<MV, 2, false, false, true>), dim3(G.blocks), dim3(256), 0, c->stream, c->dQ, p1, p2, \
-                                c->dFB + c->fb_step_elems, nullptr, c->dCand, batch, c->res, qstride, 1u, c->nclass, G.rows_per_class, \
-                                c->keep_mask, c->n, rf, c->i8, nullptr, c->dI8Stat + 2); break;
+                                c->tab.dFB + c->fb_step_elems, nullptr, c->dCand, batch, c->res, qstride, 1u, c->nclass, G.rows_per_class, \
+                                c->keep_mask, c->n, rf, c->tab.i8, nullptr, c->dI8Stat + 2); break;
         switch (c->m) {
 #ifndef BAZ_MUSIC_QUICK
             BAZ_VALP(2) BAZ_VALP(3)
@@ -3223,17 +3167,10 @@ int baz_music_debug_i8_margin(baz_music_ctx* c, const void* d_in, uint32_t batch
         }
 #undef BAZ_VALP
         HIP_TRY(c, hipGetLastError());
-        unsigned long long packed[3] = {0, 0, 0};
-        HIP_TRY(c, hipMemcpyAsync(packed, c->dI8Stat + 2, sizeof(packed), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        for (int k = 0; k < 3; ++k) {
-            const unsigned int bits = (unsigned int)packed[k];
-            std::memcpy(worst + k, &bits, sizeof(float));
-        }
-        return BAZ_MUSIC_OK;
+        return read_i8_margins(c, worst);
     }
 #endif
-    if (c->wide || !c->dIB || !c->i8_ok || c->m < 6 || c->m > 16 || c->n > 4) return BAZ_MUSIC_E_UNSUPPORTED;
+    if (c->wide || !c->tab.dIB || !c->tab.i8_ok || c->m < 6 || c->m > 16 || c->n > 4) return BAZ_MUSIC_E_UNSUPPORTED;
     int r = ensure_workspace(c, batch);
     if (r) return r;
     r = reserve_candidates(c, batch);
@@ -3241,18 +3178,16 @@ int baz_music_debug_i8_margin(baz_music_ctx* c, const void* d_in, uint32_t batch
     const uint32_t qstride = baz_music_q_stride(batch);
     const int on = c->i8_on;
     c->i8_on = 1;                       // (the EVD must write the projector coefficients: short_form_in_use())
-    r = launch_cov(c, static_cast<const float*>(d_in), batch, c->dR);
-    if (!r) r = launch_evd(c, c->dR, batch, c->dQ, qstride, c->dG);
+    r = launch_frontend(c, d_in, batch, c->dQ, qstride);
     c->i8_on = on;
     if (r) return r;
     HIP_TRY(c, hipMemsetAsync(c->dI8Stat + 2, 0, 3 * sizeof(unsigned long long), c->stream));
-    ScanRefine rf;
-    rf.Gs = nullptr; rf.TB = c->dTB + c->tb_step_elems; rf.below = 0.0; rf.count = nullptr; rf.A2 = nullptr;
+    const ScanRefine rf = scan_refine_validation(c);
     const uint32_t blocks = (batch + 63) / 64;
 #define BAZ_VAL8(MV)                                                                                                      \
     case MV: hipLaunchKernelGGL((scan_i8_kernel<MV, 2, false, false, true>), dim3(blocks), dim3(256), 0, c->stream, c->dQ, \
-                                c->dIB, c->dIB + i8_image_bytes5(c->m, c->fb_steps) / 16, c->dFB + c->fb_step_elems, nullptr, c->dCand, \
-                                batch, c->res, qstride, 1u, c->keep_mask, c->n, rf, c->i8, nullptr, c->dI8Stat + 2); break;
+                                c->tab.dIB, c->tab.dIB + i8_image_bytes5(c->m, c->fb_steps) / 16, c->tab.dFB + c->fb_step_elems, nullptr, c->dCand, \
+                                batch, c->res, qstride, 1u, c->keep_mask, c->n, rf, c->tab.i8, nullptr, c->dI8Stat + 2); break;
     switch (c->m) {
         BAZ_VAL8(6) BAZ_VAL8(7) BAZ_VAL8(8) BAZ_VAL8(9) BAZ_VAL8(10) BAZ_VAL8(11) BAZ_VAL8(12) BAZ_VAL8(13) BAZ_VAL8(14)
         BAZ_VAL8(15) BAZ_VAL8(16)
@@ -3260,14 +3195,7 @@ int baz_music_debug_i8_margin(baz_music_ctx* c, const void* d_in, uint32_t batch
     }
 #undef BAZ_VAL8
     HIP_TRY(c, hipGetLastError());
-    unsigned long long packed[3] = {0, 0, 0};
-    HIP_TRY(c, hipMemcpyAsync(packed, c->dI8Stat + 2, sizeof(packed), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (int k = 0; k < 3; ++k) {
-        const unsigned int bits = (unsigned int)packed[k];
-        std::memcpy(worst + k, &bits, sizeof(float));
-    }
-    return BAZ_MUSIC_OK;
+    return read_i8_margins(c, worst);
 }
 
 // Statistic of the int8 scan since the last read (resets): wave tiles (16 items x 16 bins) that ran the refined (seven-digit)
@@ -3370,24 +3298,24 @@ size_t baz_music_debug_table_image(baz_music_ctx* c, int which, void* out, size_
     const void* src = nullptr;
     size_t bytes = 0;
     switch (which) {
-        case 0: src = c->dFB; bytes = pad_steps * c->fb_step_elems * sizeof(double2); break;
-        case 1: src = c->dTB; bytes = pad_steps * c->tb_step_elems * sizeof(double2); break;
-        case 2: src = c->dCS; bytes = c->dCS ? coarse_image_bytes(c) : 0; break;
-        case 3: src = c->dIB; bytes = c->dIB ? i8_image_bytes(c->m, c->fb_steps) : 0; break;
-        case 4: src = c->dA2p; bytes = pad_steps * 64 * sizeof(double); break;
-        case 5: src = c->dTA; bytes = (size_t)c->m * c->res * sizeof(float2); break;
-        case 6: src = c->dA2; bytes = (size_t)c->res * sizeof(double); break;
+        case 0: src = c->tab.dFB; bytes = pad_steps * c->fb_step_elems * sizeof(double2); break;
+        case 1: src = c->tab.dTB; bytes = pad_steps * c->tb_step_elems * sizeof(double2); break;
+        case 2: src = c->tab.dCS; bytes = c->tab.dCS ? coarse_image_bytes(c) : 0; break;
+        case 3: src = c->tab.dIB; bytes = c->tab.dIB ? i8_image_bytes(c->m, c->fb_steps) : 0; break;
+        case 4: src = c->tab.dA2p; bytes = pad_steps * 64 * sizeof(double); break;
+        case 5: src = c->tab.dTA; bytes = (size_t)c->m * c->res * sizeof(float2); break;
+        case 6: src = c->tab.dA2; bytes = (size_t)c->res * sizeof(double); break;
 #ifdef BAZ_MUSIC_LAB
-        case 8: src = c->dIP; bytes = c->dIP ? i8p_image_bytes(c->fb_steps) : 0; break;
+        case 8: src = c->tab.dIP; bytes = c->tab.dIP ? i8p_image_bytes(c->fb_steps) : 0; break;
 #endif
         case 7: {
             double p[TABLE_NPARAMS];
 #ifdef BAZ_MUSIC_LAB
-            const bool any_i8 = c->dIB != nullptr || c->dIP != nullptr;
+            const bool any_i8 = c->tab.dIB != nullptr || c->tab.dIP != nullptr;
 #else
-            const bool any_i8 = c->dIB != nullptr;
+            const bool any_i8 = c->tab.dIB != nullptr;
 #endif
-            pack_table_params(active_table_set(c), c->dCS != nullptr, any_i8, p);
+            pack_table_params(c->tab, c->tab.dCS != nullptr, any_i8, p);
             if (out && out_bytes >= sizeof(p)) std::memcpy(out, p, sizeof(p));
             return sizeof(p);
         }
@@ -3395,7 +3323,7 @@ size_t baz_music_debug_table_image(baz_music_ctx* c, int which, void* out, size_
     }
     if (!src) return 0;
     // an image whose parameters could not be formed is not built (its bytes are whatever the buffer held): report it as absent
-    if ((which == 2 && !c->cs_ok) || ((which == 3 || which == 8) && !c->i8_ok)) return 0;
+    if ((which == 2 && !c->tab.cs_ok) || ((which == 3 || which == 8) && !c->tab.i8_ok)) return 0;
     if (out && out_bytes >= bytes) {
         if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) {
             (void)hipGetLastError();

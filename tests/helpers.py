@@ -53,10 +53,10 @@ def assert_doa_match(ang, lvl, ang_ref, lvl_ref, res, strength64=None):
 #     stores (float)(1 / d) (music_wide_kernels.hip.h:707-709), less.  RCP_ULPS = 3 ulp_f32, ulp_f32 = 2^-23 relative.
 #   * projector and short forms in fp64 (scan_mfma_kernel; the SIG short form ||a||^2 - ||S^H a||^2; the wide scans; the
 #     coarse-gated scan, whose outputs are those of scan_mfma_kernel bit for bit): absolute error ~ m^2 eps ||a||^2
-#     (music_kernels.hip.h:1375-1379, baz_music_hip.hip:1694-1696), kept only where d > refine_below = m 1e-8 max||a||^2
-#     (baz_music_hip.hip:1696, 3117; music_wide_kernels.hip.h:697-703, 859).  Below it the scan recomputes the value in the
-#     reference's literal form ||G^H a||^2 (literal_tile, music_kernels.hip.h:1378-1384): its rounding is that of an fp64
-#     basis perturbed by LIT_DELTA = 4 m eps, propagated like cond_term below.
+#     (music_kernels.hip.h:1375-1379, baz_music_hip.hip: build_tables_device), kept only where d > refine_below = m 1e-8 max||a||^2
+#     (baz_music_hip.hip: build_tables_device, baz_music_debug_host_table_image; music_wide_kernels.hip.h:697-703, 859).
+#     Below it the scan recomputes the value in the reference's literal form ||G^H a||^2 (literal_tile,
+#     music_kernels.hip.h:1378-1384): its rounding is that of an fp64 basis perturbed by LIT_DELTA = 4 m eps, propagated like cond_term below.
 #   * int8 scan (6 <= m <= 16, n <= 4): the kept five-digit form is within 7.5e-7 of the projector form by construction
 #     (scan_i8_kernels.hip.h:14-51; the seven-digit refined form is of the fp64 form's class): I8_EPS on top.
 #
@@ -76,7 +76,7 @@ EPS64 = 2.0 ** -53
 RCP_ULPS = 3.0
 I8_EPS = 7.5e-7                # scan_i8_kernels.hip.h:22-27 (eps of the kept bulk form)
 EVD_C = 64.0                   # units of m 2^-53 lambda_max, see above
-REFINE_REL = 1e-8              # refine_below = m REFINE_REL max||a||^2 (baz_music_hip.hip:1696)
+REFINE_REL = 1e-8              # refine_below = m REFINE_REL max||a||^2 (baz_music_hip.hip: build_tables_device)
 TIGHT_TOL = 2e-6               # the fraction of values with tol <= this is reported (and asserted by the GPU tests)
 PATHS = ("fp64", "int8")
 

@@ -233,7 +233,7 @@ def test_stage_taps_on_every_eigensolver_branch(m, n, snr, gpu_device):
     """R (debug_cov) against fp64 numpy at 1e-14 max|R|; the projector (debug_q, the coefficients evd_finish writes:
     Q_ii, 2 Re Q_ij, -2 Im Q_ij) against the eigh-based one within the Davis-Kahan bound 2 delta + delta^2 per item
     (delta = basis_delta: the helper's cond_term before propagation).  debug_q hands the kernels a buffer that is not the
-    context's own, so the subspace iteration writes the projector I - S S^H there, not S (baz_music_hip.hip:758-760)."""
+    context's own, so the subspace iteration writes the projector I - S S^H there, not S (baz_music_hip.hip: launch_evd_t)."""
     import torch
     capi = _capi()
     B, K = 37, 48
@@ -271,7 +271,7 @@ def test_stage_taps_on_every_eigensolver_branch(m, n, snr, gpu_device):
 
 @pytest.mark.parametrize("m,n", [(17, 2), (32, 9), (64, 4)])
 def test_stage_tap_covariance_of_wide_arrays(m, n, gpu_device):
-    """The wide path forms no projector (baz_music_debug_q: E_UNSUPPORTED, baz_music_hip.hip:2724); its covariance tap at
+    """The wide path forms no projector (baz_music_debug_q in baz_music_hip.hip: E_UNSUPPORTED); its covariance tap at
     0 / 25 / 80 dB (the spectra of these branches are held to the bound by test_branch_within_its_bound)."""
     import torch
     for snr in (0.0, 25.0, 80.0):
@@ -292,7 +292,7 @@ def test_stage_tap_covariance_of_wide_arrays(m, n, gpu_device):
 
 # ---- the bound notices a lost refinement -------------------------------------------------------------------------------------
 def test_extreme_snr_without_the_literal_form_fails_the_bound(gpu_device, monkeypatch):
-    """BAZ_MUSIC_NO_REFINE=1 (lab library; arithmetic only, baz_music_hip.hip:215, 2211) keeps the projector form in the
+    """BAZ_MUSIC_NO_REFINE=1 (lab library; arithmetic only: refine_off in baz_music_hip.hip) keeps the projector form in the
     nulls: at 120 dB its ~m^2 eps ||a||^2 absolute error is far outside the bound there, which the 1e-5 budget may not see
     everywhere.  The same lab build with the refinement passes."""
     m, n, K, res = 4, 2, 64, 1440
