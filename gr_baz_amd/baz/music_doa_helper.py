@@ -145,6 +145,12 @@ def _set_order_mode(h, criterion):
     h.impl.set_order_mode(modes[criterion])
 
 
+def _set_refine_mode(h, parabolic):
+    # EXTENSION, no reference counterpart: sub-bin angles by a parabolic fit of the MUSIC denominator at each reported bin and
+    # its two neighbours, see include/baz_music_hip.h.  Stays in force across set_frequency().
+    h.impl.set_refine_mode(bool(parabolic))
+
+
 if _HAVE_GR:
 
     class music_doa_helper(gr.hier_block2):
@@ -178,6 +184,11 @@ if _HAVE_GR:
             """Opt-in (not reference behaviour): the number of emitters per item by "mdl" or "aic" (None: the fixed n)."""
             _set_order_mode(self, criterion)
 
+        def set_refine_mode(self, parabolic=True):
+            """Opt-in (not reference behaviour): angles between the grid's bins by a parabolic fit of the null (False: the
+            reference's grid angles).  Best with the wrapped block's set_peak_mode(True)."""
+            _set_refine_mode(self, parabolic)
+
 else:
 
     class music_doa_helper(object):
@@ -204,6 +215,11 @@ else:
         def set_order_mode(self, criterion):
             """Opt-in (not reference behaviour): the number of emitters per item by "mdl" or "aic" (None: the fixed n)."""
             _set_order_mode(self, criterion)
+
+        def set_refine_mode(self, parabolic=True):
+            """Opt-in (not reference behaviour): angles between the grid's bins by a parabolic fit of the null (False: the
+            reference's grid angles).  Best with the wrapped block's set_peak_mode(True)."""
+            _set_refine_mode(self, parabolic)
 
         def work(self, items):
             """Runs the wrapped block on (k, nsamples) complex64 items: returns (ang, lvl[, spectrum])."""

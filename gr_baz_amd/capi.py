@@ -38,6 +38,7 @@ SYMBOLS = [
     "baz_music_set_smoothing", "baz_music_get_smoothing", "baz_music_smoothing_check",
     "baz_music_set_order_mode", "baz_music_get_order_mode", "baz_music_last_orders", "baz_music_last_orders_device",
     "baz_music_order_estimate",
+    "baz_music_set_refine_mode", "baz_music_get_refine_mode", "baz_music_last_refine_offsets", "baz_music_refine_estimate",
 ]
 ORDER_MODES = {None: 0, "mdl": 1, "aic": 2}   # baz_music_set_order_mode: criterion by name
 SMOOTH_WORKSPACE_BYTES = 128 << 20  # BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES: re-stacked items per chunk while smoothing is on
@@ -180,6 +181,14 @@ def _bind(L):
     L.baz_music_last_orders.argtypes = [_vp, ctypes.POINTER(ctypes.c_uint8), _u32]
     L.baz_music_last_orders_device.restype = _vp
     L.baz_music_last_orders_device.argtypes = [_vp]
+    L.baz_music_set_refine_mode.restype = ctypes.c_int
+    L.baz_music_set_refine_mode.argtypes = [_vp, ctypes.c_int]
+    L.baz_music_get_refine_mode.restype = ctypes.c_int
+    L.baz_music_get_refine_mode.argtypes = [_vp, ctypes.POINTER(ctypes.c_int)]
+    L.baz_music_last_refine_offsets.restype = ctypes.c_int
+    L.baz_music_last_refine_offsets.argtypes = [_vp, ctypes.POINTER(ctypes.c_double), _u32]
+    L.baz_music_refine_estimate.restype = ctypes.c_int
+    L.baz_music_refine_estimate.argtypes = [ctypes.POINTER(ctypes.c_double), _u32, ctypes.POINTER(ctypes.c_double)]
     L.baz_music_order_estimate.restype = ctypes.c_int
     L.baz_music_order_estimate.argtypes = [_u32, _u32, _u32, ctypes.c_int, ctypes.POINTER(ctypes.c_double), _u32,
                                            ctypes.POINTER(ctypes.c_uint8)]
@@ -394,6 +403,25 @@ class Context:
         """Device address of the same bytes (0 before the first call); valid until the next process*() call."""
         return int(self._L.baz_music_last_orders_device(self._h) or 0)
 
+    def set_refine_mode(self, mode):
+        """Opt-in extension (not reference behaviour): 1 moves every reported angle off the grid by a parabolic fit of the MUSIC
+        denominator at its bin and the two neighbours (include/baz_music_hip.h); 0 (default): the reference's grid angles."""
+        self._chk(self._L.baz_music_set_refine_mode(self._h, int(mode)), "baz_music_set_refine_mode")
+
+    def get_refine_mode(self):
+        mode = ctypes.c_int(0)
+        self._chk(self._L.baz_music_get_refine_mode(self._h, ctypes.byref(mode)), "baz_music_get_refine_mode")
+        return int(mode.value)
+
+    def last_refine_offsets(self, count):
+        """Sub-bin offsets (float64, in bins) of the first `count` (item, slot) entries of the last process*() call; zeros for a
+        call made with the mode off."""
+        out = np.zeros(max(int(count), 1), np.float64)
+        r = self._L.baz_music_last_refine_offsets(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(count))
+        if r < 0:
+            self._chk(r, "baz_music_last_refine_offsets")
+        return out[:r].copy()
+
     def set_stream(self, hip_stream):
         self._chk(self._L.baz_music_set_stream(self._h, _vp(hip_stream) if hip_stream else None),
                   "baz_music_set_stream")
@@ -470,6 +498,18 @@ def order_estimate(m, nsnap, n_max, criterion, eigvals_ascending):
     if r != OK:
         raise ValueError("baz_music_order_estimate: %s" % lib().baz_music_strerror(r).decode())
     return out[:ev.shape[0]].copy()
+
+
+def refine_estimate(y3):
+    """HOST-ONLY: the sub-bin offsets the kernel's decision routine gives for rows (d(b-1), d(b), d(b+1)) (needs no device).
+    Returns a float64 array, one offset per row."""
+    y = np.ascontiguousarray(y3, dtype=np.float64).reshape(-1, 3)
+    out = np.zeros(max(y.shape[0], 1), np.float64)
+    r = lib().baz_music_refine_estimate(y.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), y.shape[0],
+                                        out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    if r != OK:
+        raise ValueError("baz_music_refine_estimate: %s" % lib().baz_music_strerror(r).decode())
+    return out[:y.shape[0]].copy()
 
 
 TABLE_IMAGES = {0: "FB", 1: "TB", 2: "coarse", 3: "i8", 4: "a2p", 5: "TA", 6: "a2", 7: "params", 8: "i8 packed (m <= 4)"}

@@ -15,6 +15,7 @@
 #endif
 #include "table_kernels.hip.h"
 #include "smoothing_kernels.hip.h"
+#include "refine_kernels.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -188,6 +189,8 @@ struct baz_music_ctx {
         double* dA2p = nullptr;          // short_form_applies(): ||a||^2 per bin, padded like dFB (fb_steps + 2 steps of 64)
         float2* dTA = nullptr;           // wide arrays: steering table transposed, [m][res] complex64
         double* dA2 = nullptr;           // wide arrays: ||a||^2 per bin
+        float2* dRW = nullptr;           // the raw table as delivered, [res][m] complex64: what refine_kernel gathers its steering rows from
+                                         // (dRaw is the upload staging buffer: the next set_table overwrites it under batches in flight)
 #ifdef BAZ_MUSIC_LAB
         uint4* dIP = nullptr;            // level-packed int8 operands (m <= 4; shares i8 / i8_ok with dIB: a configuration has one of the two)
         float* dKT = nullptr;            // float32 table at the sort key's sample bins (sort_kernels.hip.h; m <= 8)
@@ -299,6 +302,15 @@ struct baz_music_ctx {
     uint8_t* ord_cur = nullptr;     // where the EVD launched next writes its counts (null: a debug tap -> dOrdTap)
     uint8_t* dOrdTap = nullptr;     // counts of the debug taps' EVD launches (never read back)
     size_t ord_tap_cap = 0;
+    // Opt-in sub-bin angle refinement (baz_music_set_refine_mode; NOT reference behaviour; refine_kernels.hip.h).  While
+    // refine_mode is 0 its kernel is not launched and nothing below is allocated.
+    int refine_mode = 0;            // 0: ang on the grid (the reference); 1: parabolic fit of the null
+    float* dRefAl = nullptr;        // ang | lvl of the chunk in flight as the pickers leave them (refine_kernel writes the caller's)
+    size_t ref_al_cap = 0;          // floats
+    double* dRefOff = nullptr;      // delta per (item, slot) of the last process*() call, in call order (all chunks)
+    size_t ref_off_cap = 0;         // doubles
+    uint32_t ref_count = 0;         // items of the call in flight recorded so far (the next chunk's offset)
+    bool ref_on = false;            // whether the last process*() call ran with the mode on (else every offset is 0)
     size_t chunk_bytes = 0;   // host-fed path: traffic per pipelined chunk (BAZ_MUSIC_CHUNK_MIB); 0 = by buffer kind
     // host-fed path: page ranges of the caller's buffers this context has page-locked (baz_music_host_register)
     struct HostPin { uintptr_t lo, hi; uint32_t asked; };   // [lo, hi): the caller's exact bytes
@@ -738,13 +750,19 @@ int grow(baz_music_ctx* c, T*& p, size_t& cap, size_t need)
 // ---- emitter-count mode: bookkeeping --------------------------------------------------------------------------------------------
 int grow_bytes(baz_music_ctx* c, uint8_t*& p, size_t& cap, size_t need) { return grow(c, p, cap, (need + 255) / 256 * 256); }
 
-// Opens a process*() call of `items` items for baz_music_last_orders: the counts of all its chunks land in dOrd in call order.
-// With the mode off this is three stores.
+// Opens a process*() call of `items` items for baz_music_last_orders and baz_music_last_refine_offsets: the counts / offsets of all
+// its chunks land in dOrd / dRefOff in call order.  With both modes off this is five stores.
 int order_begin(baz_music_ctx* c, uint32_t items)
 {
     c->ord_count = 0;
     c->ord_items = items;
     c->ord_on = c->order_mode != 0;
+    c->ref_count = 0;
+    c->ref_on = c->refine_mode != 0;
+    if (c->ref_on) {
+        const int r = grow(c, c->dRefOff, c->ref_off_cap, (size_t)items * c->n);
+        if (r) return r;
+    }
     return c->ord_on ? grow_bytes(c, c->dOrd, c->ord_cap, items) : BAZ_MUSIC_OK;
 }
 
@@ -1666,6 +1684,7 @@ int alloc_table_set(baz_music_ctx* c, TableSet& T)
     }
     if (dev_malloc((void**)&T.dFB, pad_steps * c->fb_step_elems * sizeof(double2)) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
     if (dev_malloc((void**)&T.dTB, pad_steps * c->tb_step_elems * sizeof(double2)) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
+    if (dev_malloc((void**)&T.dRW, (size_t)c->res * c->m * sizeof(float2)) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
     if (c->m <= 8 && dev_malloc((void**)&T.dCS, coarse_image_bytes(c)) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
 #ifdef BAZ_MUSIC_LAB
     if (c->m <= 8 && c->sort_mode != 0 &&            // (lab: the sort key's table)
@@ -1690,6 +1709,7 @@ void free_table_set(TableSet& T)
     if (T.dA2p) (void)dev_free(T.dA2p);
     if (T.dTA) (void)dev_free(T.dTA);
     if (T.dA2) (void)dev_free(T.dA2);
+    if (T.dRW) (void)dev_free(T.dRW);
     T = TableSet();
 }
 
@@ -1749,6 +1769,11 @@ int build_tables_device(baz_music_ctx* c, TableSet& T)
     }
     if (T.dA2) {
         hipLaunchKernelGGL(baztab::build_a2_kernel, grid_for(res), dim3(256), 0, s, c->dRaw, m, res, res, 0u, T.dA2);
+        HIP_TRY(c, hipGetLastError());
+    }
+    if (T.dRW) {    // the set's own copy of the raw table (the refinement's steering rows)
+        hipLaunchKernelGGL(baztab::copy_words_kernel, dim3((unsigned)std::min<size_t>(512, (raw_bytes / 8 + 255) / 256)), dim3(256), 0, s,
+                           reinterpret_cast<const unsigned long long*>(c->dRaw), reinterpret_cast<unsigned long long*>(T.dRW), raw_bytes / 8);
         HIP_TRY(c, hipGetLastError());
     }
     if (T.dTA) {
@@ -2101,6 +2126,43 @@ int check_launch_pointers(baz_music_ctx* c)
     return BAZ_MUSIC_OK;
 }
 
+// Opt-in sub-bin refinement of the chunk's entries (refine_kernels.hip.h): reads the staged ang | lvl, the item's projector / noise
+// vectors of this launch sequence and the raw image of the table in force; writes the caller's ang / lvl and this chunk's offsets.
+template <int M>
+int launch_refine_t(baz_music_ctx* c, const bazrefine::RefineArgs& A)
+{
+    const uint64_t entries = (uint64_t)A.batch * A.n;
+    hipLaunchKernelGGL((bazrefine::refine_kernel<M>), dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, c->stream, A);
+    HIP_TRY(c, hipGetLastError());
+    return BAZ_MUSIC_OK;
+}
+
+int launch_refine(baz_music_ctx* c, uint32_t batch, uint32_t qstride, float* d_ang, float* d_lvl)
+{
+    ProfScope ps(c, BAZ_MUSIC_STAGE_MERGE);
+    BAZ_REQUIRE(c, dRefAl); BAZ_REQUIRE(c, dRefOff); BAZ_REQUIRE_TAB(c, dRW);
+    bazrefine::RefineArgs A;
+    const size_t entries = (size_t)batch * c->n;
+    A.ang_in = c->dRefAl;
+    A.lvl_in = c->dRefAl + entries;
+    A.ang_out = d_ang;
+    A.lvl_out = d_lvl;
+    A.off_out = c->dRefOff + (size_t)c->ref_count * c->n;
+    // (where the scan runs its short form the EVD writes no projector coefficients, launch_evd_t: the literal form throughout)
+    A.Qs = short_form_in_use(c) ? nullptr : c->dQ;
+    A.Gs = c->dG;
+    A.raw = c->tab.dRW;
+    A.below = c->refine_off ? -1.0 : c->tab.refine_below;
+    A.batch = batch; A.n = c->n; A.res = c->res; A.qstride = qstride;
+    A.rows = c->m - scan_n(c);      // the rows the scans' literal form runs over (emitter-count mode: zero-padded to a uniform count)
+#define BAZ_CALL(MV) launch_refine_t<MV>(c, A)
+    switch (c->m) {
+        BAZ_M_CASES(BAZ_CALL)
+        default: return BAZ_MUSIC_E_UNSUPPORTED;
+    }
+#undef BAZ_CALL
+}
+
 int process_device_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, void* d_ang, void* d_lvl,
                           void* d_spec)
 {
@@ -2131,22 +2193,38 @@ int process_device_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, vo
         if (r) return r;
         spec = c->dPeakSpec;
     }
-    r = launch_scan(c, c->dQ, qstride, batch, static_cast<float*>(d_ang), static_cast<float*>(d_lvl), spec);
+    // refinement: the pickers write ang | lvl (lvl always: it marks the real entries) into a staging buffer of this context and
+    // refine_kernel writes the caller's -- which may be host memory mapped over the link, never read back
+    float* ang = static_cast<float*>(d_ang);
+    float* lvl = static_cast<float*>(d_lvl);
+    const size_t entries = (size_t)batch * c->n;
+    if (c->refine_mode) {
+        if (!c->ref_on || !c->dRefOff || ((size_t)c->ref_count + batch) * c->n > c->ref_off_cap) return refuse_null(c, nullptr, "dRefOff (order_begin)");
+        r = grow(c, c->dRefAl, c->ref_al_cap, entries * 2);
+        if (r) return r;
+        ang = c->dRefAl;
+        lvl = c->dRefAl + entries;
+    }
+    r = launch_scan(c, c->dQ, qstride, batch, ang, lvl, spec);
     if (r) return r;
-    r = launch_merge(c, batch, static_cast<float*>(d_ang), static_cast<float*>(d_lvl), spec);
+    r = launch_merge(c, batch, ang, lvl, spec);
     if (r) return r;
     c->stat_next_clean = true;     // the merge cleared the next call's statistic counter
     if (c->peak_mode) {
-        r = launch_peaks(c, batch, static_cast<float*>(d_ang), static_cast<float*>(d_lvl), spec);
+        r = launch_peaks(c, batch, ang, lvl, spec);
         if (r) return r;
     }
     if (ord) {                     // (0, 0) at and beyond every item's own count: the n - k weakest entries of either picker
         ProfScope ps(c, BAZ_MUSIC_STAGE_MERGE);
-        const uint64_t entries = (uint64_t)batch * c->n;
         hipLaunchKernelGGL(bazorder::order_truncate_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, c->stream,
-                           static_cast<float*>(d_ang), static_cast<float*>(d_lvl), ord, batch, c->n);
+                           ang, lvl, ord, batch, c->n);
         HIP_TRY(c, hipGetLastError());
         c->ord_count += batch;
+    }
+    if (c->refine_mode) {
+        r = launch_refine(c, batch, qstride, static_cast<float*>(d_ang), static_cast<float*>(d_lvl));
+        if (r) return r;
+        c->ref_count += batch;
     }
     return BAZ_MUSIC_OK;
 }
@@ -2617,6 +2695,8 @@ void baz_music_destroy(baz_music_ctx* c)
 #endif
         if (c->dOrd) (void)dev_free(c->dOrd);
         if (c->dOrdTap) (void)dev_free(c->dOrdTap);
+        if (c->dRefAl) (void)dev_free(c->dRefAl);
+        if (c->dRefOff) (void)dev_free(c->dRefOff);
         if (c->dCand) (void)dev_free(c->dCand);
         if (c->dR) (void)dev_free(c->dR);
         if (c->dQ) (void)dev_free(c->dQ);
@@ -2697,6 +2777,11 @@ int baz_music_reserve(baz_music_ctx* c, uint32_t max_batch)
         const int ro = grow_bytes(oc, oc->dOrd, oc->ord_cap, max_batch);
         if (ro) return ro;
     }
+    if (c->refine_mode && !c->ord_driven) {  // refinement: one offset per entry of a whole call (kept by the context that runs the kernels)
+        baz_music_ctx* const oc = c->sm.inner ? c->sm.inner : c;
+        const int rr = grow(oc, oc->dRefOff, oc->ref_off_cap, (size_t)max_batch * oc->n);
+        if (rr) return rr;
+    }
     if (c->sm.inner) {   // smoothing on: the inner context's workspace for one chunk, and the re-stacked chunk
         const uint32_t chunk = smooth_chunk(c, max_batch);
         const int rs = grow(c, c->sm.dY, c->sm.y_cap, (size_t)chunk * c->sm.Kp * c->sm.ms);
@@ -2709,6 +2794,7 @@ int baz_music_reserve(baz_music_ctx* c, uint32_t max_batch)
         return (rw || !c->wide_mfma || c->wide_literal_only) ? rw : ensure_candidates(c, wide_cand_entries(c, pass));
     }
     int r = ensure_workspace(c, max_batch);
+    if (r == BAZ_MUSIC_OK && c->refine_mode) r = grow(c, c->dRefAl, c->ref_al_cap, (size_t)max_batch * c->n * 2);   // (the pickers' staging)
 #ifdef BAZ_MUSIC_LAB
     if (r == BAZ_MUSIC_OK && c->sort_mode != 0) r = ensure_sort_workspace(c, max_batch);
 #endif
@@ -3594,6 +3680,7 @@ int baz_music_set_smoothing(baz_music_ctx* c, uint32_t subarray, int forward_bac
         r = baz_music_set_stream(inner, c->stream);
         if (r == BAZ_MUSIC_OK) r = baz_music_set_peak_mode(inner, c->peak_mode);
         if (r == BAZ_MUSIC_OK) r = baz_music_set_order_mode(inner, c->order_mode);
+        if (r == BAZ_MUSIC_OK) r = baz_music_set_refine_mode(inner, c->refine_mode);
         if (r == BAZ_MUSIC_OK) {
             inner->order_nsnap = c->K;            // N of the criterion: this context's snapshots, not the K' re-stacked columns
             inner->ord_driven = true;
@@ -3670,6 +3757,51 @@ int baz_music_order_estimate(uint32_t m, uint32_t nsnap, uint32_t n_max, int cri
         const double* l = eigvals_ascending + (size_t)it * m;
         out[it] = (uint8_t)bazorder::order_decide<0>((int)m, (int)n_max, (double)nsnap, criterion, [&](int i) { return l[i]; });
     }
+    return BAZ_MUSIC_OK;
+}
+
+int baz_music_set_refine_mode(baz_music_ctx* c, int mode)
+{
+    if (!c || (mode != 0 && mode != 1)) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    if (mode && c->wide) return BAZ_MUSIC_E_UNSUPPORTED;   // no peak picker on the run-time-m path: only first entries would move
+    if (c->sm.inner) {   // (the inner context is never wider than this one)
+        const int r = baz_music_set_refine_mode(c->sm.inner, mode);
+        if (r != BAZ_MUSIC_OK) return r;
+    }
+    c->refine_mode = mode;
+    return BAZ_MUSIC_OK;
+}
+
+int baz_music_get_refine_mode(const baz_music_ctx* c, int* mode)
+{
+    if (!c || !mode) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(const_cast<baz_music_ctx*>(c)->mtx);
+    *mode = c->refine_mode;
+    return BAZ_MUSIC_OK;
+}
+
+int baz_music_last_refine_offsets(baz_music_ctx* c, double* out, uint32_t count)
+{
+    if (!c || (!out && count)) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    if (c->sm.inner) return baz_music_last_refine_offsets(c->sm.inner, out, count);
+    DeviceGuard guard(c->device);
+    const uint64_t total = (uint64_t)(c->ref_on ? c->ref_count : c->ord_items) * c->n;
+    const uint32_t have = (uint32_t)std::min<uint64_t>(count, total);
+    if (!c->ref_on) {                              // the call ran with the mode off: nothing moved
+        if (have) memset(out, 0, (size_t)have * sizeof(double));
+        return (int)have;
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (have) HIP_TRY(c, hipMemcpy(out, c->dRefOff, (size_t)have * sizeof(double), hipMemcpyDeviceToHost));
+    return (int)have;
+}
+
+int baz_music_refine_estimate(const double* y3, uint32_t count, double* delta_out)
+{
+    if (count && (!y3 || !delta_out)) return BAZ_MUSIC_E_INVALID;
+    for (uint32_t k = 0; k < count; ++k) delta_out[k] = bazrefine::refine_decide(y3[3 * (size_t)k], y3[3 * (size_t)k + 1], y3[3 * (size_t)k + 2]);
     return BAZ_MUSIC_OK;
 }
 

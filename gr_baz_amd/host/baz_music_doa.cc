@@ -182,6 +182,12 @@ void baz_music_doa::set_order_mode(int criterion)
     if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: set_order_mode: ") + baz_music_strerror(rc));
 }
 
+void baz_music_doa::set_refine_mode(bool parabolic)
+{
+    const int rc = baz_music_set_refine_mode(d_ctx, parabolic ? 1 : 0);
+    if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: set_refine_mode: ") + baz_music_strerror(rc));
+}
+
 std::vector<unsigned char> baz_music_doa::last_orders(unsigned int count)
 {
     std::vector<unsigned char> out(count);

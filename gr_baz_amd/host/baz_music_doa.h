@@ -69,6 +69,10 @@ public:
      * then (0, 0).  last_orders: the counts of the first `count` items of the last work() call. */
     void set_order_mode(int criterion);
     std::vector<unsigned char> last_orders(unsigned int count);
+    /* Extension, off by default (not in the reference): move every reported angle off the steering grid by a parabolic fit of
+     * the MUSIC denominator at its bin and the two neighbours (baz_music_set_refine_mode, include/baz_music_hip.h); meant to be
+     * used with set_peak_mode(true).  lvl and the spectrum port do not change. */
+    void set_refine_mode(bool parabolic);
 
     /* Page-locking of the scheduler's stream buffers (baz_music_set_host_pinning, include/baz_music_hip.h): work()
      * registers the ranges it is handed the first time it sees them, stop() and the destructor release them.  On by

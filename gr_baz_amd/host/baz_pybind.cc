@@ -242,6 +242,7 @@ PYBIND11_MODULE(_baz_music, mod)
         .def("set_smoothing", [](music_doa_handle& h, unsigned int subarray, bool fb) { h.blk->set_smoothing(subarray, fb); },
              py::arg("subarray"), py::arg("forward_backward") = false)
         .def("set_order_mode", [](music_doa_handle& h, int criterion) { h.blk->set_order_mode(criterion); }, py::arg("criterion"))
+        .def("set_refine_mode", [](music_doa_handle& h, bool on) { h.blk->set_refine_mode(on); }, py::arg("parabolic"))
         .def("last_orders",
              [](music_doa_handle& h, unsigned int count) {
                  const std::vector<unsigned char> v = h.blk->last_orders(count);

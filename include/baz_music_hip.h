@@ -248,7 +248,7 @@ BAZ_MUSIC_API int baz_music_set_peak_mode(baz_music_ctx* ctx, int mode);
  *   WHILE ON    mode changes and set_table take effect for items submitted after they return and are serialised against
  *               process*() (a batch sees the old mode / table or the new one).  set_table must pass the mode's checks, else it
  *               returns BAZ_MUSIC_E_INVALID and keeps the old table and mode.  process, process_device, process_device_on,
- *               reserve, sync, set_stream (forwarded), set_peak_mode, set_order_mode (forwarded), host_register / set_host_pinning work; every call
+ *               reserve, sync, set_stream (forwarded), set_peak_mode, set_order_mode, set_refine_mode (forwarded), host_register / set_host_pinning work; every call
  *               is cut into chunks whose re-stacked items fit BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES (at least one item per chunk), and
  *               the host path stages its chunks through device buffers: its results equal the device path's bit for bit.
  *               uses_i8_scan answers for the inner context.  profile, stage_ms, refined_values / refined_items and the debug_
@@ -304,6 +304,46 @@ BAZ_MUSIC_API int baz_music_last_orders(baz_music_ctx* ctx, uint8_t* out, uint32
 BAZ_MUSIC_API const void* baz_music_last_orders_device(baz_music_ctx* ctx);
 BAZ_MUSIC_API int baz_music_order_estimate(uint32_t m, uint32_t nsnap, uint32_t n_max, int criterion,
                                            const double* eigvals_ascending, uint32_t count, uint8_t* out);
+/* OPT-IN extension, NOT reference behaviour: sub-bin angle refinement.  The reference reports angles on the steering grid,
+ * ang = (float)(bin * 360 / resolution) (lib/baz_music_doa.cc:134,152).  Near an emitter the denominator d(theta) = ||G^H a(theta)||^2 is a
+ * smooth null, d_min + c (theta - theta_0)^2 to leading order, so a parabola through d at the reported bin and its two neighbours locates
+ * theta_0 far inside a bin (the fit is on d: the spectrum 1 / d is a Lorentzian there and fits a parabola badly).  mode: 0 = the
+ * reference (the default), 1 = the parabolic null fit; anything else BAZ_MUSIC_E_INVALID.
+ *   DEFINITION  for every reported entry (item, slot) with bin b, whichever picker produced it (the reference's top-n, peak mode 1,
+ *               the emitter-count mode's truncation): y-, y0, y+ = the fp64 values of d at bins b - 1, b, b + 1 on the circle (the wrap of
+ *               peak mode),
+ *                 p = y- - y0,  q = y+ - y0
+ *                 delta = (p - q) / (2 (p + q))    if p >= 0, q >= 0, p + q > 0 and all three values are finite
+ *                 delta = 0                        otherwise (b on a flank, a plateau, next to a NaN / Inf)
+ *               so |delta| <= 1/2, and  ang = (float)(((b + delta) mod resolution) * 360 / resolution)  evaluated in fp64 (b + delta < 0
+ *               only at b = 0: one turn is added); a result that rounds to 360.0f is stored as 0.0f.  An entry with delta == 0 keeps
+ *               exactly the ang bits of mode 0.  lvl and the spectrum port do not change by a single bit (lvl[i] == spectrum[b] still
+ *               holds).  Missing entries -- missing peaks of peak mode 1, slots at or beyond an item's count in the emitter-count mode,
+ *               the (0, 0) of .cc:95 -- stay (0, 0) whether or not lvl is wired.  tests/refine_ref.py restates this in numpy.
+ *   THE VALUES  each of the three is formed the way the exact fp64 scan forms a value: the projector form a^H Q a in fp64, and the
+ *               reference's literal form ||G^H a||^2 from the item's noise vectors where the projector form is at or below the table's
+ *               threshold (~m 1e-8 max ||a||^2, see baz_music_refined_values).  Contexts whose scan runs the short form (one emitter from
+ *               6 antennas, two from 9) keep no projector coefficients: there all three take the literal form.  In the emitter-count
+ *               mode Q and G are the item's own variable-rank ones.  The int8 and f16 coarse forms are never used for these values.
+ *   WHAT RUNS   one kernel (gr_baz_amd/csrc/refine_kernels.hip.h) after the merge / the picker / the truncation, one thread per entry;
+ *               while the mode is on the pickers write into a staging buffer of the context and that kernel writes the caller's ang /
+ *               lvl.  Steering rows come from an image that belongs to the table set in force: a batch sees the old table or the new
+ *               one, for ang too.  Mode 0 launches exactly the kernels it launched before the mode existed and is the reference bit for
+ *               bit: a context never set, one set to 0, one switched on and off again.
+ *   SCOPE       up to BAZ_MUSIC_FAST_M antennas (BAZ_MUSIC_E_UNSUPPORTED beyond), like peak mode.  Meant to be used with peak mode 1:
+ *               under the reference's top-n the entries after the first usually sit on a flank of the first one's null and stay put.
+ *               Composes with the emitter-count mode and with smoothing (forwarded to the inner context).
+ *   WHEN        set_refine_mode takes effect for items submitted after it returns and is serialised against process*() like
+ *               set_peak_mode: a batch sees the old mode or the new one.  The previous mode stays in force after any error.
+ * last_refine_offsets: delta of the entries of the LAST process*() call in call order ([item][slot]), at most `count` of them (a host-fed
+ * call cut into chunks, or a smoothing call, reports all its items); blocks until that call is done; returns how many were written, or
+ * < 0.  A call that ran with the mode off reports zeros.  (The float ang hides everything below ~2e-5 degrees; this tap does not.)  The
+ * buffer behind it (8 n bytes per item) is allocated only by calls made with the mode on.  refine_estimate needs no device: the same decision routine the
+ * kernel calls, on `count` triples (y-, y0, y+) at y3[3k .. 3k+2]; BAZ_MUSIC_E_INVALID for a NULL array with count > 0. */
+BAZ_MUSIC_API int baz_music_set_refine_mode(baz_music_ctx* ctx, int mode);
+BAZ_MUSIC_API int baz_music_get_refine_mode(const baz_music_ctx* ctx, int* mode);
+BAZ_MUSIC_API int baz_music_last_refine_offsets(baz_music_ctx* ctx, double* out, uint32_t count);
+BAZ_MUSIC_API int baz_music_refine_estimate(const double* y3, uint32_t count, double* delta_out);
 /* Statistic: how many (item, bin) values of the LAST process call were recomputed in the reference's literal form
  * ||G^H a||^2 because the projector form a^H Q a put them at or below ~m 1e-8 max||a||^2 (near-nulls of the noise
  * subspace, SNR >~ 55 dB); blocks until that call is done (a host-fed call cut into chunks reports their sum).
