@@ -244,7 +244,6 @@ struct baz_music_ctx {
     uint32_t cov4_resident_blocks = 256u;        // grid of cov4_x4_kernel (persistent waves): one workgroup per CU
     // coarse-gated scan (scan_coarse_kernels.hip.h): m <= 8, spectrum port not wired
     uint32_t cs_tiles = 0;         // tiles in the image (a multiple of 8)
-    uint32_t last_nsplit = 1;      // bin ranges per item the last scan launch produced candidates for (the merge folds them)
     int coarse = 1;                // BAZ_MUSIC_COARSE=0: the full fp64 scan also without the spectrum port (A/B, tests)
     int coarse_rg = 4;             // BAZ_MUSIC_COARSE_RG: row groups (x 16 items) per wave, 2 or 4 (lab)
     int coarse_lab = 0;            // BAZ_MUSIC_COARSE_LAB=1: never run an exact tile (cost of the coarse passes alone; wrong results)
@@ -269,7 +268,6 @@ struct baz_music_ctx {
     uint64_t sort_clock = 0, sort_retry_at = 0;
     double rate_unsorted = 0.0;
     uint64_t sorted_calls = 0, unsorted_calls = 0;     // (tap: baz_music_debug_sort_state)
-    bool last_gated_sorted = false;
 #endif
     uint32_t scan_lds_pad = 0;     // lab (BAZ_MUSIC_SCAN_LDS_PAD bytes): dynamic LDS the fp64 scan asks for and never touches -- caps its workgroups per CU
                                    // (tests/lab/two_ctx_split.py: does a low-register covariance of ANOTHER context fit beside three of them?)
@@ -324,7 +322,7 @@ struct baz_music_ctx {
     StageProf prof[BAZ_MUSIC_NUM_STAGES];
     std::string stage_name[BAZ_MUSIC_NUM_STAGES];
     char scan_names[4][64] = {{0}, {0}, {0}, {0}};   // baz_music_stage_name(SCAN) by scan_kind, written once by baz_music_create
-    int scan_kind = -1;     // the scan kernel the LAST launch took: 0 scan_mfma_kernel, 1 scan_i8_kernel, 2 scan_coarse_kernel, 3 scan_i8p_kernel (-1: none yet)
+    int scan_kind = -1;     // the scan kernel the LAST launch took (ScanKind; -1: none yet): only baz_music_stage_name reads it
     char hip_err[256] = {0};
     // Opt-in forward-backward averaging / spatial smoothing (baz_music_set_smoothing; NOT reference behaviour).  While `inner` is
     // set, every process* call re-stacks its items (smoothing_kernels.hip.h) into `dY` and runs them through `inner`, a context of
@@ -647,6 +645,7 @@ bool build_i8p_image(const std::vector<double>& F, uint32_t m, uint32_t res, uin
 // the scan's short form (scan_mfma_kernel, SIG) needs fewer MFMAs than the projector GEMM
 bool short_form_applies(uint32_t m, uint32_t n) { return (n == 2 && m >= 9 && m <= 16) || (n == 1 && m >= 6 && m <= 16); }
 // The int8-matrix-core scan applies: 6 .. 16 antennas (row classes below, run-time-m kernels above), lists of <= 4 keys.
+// (launch_scan_i8 / _i8p / _coarse hold `if constexpr` bounds equal to what i8_active / i8p_active / coarse_applies admit: widen both or get E_UNSUPPORTED)
 bool i8_active(const baz_music_ctx* c)
 {
     return c->i8_on && c->tab.i8_ok && c->tab.dIB && c->m >= 6 && c->m <= 16 && c->n <= 4 && !c->lab_variant;
@@ -926,35 +925,50 @@ int launch_frontend(baz_music_ctx* c, const void* d_in, uint32_t batch, double* 
     return r ? r : launch_evd(c, c->dR, batch, dQ, qstride, c->dG);
 }
 
-// Launch geometry of the scan: rows are taken class by class (class k = items nclass*j + k, see the kernel's ROW
-// CLASSES note), every class padded to a multiple of 64 rows (one block = 4 waves x 16 rows of ONE class), times
-// `nsplit` ranges of 64-bin steps, chosen so that a launch has >= ~8 waves/SIMD worth of wave tasks even for small
-// batches / long tables (config 3: 4,096 items x 36,000 bins).  Every range of every item yields NMAX candidate keys
-// for topn_merge_kernel.
-struct ScanGeom {
-    uint32_t groups, nsplit, blocks, rows_per_class;
-};
+// ---- launch geometry of the scan kernels, and beside each the candidate keys it can ask for -----------------------------------------
+// Every bin range of every item yields topn_list_len(n) candidate keys for topn_merge_kernel.  nb * nsplit(nb) is not monotonic in nb
+// (nsplit = ceil(wanted / groups) while that stays under the kernel's cap), so a reservation for `batch` items is sized for the worst
+// launch of ANY nb <= batch (*_cand_ranges): a smaller batch or the short tail chunk of baz_music_process never re-allocates mid-pipeline.
+uint32_t topn_list_len(uint32_t n) { return n <= 2 ? 2u : (n <= 4 ? 4u : (n <= 8 ? 8u : 16u)); }
+// tests / lab (BAZ_MUSIC_NSPLIT=k > 0): k bin ranges per item, as far as the kernel has that many
+uint32_t forced_nsplit(int force_nsplit, uint32_t most) { return std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)force_nsplit, most)); }
 
+// The fp64 scan (and the level-packed int8 scan of lab builds): rows are taken class by class (class k = items nclass*j + k, see the
+// kernel's ROW CLASSES note), every class padded to a multiple of 64 rows (one block = 4 waves x 16 rows of ONE class), times
+// `nsplit` ranges of 64-bin steps, chosen so that a launch has >= ~8 waves/SIMD worth of wave tasks even for small
+// batches / long tables (config 3: 4,096 items x 36,000 bins).
+struct ScanGeom { uint32_t groups, nsplit, blocks, rows_per_class; };
+// Wave tasks wanted = 2 x the waves the chip holds at once (256 CUs x 4 SIMDs x 4): enough to balance the tail,
+// and no more -- every extra range restarts the top-n lists (the gate fires until they fill), writes another
+// candidate list per item and multiplies the row streams written at once: 262,144 cfg2 items ran the scan in 0.716 /
+// 0.758 / 0.826 ms at 1 / 2 / 4 ranges (round 1 asked for 8 waves/SIMD worth = 32,768 tasks, i.e. 2 ranges there).
+// From 9 antennas on the kernel holds 2 waves per SIMD (256 registers) and a task costs more to set up (the short form's
+// 32 coefficient registers): ONE round of the 2,048 wave slots is best there -- 16 antennas, 3,600 bins: 16,384 items ran
+// the scan in 0.358 / 0.278 / 0.294 / 0.321 ms at 1 / 2 / 4 / 8 ranges, 4,096 items in 0.093 / 0.088 / 0.095 / 0.107 ms at
+// 4 / 8 / 16 / 32 (profiles/r03_bin_ranges_by_shape.txt; 5..8 antennas do not care between 2 and 8).
+constexpr uint32_t SCAN_WANT_TASKS = 256u * 4u * 4u * 2u;      // up to 8 antennas; a quarter of it from 9 on
+constexpr uint32_t SCAN_MAX_NSPLIT = 64;
 ScanGeom scan_geometry(uint32_t batch, uint32_t nsteps, uint32_t nclass, int force_nsplit, uint32_t m)
 {
     ScanGeom G;
     G.rows_per_class = round_up((batch + nclass - 1) / nclass, 64);
     G.groups = nclass * (G.rows_per_class / 16);
     const uint32_t live_groups = (batch + 15) / 16;
-    // Wave tasks wanted = 2 x the waves the chip holds at once (256 CUs x 4 SIMDs x 4): enough to balance the tail,
-    // and no more -- every extra range restarts the top-n lists (the gate fires until they fill), writes another
-    // candidate list per item and multiplies the row streams written at once: 262,144 cfg2 items ran the scan in 0.716 /
-    // 0.758 / 0.826 ms at 1 / 2 / 4 ranges (round 1 asked for 8 waves/SIMD worth = 32,768 tasks, i.e. 2 ranges there).
-    // From 9 antennas on the kernel holds 2 waves per SIMD (256 registers) and a task costs more to set up (the short form's
-    // 32 coefficient registers): ONE round of the 2,048 wave slots is best there -- 16 antennas, 3,600 bins: 16,384 items ran
-    // the scan in 0.358 / 0.278 / 0.294 / 0.321 ms at 1 / 2 / 4 / 8 ranges, 4,096 items in 0.093 / 0.088 / 0.095 / 0.107 ms at
-    // 4 / 8 / 16 / 32 (profiles/r03_bin_ranges_by_shape.txt; 5..8 antennas do not care between 2 and 8).
-    const uint32_t want_tasks = (m >= 9) ? 256u * 4u * 2u : 256u * 4u * 4u * 2u;
-    uint32_t ns = (want_tasks + live_groups - 1) / live_groups;
-    G.nsplit = std::max<uint32_t>(1u, std::min<uint32_t>(ns, std::min<uint32_t>(nsteps, 64u)));
-    if (force_nsplit > 0) G.nsplit = std::min<uint32_t>((uint32_t)force_nsplit, std::min<uint32_t>(nsteps, 64u));   // tests / lab
+    const uint32_t want_tasks = (m >= 9) ? SCAN_WANT_TASKS / 4u : SCAN_WANT_TASKS;
+    const uint32_t ns = (want_tasks + live_groups - 1) / live_groups;
+    G.nsplit = std::max<uint32_t>(1u, std::min<uint32_t>(ns, std::min<uint32_t>(nsteps, SCAN_MAX_NSPLIT)));
+    if (force_nsplit > 0) G.nsplit = forced_nsplit(force_nsplit, std::min<uint32_t>(nsteps, SCAN_MAX_NSPLIT));
     G.blocks = (G.groups / 4) * G.nsplit;
     return G;
+}
+// nb * nsplit(nb) < nb * (want_tasks / ceil(nb/16) + 1) <= 16 * want_tasks + nb, and <= nb * min(64, nsteps)
+size_t scan_cand_ranges(const baz_music_ctx* c, uint32_t batch)
+{
+    const size_t cap_split = std::min<size_t>(SCAN_MAX_NSPLIT, std::max<uint32_t>(1u, c->fb_steps));
+    const size_t exact = (size_t)batch * scan_geometry(batch, c->fb_steps, c->nclass, c->force_nsplit, c->m).nsplit;
+    const size_t worst = std::min<size_t>((size_t)batch * cap_split, (size_t)16u * SCAN_WANT_TASKS + (size_t)batch);
+    const size_t forced = c->force_nsplit > 0 ? (size_t)batch * forced_nsplit(c->force_nsplit, (uint32_t)cap_split) : 0;
+    return std::max(std::max(exact, worst), std::max(forced, (size_t)batch));
 }
 
 // Bin ranges per item of scan_i8_kernel: its workgroups (4 waves x 16 items, one range of 64-bin steps) should fill the
@@ -962,15 +976,15 @@ ScanGeom scan_geometry(uint32_t batch, uint32_t nsteps, uint32_t nclass, int for
 // are 256 groups; 8 ranges made 2,048 workgroups for 768 slots, 2.67 rounds of which the last ran a third empty, where 3 ranges
 // fill every slot exactly once (and restart the top-n lists 3 times instead of 8).  Up to 8 rounds are tried; the fewest
 // rounds within 3 % of the best filling win.  Ranges of fewer than 4 steps are not made.
-constexpr uint32_t I8_MAX_NSPLIT = 16;
+constexpr uint32_t I8_MAX_NSPLIT = 16, I8_MAX_ROUNDS = 8;
 uint32_t i8_nsplit(uint32_t batch, uint32_t nsteps, uint32_t slots, int force_nsplit)
 {
     const uint32_t groups = std::max<uint32_t>(1u, (batch + 63) / 64);
     const uint32_t cap = std::max<uint32_t>(1u, std::min<uint32_t>(I8_MAX_NSPLIT, nsteps / 4));
-    if (force_nsplit > 0) return std::max<uint32_t>(1u, std::min<uint32_t>((uint32_t)force_nsplit, std::min<uint32_t>(nsteps, 64u)));
+    if (force_nsplit > 0) return forced_nsplit(force_nsplit, std::min<uint32_t>(nsteps, SCAN_MAX_NSPLIT));
     uint32_t best = 1;
     double best_fill = 0.0;
-    for (uint32_t r = 1; r <= 8; ++r) {
+    for (uint32_t r = 1; r <= I8_MAX_ROUNDS; ++r) {
         const uint32_t ns = std::max<uint32_t>(1u, std::min<uint32_t>(cap, (uint32_t)(((uint64_t)r * slots) / groups)));
         const uint64_t blocks = (uint64_t)groups * ns;
         const uint64_t rounds = (blocks + slots - 1) / slots;
@@ -979,6 +993,13 @@ uint32_t i8_nsplit(uint32_t batch, uint32_t nsteps, uint32_t slots, int force_ns
         if (ns == cap) break;
     }
     return best;
+}
+// nsplit <= r slots / ceil(nb / 64) with r <= I8_MAX_ROUNDS rounds of <= 4 x 256-CU slots, and <= I8_MAX_NSPLIT
+size_t i8_cand_ranges(const baz_music_ctx* c, uint32_t batch)
+{
+    if (!c->tab.dIB) return 0;
+    const size_t exact = (size_t)batch * (c->force_nsplit > 0 ? forced_nsplit(c->force_nsplit, SCAN_MAX_NSPLIT) : I8_MAX_NSPLIT);
+    return std::max(exact, std::min<size_t>((size_t)batch * I8_MAX_NSPLIT, (size_t)64u * I8_MAX_ROUNDS * 4u * c->num_cus + (size_t)batch));
 }
 
 int ensure_candidates(baz_music_ctx* c, size_t entries) { return grow(c, c->dCand, c->cand_cap, entries); }
@@ -992,12 +1013,9 @@ bool coarse_applies(const baz_music_ctx* c)
 }
 
 constexpr int coarse_rg_wide(int m, int nmax) { return (cs_groups(m) == 4 && nmax > 2) ? 1 : 2; }   // (what the register file holds without spilling)
-
 // its launch geometry: a workgroup = 4 waves x RG x 16 items; ranges of table phases so that small batches still fill the chip
-constexpr uint32_t COARSE_WANT_BLOCKS = 1024;
-struct CoarseGeom {
-    uint32_t groups, nsplit, nphases, tpp;
-};
+constexpr uint32_t COARSE_WANT_BLOCKS = 1024, COARSE_MAX_NSPLIT = 16;
+struct CoarseGeom { uint32_t groups, nsplit, nphases, tpp; };
 CoarseGeom coarse_geometry(const baz_music_ctx* c, uint32_t batch)
 {
     CoarseGeom G;
@@ -1009,9 +1027,23 @@ CoarseGeom coarse_geometry(const baz_music_ctx* c, uint32_t batch)
     G.nphases = c->cs_tiles / G.tpp;
     G.groups = (batch + 64 * rg - 1) / (64 * rg);
     const uint32_t ns = (COARSE_WANT_BLOCKS + G.groups - 1) / G.groups;
-    G.nsplit = std::max(1u, std::min(ns, std::min(G.nphases, 16u)));
-    if (c->force_nsplit > 0) G.nsplit = std::max(1u, std::min((uint32_t)c->force_nsplit, std::min(G.nphases, 16u)));
+    G.nsplit = std::max(1u, std::min(ns, std::min(G.nphases, COARSE_MAX_NSPLIT)));
+    if (c->force_nsplit > 0) G.nsplit = forced_nsplit(c->force_nsplit, std::min(G.nphases, COARSE_MAX_NSPLIT));
     return G;
+}
+// nsplit = ceil(COARSE_WANT_BLOCKS / ceil(nb / (64 rg))) <= 16, rg <= 4 row groups per wave  ->  nb * nsplit <= 256 * WANT + nb
+size_t coarse_cand_ranges(const baz_music_ctx* c, uint32_t batch)
+{
+    if (c->m > 8) return 0;
+    const size_t exact = c->tab.dCS ? (size_t)batch * coarse_geometry(c, batch).nsplit : 0;
+    return std::max(exact, std::min<size_t>((size_t)batch * COARSE_MAX_NSPLIT, (size_t)256u * COARSE_WANT_BLOCKS + (size_t)batch));
+}
+
+// the candidate buffer for launches of up to `batch` items: the largest of the kernels this context can take with either port wiring
+int reserve_candidates(baz_music_ctx* c, uint32_t batch)
+{
+    const size_t ranges = std::max(scan_cand_ranges(c, batch), std::max(coarse_cand_ranges(c, batch), i8_cand_ranges(c, batch)));
+    return ensure_candidates(c, ranges * topn_list_len(c->n));
 }
 
 // ---- sorting in front of the gated scan (sort_kernels.hip.h): LAB builds only --------------------------------------------------------
@@ -1117,341 +1149,324 @@ ScanRefine scan_refine(const baz_music_ctx* c, bool a2)
     return rf;
 }
 // ... and of the debug taps' validation launches: nothing refined, nothing counted
-ScanRefine scan_refine_validation(const baz_music_ctx* c)
+ScanRefine scan_refine_validation(const baz_music_ctx* c) { return {nullptr, c->tab.dTB + c->tb_step_elems, 0.0, nullptr, nullptr}; }
+
+// ---- the scan: which kernel a launch takes (scan_form), one launcher per kernel ------------------------------------------------------
+enum ScanKind { SCAN_FP64 = 0, SCAN_I8 = 1, SCAN_COARSE = 2, SCAN_I8P = 3 };   // the order of baz_music_ctx::scan_names
+struct ScanForm { ScanKind kind; bool short_form; };   // short_form (SCAN_FP64): ||a||^2 - sum_c |s_c^H a|^2 on c->dSs, not the projector form on c->dQ
+
+// The scan kernel of a launch, from the context and the port wiring alone (`spec`: the launch writes a spectrum -- the caller's, or the
+// private one of peak mode).  In priority order (DESIGN.md 5.0 has the table):
+//   1. no spectrum: the coarse-gated scan where it applies.  (Not in emitter-count mode: the gate reads n both as list length and as the
+//      literal form's row count, and its list-length bound is what prunes tiles; the full scans' n is the row count alone.)
+//   2. lab builds, 2 .. 4 antennas with a spectrum: the level-packed int8 scan.
+//   3. 6 .. 16 antennas: the int8 scan -- except a shape of the gated scan without a spectrum whose gate does not apply (BAZ_MUSIC_COARSE=0,
+//      emitter-count mode, an unrepresentable table scale): COARSE=0 is the gate's A/B and must stay bit-identical to it, so the fp64 scan.
+//   4. the fp64 scan: its short form where that needs fewer MFMAs (n = 2 from 9 antennas, n = 1 from 6), else the projector form.
+ScanForm scan_form(const baz_music_ctx* c, bool spec)
 {
+    if (!spec && coarse_applies(c) && !c->order_mode) return {SCAN_COARSE, false};
+    if (spec && i8p_active(c)) return {SCAN_I8P, false};
+    const bool gated_shape = c->m <= 8 && !short_form_applies(c->m, c->n);
+    if (i8_active(c) && (spec || !gated_shape)) return {SCAN_I8, false};
+    return {SCAN_FP64, short_form_in_use(c)};
+}
+
+// One scan launch over the workspace: c->dQ (c->dSs: the short form) -> candidates in c->dCand; spec: where a spectrum is written (vec4: 16-byte stores)
+struct ScanCall { uint32_t batch, qstride; float* spec; bool vec4; };
+
+// What a scan launch did, for the merge that folds its candidate lists (nsplit: bin ranges per item)
+struct ScanDone {
+    int rc;
+    ScanKind kind;
+    uint32_t nsplit;
+#ifdef BAZ_MUSIC_LAB
+    bool sorted = false;    // (BAZ_MUSIC_SORT) the gated scan walked the items through its index list
+#endif
+};
+// a launcher's last word: the outcome, and for baz_music_stage_name the kernel this context last LAUNCHED (a refused launch leaves it)
+ScanDone scan_result(baz_music_ctx* c, ScanDone done, int rc) { done.rc = rc; if (rc == BAZ_MUSIC_OK) c->scan_kind = done.kind; return done; }
+int launch_rc(baz_music_ctx* c) { HIP_TRY(c, hipGetLastError()); return BAZ_MUSIC_OK; }
+ScanDone scan_no_kernel(ScanKind kind) { return {BAZ_MUSIC_E_UNSUPPORTED, kind, 1}; }   // (a launcher outside its kernel's bounds: scan_form sends no shape there)
+// The argument lists, each written once: the product launches below and the validation taps (baz_music_debug_coarse_margin,
+// baz_music_debug_i8_margin) differ in the instantiation, the grid and what the structs here hold.
+struct CoarseLaunch {
+    uint32_t blocks, nphases, nsplit;
     ScanRefine rf;
-    rf.Gs = nullptr;
-    rf.TB = c->tab.dTB + c->tb_step_elems;
-    rf.below = 0.0;
-    rf.count = nullptr;
-    rf.A2 = nullptr;
-    return rf;
+    unsigned long long* stats;                 // lab: exact tile evaluations, summed over launches; VAL: the margin
+    float* val_dump = nullptr;
+    const uint32_t* perm = nullptr;            // the product walks the items in their own order and keeps no fire statistic
+    unsigned long long* fstat = nullptr;
+};
+template <int M, typename Kernel>
+void coarse_launch(baz_music_ctx* c, Kernel kernel, const CoarseLaunch& L, uint32_t batch, uint32_t qstride)
+{
+    hipLaunchKernelGGL(kernel, dim3(L.blocks), dim3(256), 0, c->stream, c->dQ, c->tab.dCS, c->tab.dCS + (size_t)(c->cs_tiles + 1) * cs_c_units(M),
+                       c->dCand, batch, c->res, qstride, L.nphases, L.nsplit, c->keep_mask, c->n, L.rf, c->tab.cs, L.stats, L.val_dump, L.perm, L.fstat);
+}
+
+struct I8Launch {                              // scan_i8_kernel and, in lab builds, scan_i8p_kernel
+    uint32_t blocks, nsplit, n;
+    float* spec;
+    ScanRefine rf;
+    unsigned long long *stat, *margin;         // margin: VAL
+};
+template <typename Kernel>
+void i8_launch(baz_music_ctx* c, Kernel kernel, const I8Launch& L, uint32_t batch, uint32_t qstride)
+{
+    hipLaunchKernelGGL(kernel, dim3(L.blocks), dim3(256), 0, c->stream, c->dQ, c->tab.dIB, c->tab.dIB + i8_image_bytes5(c->m, c->fb_steps) / 16,
+                       c->tab.dFB + c->fb_step_elems, L.spec, c->dCand, batch, c->res, qstride, L.nsplit, c->keep_mask, L.n, L.rf, c->tab.i8, L.stat, L.margin);
 }
 
 template <int M, int NMAX>
-int launch_scan_t(baz_music_ctx* c, const double* dQ, uint32_t qstride, uint32_t batch, float* d_ang,
-                  float* d_lvl, float* d_spec)
+ScanDone launch_scan_coarse(baz_music_ctx* c, const ScanCall& s)
 {
     if constexpr (M <= 8 && NMAX <= 4) {
-        // (emitter-count mode: the gate reads n both as list length and as the literal form's row count, and its list-length bound
-        // is what prunes tiles -- such contexts take the full scans below, whose n is the row count alone)
-        if (!d_spec && coarse_applies(c) && dQ == c->dQ && !c->order_mode) {
-            const CoarseGeom CG = coarse_geometry(c, batch);
-            if ((size_t)batch * CG.nsplit * NMAX > c->cand_cap) return BAZ_MUSIC_E_INVALID;
-            const ScanRefine rf = scan_refine(c, false);
-            unsigned long long* stats = c->coarse_stats ? c->dMargin : nullptr;     // lab: exact tile evaluations, summed over launches
+        const CoarseGeom CG = coarse_geometry(c, s.batch);
+        ScanDone done{BAZ_MUSIC_OK, SCAN_COARSE, CG.nsplit};
+        if ((size_t)s.batch * CG.nsplit * NMAX > c->cand_cap) return scan_result(c, done, BAZ_MUSIC_E_INVALID);   // reserve_candidates() sized it
+        CoarseLaunch L{CG.groups * CG.nsplit, CG.nphases, CG.nsplit, scan_refine(c, false), c->coarse_stats ? c->dMargin : nullptr};
+        auto* kernel = &scan_coarse_kernel<M, NMAX, (M > 4 ? coarse_rg_wide(M, NMAX) : 4), (M > 4 ? 4 : 8)>;
+        if constexpr (M <= 4) if (CG.tpp == 4) kernel = &scan_coarse_kernel<M, NMAX, 2, 4>;
 #ifdef BAZ_MUSIC_LAB
-            // lab (BAZ_MUSIC_SORT): the items in an order in which neighbours share their nulls, while the scan's own statistic says that pays
-            int sr = ensure_sort_workspace(c, batch);
-            if (sr) return sr;
-            const bool sorted = sort_decide(c, batch);
-            if (sorted) {
-                sr = launch_sort_t<M>(c, dQ, qstride, batch);
-                if (sr) return sr;
-                ++c->sorted_calls;
-            } else {
-                ++c->unsorted_calls;
+        // lab (BAZ_MUSIC_SORT): the items in an order in which neighbours share their nulls, while the scan's own statistic says that pays
+        int sr = ensure_sort_workspace(c, s.batch);
+        done.sorted = !sr && sort_decide(c, s.batch);
+        if (done.sorted) sr = launch_sort_t<M>(c, c->dQ, s.qstride, s.batch);
+        if (sr) return scan_result(c, done, sr);
+        if (done.sorted) ++c->sorted_calls;
+        else ++c->unsorted_calls;
+        L.perm = done.sorted ? c->dPerm : nullptr;
+        L.fstat = c->dFire;
+        if constexpr (M <= 4) {
+            if (CG.tpp != 4) {                 // (two row groups per wave have the product's kernel alone)
+                if (c->sort_mode != 0 && !c->coarse_lab) kernel = &scan_coarse_kernel<M, NMAX, 4, 8, false, 0, true>;   // the index list and the fire statistic
+                else if (c->coarse_lab == 1) kernel = &scan_coarse_kernel<M, NMAX, 4, 8, false, 1>;
+                else if (c->coarse_lab == 2) kernel = &scan_coarse_kernel<M, NMAX, 4, 8, false, 2>;
             }
-            c->last_gated_sorted = sorted;
-            const uint32_t* perm = sorted ? c->dPerm : nullptr;
-            unsigned long long* fstat = c->dFire;
-#else
-            const uint32_t* perm = nullptr;                 // the product walks the items in their own order and keeps no fire statistic
-            unsigned long long* fstat = nullptr;
-#endif
-#define BAZ_COARSE_ARGS dim3(CG.groups * CG.nsplit), dim3(256), 0, c->stream, dQ, c->tab.dCS, c->tab.dCS + (size_t)(c->cs_tiles + 1) * cs_c_units(M), \
-                        c->dCand, batch, c->res, qstride, CG.nphases, CG.nsplit, c->keep_mask, c->n, rf, c->tab.cs, stats, nullptr, perm, fstat
-#ifdef BAZ_MUSIC_LAB
-            if (c->sort_mode != 0 && M <= 4 && CG.tpp != 4 && !c->coarse_lab) {        // lab (BAZ_MUSIC_SORT): the index list and the fire statistic
-                if constexpr (M <= 4) hipLaunchKernelGGL((scan_coarse_kernel<M, NMAX, 4, 8, false, 0, true>), BAZ_COARSE_ARGS);
-            } else
-#endif
-            if constexpr (M > 4) hipLaunchKernelGGL((scan_coarse_kernel<M, NMAX, coarse_rg_wide(M, NMAX), 4>), BAZ_COARSE_ARGS);
-            else if (CG.tpp == 4) hipLaunchKernelGGL((scan_coarse_kernel<M, NMAX, 2, 4>), BAZ_COARSE_ARGS);
-#ifdef BAZ_MUSIC_LAB
-            else if (c->coarse_lab == 1) hipLaunchKernelGGL((scan_coarse_kernel<M, NMAX, 4, 8, false, 1>), BAZ_COARSE_ARGS);
-            else if (c->coarse_lab == 2) hipLaunchKernelGGL((scan_coarse_kernel<M, NMAX, 4, 8, false, 2>), BAZ_COARSE_ARGS);
-#endif
-            else hipLaunchKernelGGL((scan_coarse_kernel<M, NMAX, 4, 8>), BAZ_COARSE_ARGS);
-#undef BAZ_COARSE_ARGS
-            HIP_TRY(c, hipGetLastError());
-            c->last_nsplit = CG.nsplit;
-            c->scan_kind = 2;
-            return BAZ_MUSIC_OK;
         }
-    }
-    ScanGeom G = scan_geometry(batch, c->fb_steps, c->nclass, c->force_nsplit, c->m);
-    c->last_nsplit = G.nsplit;
-    double* cand = c->dCand;
-    if ((size_t)batch * G.nsplit * NMAX > c->cand_cap) return BAZ_MUSIC_E_INVALID;   // reserve_candidates() sized it
-    const bool spec = d_spec != nullptr;
-    const bool vec4 = (c->res % 4u) == 0 && (reinterpret_cast<uintptr_t>(d_spec) % 16u) == 0;
-#ifdef BAZ_MUSIC_LAB
-    if constexpr (M <= 4 && NMAX <= 4) {
-        // LAB (BAZ_MUSIC_I8P=1): 2 .. 4 antennas with the spectrum port: the int8 matrix core with level-packed operands (scan_i8p_kernels.hip.h); same
-        // geometry (row classes, bin ranges) and candidate lists as the fp64 scan below.  Without the port the coarse-gated scan above.
-        if (spec && i8p_active(c) && dQ == c->dQ) {
-            const ScanRefine rf = scan_refine(c, false);
-            const uint4* p1 = c->tab.dIP + I8P_STEP_UNITS;                            // step 0 (a padded step lies in front)
-            const uint4* p2 = p1 + i8p_operand_units(c->fb_steps);
-#define BAZ_I8P_ARGS dim3(G.blocks), dim3(256), 0, c->stream, dQ, p1, p2, c->tab.dFB + c->fb_step_elems, d_spec, cand, batch, c->res, qstride, \
-                     G.nsplit, c->nclass, G.rows_per_class, c->keep_mask, c->n, rf, c->tab.i8, c->dI8Stat, nullptr
-#ifdef BAZ_MUSIC_LAB
-            if constexpr (M == 4 && NMAX == 2) {       // lab: timing ablations (wrong results)
-                if (vec4 && c->i8_abl) {
-                    if (c->i8_abl == 1) hipLaunchKernelGGL((scan_i8p_kernel<M, NMAX, true, true, false, 1>), BAZ_I8P_ARGS);
-                    else if (c->i8_abl == 2) hipLaunchKernelGGL((scan_i8p_kernel<M, NMAX, true, true, false, 2>), BAZ_I8P_ARGS);
-                    else if (c->i8_abl == 4) hipLaunchKernelGGL((scan_i8p_kernel<M, NMAX, true, true, false, 4>), BAZ_I8P_ARGS);
-                    else if (c->i8_abl == 5) hipLaunchKernelGGL((scan_i8p_kernel<M, NMAX, true, true, false, 5>), BAZ_I8P_ARGS);
-                    else hipLaunchKernelGGL((scan_i8p_kernel<M, NMAX, true, true, false, 3>), BAZ_I8P_ARGS);
-                    HIP_TRY(c, hipGetLastError());
-                    c->scan_kind = 3;
-                    return BAZ_MUSIC_OK;
-                }
-            }
 #endif
-            if (vec4) hipLaunchKernelGGL((scan_i8p_kernel<M, NMAX, true, true>), BAZ_I8P_ARGS);
-            else hipLaunchKernelGGL((scan_i8p_kernel<M, NMAX, true, false>), BAZ_I8P_ARGS);
-#undef BAZ_I8P_ARGS
-            HIP_TRY(c, hipGetLastError());
-            c->scan_kind = 3;
-            return BAZ_MUSIC_OK;
-        }
+        coarse_launch<M>(c, kernel, L, s.batch, s.qstride);
+        return scan_result(c, done, launch_rc(c));
     }
-#endif
-    if constexpr (M >= 6 && NMAX <= 4) {
-        // the bulk of the values on the int8 matrix core, exactly accumulated; steps with a value under the accuracy
-        // threshold in this kernel's own fp64 form (scan_i8_kernels.hip.h).  Same launch geometry (nclass = 1 from m = 6 on).
-        // (5 .. 8 antennas without the spectrum port belong to the coarse-gated scan above; BAZ_MUSIC_COARSE=0 is its A/B and
-        // must stay bit-identical to it: the fp64 scan below.  One emitter from 6 antennas on has no gated scan: here.)
-        const bool gated_shape = M <= 8 && NMAX <= 4 && !short_form_applies(c->m, c->n);
-        if (i8_active(c) && dQ == c->dQ && (spec || !gated_shape)) {
-            const ScanRefine rf = scan_refine(c, false);
-            // its own bin ranges: whole rounds of the resident workgroup slots (i8_nsplit)
-            int& per_cu = c->i8_wgs_per_cu[NMAX > 2 ? 1 : 0][spec ? 1 : 0][vec4 ? 1 : 0];
-            if (per_cu == 0) {
-                int occ = 0;
-                hipError_t oe;
-                if (spec && vec4) oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, scan_i8_kernel<M, NMAX, true, true>, 256, 0);
-                else if (spec) oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, scan_i8_kernel<M, NMAX, true, false>, 256, 0);
-                else oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, scan_i8_kernel<M, NMAX, false, false>, 256, 0);
-                per_cu = (oe == hipSuccess && occ > 0) ? occ : 2;
-                (void)hipGetLastError();
-            }
-            G.nsplit = i8_nsplit(batch, c->fb_steps, c->num_cus * (uint32_t)per_cu, c->force_nsplit);
-            G.blocks = (G.groups / 4) * G.nsplit;
-            c->last_nsplit = G.nsplit;
-            if ((size_t)batch * G.nsplit * NMAX > c->cand_cap) return BAZ_MUSIC_E_INVALID;
-#define BAZ_I8_LAUNCH(SPEC, VEC4)                                                                                       \
-    hipLaunchKernelGGL((scan_i8_kernel<M, NMAX, SPEC, VEC4>), dim3(G.blocks), dim3(256), 0, c->stream, dQ, c->tab.dIB,      \
-                       c->tab.dIB + i8_image_bytes5(c->m, c->fb_steps) / 16, c->tab.dFB + c->fb_step_elems, d_spec, cand, batch, c->res, qstride, G.nsplit, c->keep_mask, scan_n(c), rf, \
-                       c->tab.i8, c->dI8Stat, nullptr)
-#ifdef BAZ_MUSIC_LAB
-            if constexpr ((M == 8 || M == 16) && NMAX == 2) {        // lab: ablations of the bulk loop (timing only, wrong results)
-                if (spec && vec4 && c->i8_abl) {
-#define BAZ_I8_ABL(ABLV)                                                                                                  \
-    hipLaunchKernelGGL((scan_i8_kernel<M, NMAX, true, true, false, ABLV>), dim3(G.blocks), dim3(256), 0, c->stream, dQ, c->tab.dIB, \
-                       c->tab.dIB + i8_image_bytes5(c->m, c->fb_steps) / 16, c->tab.dFB + c->fb_step_elems, d_spec, cand, batch, c->res, \
-                       qstride, G.nsplit, c->keep_mask, c->n, rf, c->tab.i8, c->dI8Stat, nullptr)
-                    switch (c->i8_abl) {
-                        case 1: BAZ_I8_ABL(1); break;      // no spectrum stores
-                        case 4: BAZ_I8_ABL(4); break;      // no MFMAs
-                        case 5: BAZ_I8_ABL(5); break;
-                        case 33: BAZ_I8_ABL(33); break;    // staging and barriers alone
-                        case 256: BAZ_I8_ABL(256); break;  // the steps left to right (round 4's walk): A/B of the strided walk
-                        case 257: BAZ_I8_ABL(257); break;  // ... without the stores
-                        case 9: BAZ_I8_ABL(9); break;      // first phase staged only, no stores: the tiles' arithmetic alone
-                        default: BAZ_I8_ABL(32); break;    // staging, barriers and stores alone
-                    }
-#undef BAZ_I8_ABL
-                    HIP_TRY(c, hipGetLastError());
-                    return BAZ_MUSIC_OK;
-                }
-            }
-#endif
-            if (spec && vec4) BAZ_I8_LAUNCH(true, true);
-            else if (spec) BAZ_I8_LAUNCH(true, false);
-            else BAZ_I8_LAUNCH(false, false);
-#undef BAZ_I8_LAUNCH
-            HIP_TRY(c, hipGetLastError());
-            c->scan_kind = 1;
-            return BAZ_MUSIC_OK;
-        }
-    }
-    c->scan_kind = 0;
-    const ScanRefine rf = scan_refine(c, true);
-    const double2* fb0 = c->tab.dFB + c->fb_step_elems;   // step 0 (a padded step lies in front)
-    if constexpr (M >= 6 && NMAX == 2) {
-        // one or two emitters: the short form ||a||^2 - sum_c |s_c^H a|^2 (scan_mfma_kernel, SIG) where it needs fewer
-        // MFMAs than the projector GEMM: n = 2 from 9 antennas, n = 1 from 6
-        if (short_form_in_use(c) && dQ == c->dQ) {
-            const double2* tb0 = c->tab.dTB + c->tb_step_elems;
-#define BAZ_SIG_LAUNCH(SPEC, VEC4, SIGV)                                                                                    \
-    hipLaunchKernelGGL((scan_mfma_kernel<M, NMAX, SPEC, VEC4, 0, (1 | 2 | 16), SIGV>), dim3(G.blocks), dim3(256), 0, c->stream, \
-                       c->dSs, tb0, d_spec, cand, batch, c->res, qstride, G.nsplit, c->nclass, G.rows_per_class, c->keep_mask, scan_n(c), rf, (uint32_t)c->seq_walk)
-            if (c->n == 2) {
-                if constexpr (M >= 9) {
-                    if (spec && vec4) BAZ_SIG_LAUNCH(true, true, 2);
-                    else if (spec) BAZ_SIG_LAUNCH(true, false, 2);
-                    else BAZ_SIG_LAUNCH(false, false, 2);
-                }
-            } else {
-                if (spec && vec4) BAZ_SIG_LAUNCH(true, true, 1);
-                else if (spec) BAZ_SIG_LAUNCH(true, false, 1);
-                else BAZ_SIG_LAUNCH(false, false, 1);
-            }
-#undef BAZ_SIG_LAUNCH
-            HIP_TRY(c, hipGetLastError());
-            return BAZ_MUSIC_OK;
-        }
-    }
-#define BAZ_SCAN_ARGS dQ, fb0, d_spec, cand, batch, c->res, qstride, G.nsplit, c->nclass, G.rows_per_class, c->keep_mask, scan_n(c), rf, (uint32_t)c->seq_walk
-#define BAZ_SCAN_LAUNCH(SPEC, VEC4, ABLV, AUXV)                                                                    \
-    hipLaunchKernelGGL((scan_mfma_kernel<M, NMAX, SPEC, VEC4, ABLV, AUXV>), dim3(G.blocks), dim3(256), (size_t)c->scan_lds_pad, c->stream, \
-                       BAZ_SCAN_ARGS)
-#ifdef BAZ_MUSIC_LAB
-    if constexpr (M == 4 && NMAX == 2) {   // lab switches for the A/Bs in profiles/HISTORY_r01_r02.md 5.3 (BAZ_MUSIC_SCAN_VARIANT)
-        if (spec && vec4 && c->lab_variant) {
-            switch (c->lab_variant) {
-                case 2: BAZ_SCAN_LAUNCH(true, true, 64, (1 | 2 | 16)); break;   // ungated top-n network (round 1)
-                case 3: BAZ_SCAN_LAUNCH(true, true, 0, 0); break;               // plain cached spectrum stores
-                case 4: BAZ_SCAN_LAUNCH(true, true, 0, 2); break;               // nt
-                case 5: BAZ_SCAN_LAUNCH(true, true, 0, (1 | 16)); break;        // sc0 sc1
-                // (6-8: timing only, wrong results -- tests/lab/scan_ablate.py, profiles/r03_scan_ablation_real_inputs.txt)
-                case 6: BAZ_SCAN_LAUNCH(true, true, 1, (1 | 2 | 16)); break;              // everything but the spectrum stores
-                case 7: BAZ_SCAN_LAUNCH(true, true, (8 | 2 | 4), (1 | 2 | 16)); break;    // stores + staging + barriers only
-                case 8: BAZ_SCAN_LAUNCH(true, true, (1 | 2), (1 | 2 | 16)); break;        // MFMA + conversions, no top-n, no stores
-                // (9 - 11, round 5: A/B of the rotating LDS-DMA loader; results are right)
-                case 9: BAZ_SCAN_LAUNCH(true, true, 1024, (1 | 2 | 16)); break;           // rotating loader (negative: profiles/r05_loader_ab.txt)
-                case 10: BAZ_SCAN_LAUNCH(true, true, (1024 | 2048), (1 | 2 | 16)); break;  // rotating loader at 3 waves per SIMD (168 registers: no spills)
-                case 11: BAZ_SCAN_LAUNCH(true, true, 2048, (1 | 2 | 16)); break;          // register staging (the product's) at 3 waves per SIMD
-                case 12: BAZ_SCAN_LAUNCH(true, true, 4096, (1 | 2 | 16)); break;          // blocks in the compact order (negative: profiles/r05_write_order.txt)
-                case 13: BAZ_SCAN_LAUNCH(true, true, (8 | 2 | 4 | 4096), (1 | 2 | 16)); break;   // stores + staging + barriers only, compact order
-                case 14: BAZ_SCAN_LAUNCH(true, true, 8192, (1 | 2 | 16)); break;          // (round 6) s_setprio 3 around the MFMAs of a step
-                case 15: BAZ_SCAN_LAUNCH(true, true, 16384, (1 | 2 | 16)); break;         // ... s_setprio 3 around epilogue, staging and stores instead
-                default: BAZ_SCAN_LAUNCH(true, true, 0, (1 | 2 | 16)); break;
-            }
-            HIP_TRY(c, hipGetLastError());
-            return BAZ_MUSIC_OK;
-        }
-    }
-#endif
-    if (spec && vec4) BAZ_SCAN_LAUNCH(true, true, 0, (1 | 2 | 16));
-    else if (spec) BAZ_SCAN_LAUNCH(true, false, 0, (1 | 2 | 16));
-    else BAZ_SCAN_LAUNCH(false, false, 0, (1 | 2 | 16));
-#undef BAZ_SCAN_LAUNCH
-#undef BAZ_SCAN_ARGS
-    HIP_TRY(c, hipGetLastError());
-    return BAZ_MUSIC_OK;
+    return scan_no_kernel(SCAN_COARSE);
 }
 
-template <int NMAX>
-int launch_merge_t(baz_music_ctx* c, uint32_t batch, float* d_ang, float* d_lvl, float* d_spec)
+// The bulk of the values on the int8 matrix core, exactly accumulated; steps with a value under the accuracy threshold in this
+// kernel's own fp64 form (scan_i8_kernels.hip.h).  Its own bin ranges: whole rounds of the resident workgroup slots (i8_nsplit).
+template <int M, int NMAX>
+ScanDone launch_scan_i8(baz_music_ctx* c, const ScanCall& s)
 {
+    if constexpr (M >= 6 && NMAX <= 4) {
+        auto* kernel = &scan_i8_kernel<M, NMAX, false, false>;
+        if (s.vec4) kernel = &scan_i8_kernel<M, NMAX, true, true>;
+        else if (s.spec) kernel = &scan_i8_kernel<M, NMAX, true, false>;
+        int& per_cu = c->i8_wgs_per_cu[NMAX > 2 ? 1 : 0][s.spec ? 1 : 0][s.vec4 ? 1 : 0];
+        if (per_cu == 0) {
+            int occ = 0;
+            const hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, 256, 0);
+            per_cu = (oe == hipSuccess && occ > 0) ? occ : 2;
+            (void)hipGetLastError();
+        }
+        const uint32_t nsplit = i8_nsplit(s.batch, c->fb_steps, c->num_cus * (uint32_t)per_cu, c->force_nsplit);
+        ScanDone done{BAZ_MUSIC_OK, SCAN_I8, nsplit};
+        if ((size_t)s.batch * nsplit * NMAX > c->cand_cap) return scan_result(c, done, BAZ_MUSIC_E_INVALID);
+        const ScanGeom G = scan_geometry(s.batch, c->fb_steps, c->nclass, c->force_nsplit, c->m);     // (its groups: nclass = 1 from m = 6 on)
+        I8Launch L{(G.groups / 4) * nsplit, nsplit, scan_n(c), s.spec, scan_refine(c, false), c->dI8Stat, nullptr};
 #ifdef BAZ_MUSIC_LAB
-    // lab (BAZ_MUSIC_SORT): the gated scan just ran with its fire statistic on -- it travels to page-locked memory with this merge
-    const bool gated = c->scan_kind == 2 && c->sort_mode != 0 && c->dFire && c->hFireDev;
-    const unsigned long long tag = gated ? ((++c->fire_calls) << 1) | (c->last_gated_sorted ? 1ull : 0ull) : 0ull;
-    hipLaunchKernelGGL((topn_merge_kernel<NMAX>), dim3((batch + 255) / 256), dim3(256), 0, c->stream, c->dCand,
-                       d_spec, d_ang, d_lvl, batch, c->res, c->n, c->last_nsplit, c->keep_mask, c->dRefined + (c->stat_parity ^ 1),
-                       gated ? c->dFire : nullptr, gated ? c->hFireDev : nullptr, tag);
-#else
-    hipLaunchKernelGGL((topn_merge_kernel<NMAX>), dim3((batch + 255) / 256), dim3(256), 0, c->stream, c->dCand,
-                       d_spec, d_ang, d_lvl, batch, c->res, c->n, c->last_nsplit, c->keep_mask, c->dRefined + (c->stat_parity ^ 1),
-                       nullptr, nullptr, 0ull);
+        if constexpr ((M == 8 || M == 16) && NMAX == 2) {        // lab (BAZ_MUSIC_I8_ABL): ablations of the bulk loop (timing only, wrong results)
+            if (s.vec4 && c->i8_abl) {
+                L.n = c->n;
+                switch (c->i8_abl) {
+                    case 1: kernel = &scan_i8_kernel<M, NMAX, true, true, false, 1>; break;      // no spectrum stores
+                    case 4: kernel = &scan_i8_kernel<M, NMAX, true, true, false, 4>; break;      // no MFMAs
+                    case 5: kernel = &scan_i8_kernel<M, NMAX, true, true, false, 5>; break;
+                    case 33: kernel = &scan_i8_kernel<M, NMAX, true, true, false, 33>; break;    // staging and barriers alone
+                    case 256: kernel = &scan_i8_kernel<M, NMAX, true, true, false, 256>; break;  // the steps left to right (round 4's walk): A/B of the strided walk
+                    case 257: kernel = &scan_i8_kernel<M, NMAX, true, true, false, 257>; break;  // ... without the stores
+                    case 9: kernel = &scan_i8_kernel<M, NMAX, true, true, false, 9>; break;      // first phase staged only, no stores: the tiles' arithmetic alone
+                    default: kernel = &scan_i8_kernel<M, NMAX, true, true, false, 32>; break;    // staging, barriers and stores alone
+                }
+            }
+        }
 #endif
-    HIP_TRY(c, hipGetLastError());
-    return BAZ_MUSIC_OK;
+        i8_launch(c, kernel, L, s.batch, s.qstride);
+        return scan_result(c, done, launch_rc(c));
+    }
+    return scan_no_kernel(SCAN_I8);
+}
+
+#ifdef BAZ_MUSIC_LAB
+// LAB (BAZ_MUSIC_I8P=1): 2 .. 4 antennas with the spectrum port: the int8 matrix core with level-packed operands
+// (scan_i8p_kernels.hip.h); the geometry (row classes, bin ranges) and candidate lists of the fp64 scan.
+template <typename Kernel>
+void i8p_launch(baz_music_ctx* c, Kernel kernel, const I8Launch& L, uint32_t rows_per_class, uint32_t batch, uint32_t qstride)
+{
+    const uint4* p1 = c->tab.dIP + I8P_STEP_UNITS;                            // step 0 (a padded step lies in front)
+    const uint4* p2 = p1 + i8p_operand_units(c->fb_steps);
+    hipLaunchKernelGGL(kernel, dim3(L.blocks), dim3(256), 0, c->stream, c->dQ, p1, p2, c->tab.dFB + c->fb_step_elems, L.spec, c->dCand, batch, c->res,
+                       qstride, L.nsplit, c->nclass, rows_per_class, c->keep_mask, L.n, L.rf, c->tab.i8, L.stat, L.margin);
+}
+
+template <int M, int NMAX>
+ScanDone launch_scan_i8p(baz_music_ctx* c, const ScanCall& s)
+{
+    if constexpr (M <= 4 && NMAX <= 4) {
+        const ScanGeom G = scan_geometry(s.batch, c->fb_steps, c->nclass, c->force_nsplit, c->m);
+        ScanDone done{BAZ_MUSIC_OK, SCAN_I8P, G.nsplit};
+        if ((size_t)s.batch * G.nsplit * NMAX > c->cand_cap) return scan_result(c, done, BAZ_MUSIC_E_INVALID);
+        const I8Launch L{G.blocks, G.nsplit, c->n, s.spec, scan_refine(c, false), c->dI8Stat, nullptr};
+        auto* kernel = s.vec4 ? &scan_i8p_kernel<M, NMAX, true, true> : &scan_i8p_kernel<M, NMAX, true, false>;
+        if constexpr (M == 4 && NMAX == 2) {       // lab (BAZ_MUSIC_I8_ABL): timing ablations (wrong results)
+            if (s.vec4 && c->i8_abl) {
+                switch (c->i8_abl) {
+                    case 1: kernel = &scan_i8p_kernel<M, NMAX, true, true, false, 1>; break;
+                    case 2: kernel = &scan_i8p_kernel<M, NMAX, true, true, false, 2>; break;
+                    case 4: kernel = &scan_i8p_kernel<M, NMAX, true, true, false, 4>; break;
+                    case 5: kernel = &scan_i8p_kernel<M, NMAX, true, true, false, 5>; break;
+                    default: kernel = &scan_i8p_kernel<M, NMAX, true, true, false, 3>; break;
+                }
+            }
+        }
+        i8p_launch(c, kernel, L, G.rows_per_class, s.batch, s.qstride);
+        return scan_result(c, done, launch_rc(c));
+    }
+    return scan_no_kernel(SCAN_I8P);
+}
+#else
+template <int M, int NMAX>
+ScanDone launch_scan_i8p(baz_music_ctx*, const ScanCall&) { return scan_no_kernel(SCAN_I8P); }
+#endif
+
+// scan_mfma_kernel<M, NMAX, SPEC, VEC4, ABL, AUX, SIG> by what the launch writes
+template <int M, int NMAX, int SIG>
+auto* scan_fp64_kernel(const ScanCall& s)
+{
+    if (s.vec4) return &scan_mfma_kernel<M, NMAX, true, true, 0, (1 | 2 | 16), SIG>;
+    if (s.spec) return &scan_mfma_kernel<M, NMAX, true, false, 0, (1 | 2 | 16), SIG>;
+    return &scan_mfma_kernel<M, NMAX, false, false, 0, (1 | 2 | 16), SIG>;
+}
+
+// The fp64 matrix core throughout.  One or two emitters: the short form ||a||^2 - sum_c |s_c^H a|^2 (SIG) where it needs fewer
+// MFMAs than the projector GEMM: n = 2 from 9 antennas, n = 1 from 6.
+template <int M, int NMAX>
+ScanDone launch_scan_fp64(baz_music_ctx* c, const ScanCall& s, bool short_form)
+{
+    const ScanGeom G = scan_geometry(s.batch, c->fb_steps, c->nclass, c->force_nsplit, c->m);
+    ScanDone done{BAZ_MUSIC_OK, SCAN_FP64, G.nsplit};
+    if ((size_t)s.batch * G.nsplit * NMAX > c->cand_cap) return scan_result(c, done, BAZ_MUSIC_E_INVALID);   // reserve_candidates() sized it
+    auto* kernel = scan_fp64_kernel<M, NMAX, 0>(s);
+    if constexpr (M >= 6 && NMAX == 2) {
+        if (short_form && c->n == 1) kernel = scan_fp64_kernel<M, NMAX, 1>(s);
+        if constexpr (M >= 9) if (short_form && c->n == 2) kernel = scan_fp64_kernel<M, NMAX, 2>(s);
+    }
+#ifdef BAZ_MUSIC_LAB
+    if constexpr (M == 4 && NMAX == 2) {   // lab switches for the A/Bs in profiles/HISTORY_r01_r02.md 5.3 (BAZ_MUSIC_SCAN_VARIANT)
+        if (s.vec4 && c->lab_variant) {
+            switch (c->lab_variant) {
+                case 2: kernel = &scan_mfma_kernel<M, NMAX, true, true, 64, (1 | 2 | 16)>; break;   // ungated top-n network (round 1)
+                case 3: kernel = &scan_mfma_kernel<M, NMAX, true, true, 0, 0>; break;               // plain cached spectrum stores
+                case 4: kernel = &scan_mfma_kernel<M, NMAX, true, true, 0, 2>; break;               // nt
+                case 5: kernel = &scan_mfma_kernel<M, NMAX, true, true, 0, (1 | 16)>; break;        // sc0 sc1
+                // (6-8: timing only, wrong results -- tests/lab/scan_ablate.py, profiles/r03_scan_ablation_real_inputs.txt)
+                case 6: kernel = &scan_mfma_kernel<M, NMAX, true, true, 1, (1 | 2 | 16)>; break;              // everything but the spectrum stores
+                case 7: kernel = &scan_mfma_kernel<M, NMAX, true, true, (8 | 2 | 4), (1 | 2 | 16)>; break;    // stores + staging + barriers only
+                case 8: kernel = &scan_mfma_kernel<M, NMAX, true, true, (1 | 2), (1 | 2 | 16)>; break;        // MFMA + conversions, no top-n, no stores
+                // (9 - 11, round 5: A/B of the rotating LDS-DMA loader; results are right)
+                case 9: kernel = &scan_mfma_kernel<M, NMAX, true, true, 1024, (1 | 2 | 16)>; break;           // rotating loader (negative: profiles/r05_loader_ab.txt)
+                case 10: kernel = &scan_mfma_kernel<M, NMAX, true, true, (1024 | 2048), (1 | 2 | 16)>; break;  // rotating loader at 3 waves per SIMD (168 registers: no spills)
+                case 11: kernel = &scan_mfma_kernel<M, NMAX, true, true, 2048, (1 | 2 | 16)>; break;          // register staging (the product's) at 3 waves per SIMD
+                case 12: kernel = &scan_mfma_kernel<M, NMAX, true, true, 4096, (1 | 2 | 16)>; break;          // blocks in the compact order (negative: profiles/r05_write_order.txt)
+                case 13: kernel = &scan_mfma_kernel<M, NMAX, true, true, (8 | 2 | 4 | 4096), (1 | 2 | 16)>; break;   // stores + staging + barriers only, compact order
+                case 14: kernel = &scan_mfma_kernel<M, NMAX, true, true, 8192, (1 | 2 | 16)>; break;          // (round 6) s_setprio 3 around the MFMAs of a step
+                case 15: kernel = &scan_mfma_kernel<M, NMAX, true, true, 16384, (1 | 2 | 16)>; break;         // ... s_setprio 3 around epilogue, staging and stores instead
+                default: break;
+            }
+        }
+    }
+#endif
+    // short form: coefficient vectors x raw table image; projector form: projector x product image, and the lab's LDS padding (step 0 of either image)
+    const double* coeff = short_form ? c->dSs : c->dQ;
+    const double2* image = short_form ? c->tab.dTB + c->tb_step_elems : c->tab.dFB + c->fb_step_elems;
+    hipLaunchKernelGGL(kernel, dim3(G.blocks), dim3(256), short_form ? 0 : (size_t)c->scan_lds_pad, c->stream, coeff, image, s.spec, c->dCand, s.batch,
+                       c->res, s.qstride, G.nsplit, c->nclass, G.rows_per_class, c->keep_mask, scan_n(c), scan_refine(c, true), (uint32_t)c->seq_walk);
+    return scan_result(c, done, launch_rc(c));
+}
+
+template <int M, int NMAX>
+ScanDone launch_scan_t(baz_music_ctx* c, ScanForm form, const ScanCall& s)
+{
+    switch (form.kind) {
+        case SCAN_COARSE: return launch_scan_coarse<M, NMAX>(c, s);
+        case SCAN_I8P: return launch_scan_i8p<M, NMAX>(c, s);
+        case SCAN_I8: return launch_scan_i8<M, NMAX>(c, s);
+        default: return launch_scan_fp64<M, NMAX>(c, s, form.short_form);
+    }
 }
 
 template <int M>
-int launch_scan_m(baz_music_ctx* c, const double* dQ, uint32_t qstride, uint32_t batch, float* d_ang,
-                  float* d_lvl, float* d_spec)
+ScanDone launch_scan_m(baz_music_ctx* c, ScanForm form, const ScanCall& s)
 {
-    if (c->n <= 2) return launch_scan_t<M, 2>(c, dQ, qstride, batch, d_ang, d_lvl, d_spec);
-    if (c->n <= 4) return launch_scan_t<M, 4>(c, dQ, qstride, batch, d_ang, d_lvl, d_spec);
+    if (c->n <= 2) return launch_scan_t<M, 2>(c, form, s);
+    if (c->n <= 4) return launch_scan_t<M, 4>(c, form, s);
     if constexpr (M > 5) {
-        if (c->n <= 8) return launch_scan_t<M, 8>(c, dQ, qstride, batch, d_ang, d_lvl, d_spec);
+        if (c->n <= 8) return launch_scan_t<M, 8>(c, form, s);
     }
-    if constexpr (M > 9) return launch_scan_t<M, 16>(c, dQ, qstride, batch, d_ang, d_lvl, d_spec);
-    return BAZ_MUSIC_E_UNSUPPORTED;   // unreachable: n < m
+    if constexpr (M > 9) return launch_scan_t<M, 16>(c, form, s);
+    return scan_no_kernel(form.kind);   // unreachable: n < m
 }
 
-uint32_t topn_list_len(uint32_t n) { return n <= 2 ? 2u : (n <= 4 ? 4u : (n <= 8 ? 8u : 16u)); }
-
-// candidate keys one scan launch over `nb` items produces (mirrors launch_scan_t's geometry)
-size_t cand_entries(const baz_music_ctx* c, uint32_t nb)
+// The scan of `batch` items of the workspace
+ScanDone launch_scan(baz_music_ctx* c, uint32_t qstride, uint32_t batch, float* d_spec)
 {
-    size_t per_item = scan_geometry(nb, c->fb_steps, c->nclass, c->force_nsplit, c->m).nsplit;
-    if (c->m <= 8 && c->tab.dCS) per_item = std::max<size_t>(per_item, coarse_geometry(c, nb).nsplit);
-    if (c->tab.dIB) per_item = std::max<size_t>(per_item, c->force_nsplit > 0 ? (size_t)std::min<uint32_t>((uint32_t)c->force_nsplit, 64u) : I8_MAX_NSPLIT);
-    return (size_t)nb * per_item * topn_list_len(c->n);
+    ProfScope ps(c, BAZ_MUSIC_STAGE_SCAN);
+    const ScanForm form = scan_form(c, d_spec != nullptr);
+    const ScanCall s{batch, qstride, d_spec, d_spec && (c->res % 4u) == 0 && (reinterpret_cast<uintptr_t>(d_spec) % 16u) == 0};
+#define BAZ_CALL(MV) launch_scan_m<MV>(c, form, s)
+    switch (c->m) {
+        BAZ_M_CASES(BAZ_CALL)
+        default: return scan_no_kernel(form.kind);
+    }
+#undef BAZ_CALL
 }
 
-// nb * nsplit(nb) is not monotonic in nb (nsplit = ceil(want_tasks / groups) while that is <= 64 and <= nsteps), so
-// a reservation for `batch` items is sized for the worst launch of ANY nb <= batch: nb * nsplit(nb) < nb *
-// (want_tasks / ceil(nb/16) + 1) <= 16 * want_tasks + nb, and <= nb * min(64, nsteps).  A smaller batch or the short
-// tail chunk of baz_music_process then never re-allocates in the middle of the pipeline.
-size_t cand_entries_upto(const baz_music_ctx* c, uint32_t batch)
-{
-    const size_t want_tasks = 256u * 4u * 4u * 2u;   // scan_geometry()
-    const size_t cap_split = std::min<size_t>(64u, std::max<uint32_t>(1u, c->fb_steps));
-    const size_t worst = std::min<size_t>((size_t)batch * cap_split, 16u * want_tasks + (size_t)batch);
-    const size_t forced = c->force_nsplit > 0 ? (size_t)batch * std::min<size_t>((size_t)c->force_nsplit, cap_split) : 0;
-    // the coarse-gated scan: nsplit = ceil(COARSE_WANT_BLOCKS / ceil(nb / (64 rg))) <= 16, rg <= 4 row groups per wave
-    // ->  nb * nsplit <= 256 * WANT + nb
-    const size_t coarse = (c->m <= 8) ? std::min<size_t>((size_t)batch * 16u, 256u * COARSE_WANT_BLOCKS + (size_t)batch) : 0;
-    // the int8 scan: nsplit <= r slots / ceil(nb / 64) with r <= 8 rounds of <= 4 x 256-CU slots, and <= I8_MAX_NSPLIT
-    const size_t i8 = c->tab.dIB ? std::min<size_t>((size_t)batch * I8_MAX_NSPLIT, (size_t)64u * 8u * 4u * c->num_cus + (size_t)batch) : 0;
-    return std::max(std::max(std::max(std::max(worst, forced), coarse), i8), (size_t)batch) * topn_list_len(c->n);
-}
-
-int reserve_candidates(baz_music_ctx* c, uint32_t batch)
-{
-    return ensure_candidates(c, std::max(cand_entries(c, batch), cand_entries_upto(c, batch)));
-}
-
-int launch_merge(baz_music_ctx* c, uint32_t batch, float* d_ang, float* d_lvl, float* d_spec)
+// topn_merge_kernel folds the scan's candidate lists of every item into its n entries
+int launch_merge(baz_music_ctx* c, const ScanDone& scan, uint32_t batch, float* d_ang, float* d_lvl, float* d_spec)
 {
     ProfScope ps(c, BAZ_MUSIC_STAGE_MERGE);
+    auto* kernel = &topn_merge_kernel<16>;
     switch (topn_list_len(c->n)) {
-        case 2: return launch_merge_t<2>(c, batch, d_ang, d_lvl, d_spec);
-        case 4: return launch_merge_t<4>(c, batch, d_ang, d_lvl, d_spec);
-        case 8: return launch_merge_t<8>(c, batch, d_ang, d_lvl, d_spec);
-        default: return launch_merge_t<16>(c, batch, d_ang, d_lvl, d_spec);
+        case 2: kernel = &topn_merge_kernel<2>; break;
+        case 4: kernel = &topn_merge_kernel<4>; break;
+        case 8: kernel = &topn_merge_kernel<8>; break;
+        default: break;
     }
-}
-
-template <int NMAX>
-int launch_peaks_t(baz_music_ctx* c, uint32_t batch, float* d_ang, float* d_lvl, const float* d_spec)
-{
-    hipLaunchKernelGGL((peak_pick_kernel<NMAX>), dim3((batch + 3) / 4), dim3(256), 0, c->stream, d_spec, d_ang, d_lvl,
-                       batch, c->res, c->n);
-    HIP_TRY(c, hipGetLastError());
-    return BAZ_MUSIC_OK;
+    unsigned long long *fire_dev = nullptr, *fire_host = nullptr, fire_tag = 0ull;
+#ifdef BAZ_MUSIC_LAB
+    // lab (BAZ_MUSIC_SORT): the gated scan just ran with its fire statistic on -- it travels to page-locked memory with this merge
+    if (scan.kind == SCAN_COARSE && c->sort_mode != 0 && c->dFire && c->hFireDev) {
+        fire_dev = c->dFire;
+        fire_host = c->hFireDev;
+        fire_tag = ((++c->fire_calls) << 1) | (scan.sorted ? 1ull : 0ull);
+    }
+#endif
+    hipLaunchKernelGGL(kernel, dim3((batch + 255) / 256), dim3(256), 0, c->stream, c->dCand, d_spec, d_ang, d_lvl, batch, c->res, c->n,
+                       scan.nsplit, c->keep_mask, c->dRefined + (c->stat_parity ^ 1), fire_dev, fire_host, fire_tag);
+    return launch_rc(c);
 }
 
 int launch_peaks(baz_music_ctx* c, uint32_t batch, float* d_ang, float* d_lvl, const float* d_spec)
 {
     ProfScope ps(c, BAZ_MUSIC_STAGE_MERGE);
+    auto* kernel = &peak_pick_kernel<16>;
     switch (topn_list_len(c->n)) {
-        case 2: return launch_peaks_t<2>(c, batch, d_ang, d_lvl, d_spec);
-        case 4: return launch_peaks_t<4>(c, batch, d_ang, d_lvl, d_spec);
-        case 8: return launch_peaks_t<8>(c, batch, d_ang, d_lvl, d_spec);
-        default: return launch_peaks_t<16>(c, batch, d_ang, d_lvl, d_spec);
+        case 2: kernel = &peak_pick_kernel<2>; break;
+        case 4: kernel = &peak_pick_kernel<4>; break;
+        case 8: kernel = &peak_pick_kernel<8>; break;
+        default: break;
     }
-}
-
-int launch_scan(baz_music_ctx* c, const double* dQ, uint32_t qstride, uint32_t batch, float* d_ang,
-                float* d_lvl, float* d_spec)
-{
-    ProfScope ps(c, BAZ_MUSIC_STAGE_SCAN);
-#define BAZ_CALL(MV) launch_scan_m<MV>(c, dQ, qstride, batch, d_ang, d_lvl, d_spec)
-    switch (c->m) {
-        BAZ_M_CASES(BAZ_CALL)
-        default: return BAZ_MUSIC_E_UNSUPPORTED;
-    }
-#undef BAZ_CALL
+    hipLaunchKernelGGL(kernel, dim3((batch + 3) / 4), dim3(256), 0, c->stream, d_spec, d_ang, d_lvl, batch, c->res, c->n);
+    return launch_rc(c);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1482,7 +1497,7 @@ WideScanGeom wide_scan_geometry(const baz_music_ctx* c, uint32_t nb)
     W.nsplit = std::max(1u, std::min((1024u + W.groups - 1) / W.groups, std::min(c->fb_steps, 16u)));
     return W;
 }
-// candidate keys of ANY pass of up to `pass` items: nb * nsplit(nb) is not monotonic in nb (see cand_entries_upto)
+// candidate keys of ANY pass of up to `pass` items: nb * nsplit(nb) is not monotonic in nb (see scan_cand_ranges)
 size_t wide_cand_entries(const baz_music_ctx* c, uint32_t pass)
 {
     const WideScanGeom W = wide_scan_geometry(c, pass);
@@ -1617,7 +1632,6 @@ int process_wide_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, void
 #undef BAZ_WIDE_ARGS
                 HIP_TRY(c, hipGetLastError());
             }
-            c->last_nsplit = nsplit;
             {
                 ProfScope ps(c, BAZ_MUSIC_STAGE_MERGE);
                 // the statistic counter of the NEXT call is cleared by the last pass's merge only (the passes of one call add up)
@@ -2205,9 +2219,9 @@ int process_device_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, vo
         ang = c->dRefAl;
         lvl = c->dRefAl + entries;
     }
-    r = launch_scan(c, c->dQ, qstride, batch, ang, lvl, spec);
-    if (r) return r;
-    r = launch_merge(c, batch, ang, lvl, spec);
+    const ScanDone scan = launch_scan(c, qstride, batch, spec);
+    if (scan.rc) return scan.rc;
+    r = launch_merge(c, scan, batch, ang, lvl, spec);
     if (r) return r;
     c->stat_next_clean = true;     // the merge cleared the next call's statistic counter
     if (c->peak_mode) {
@@ -2652,14 +2666,10 @@ int baz_music_create(baz_music_ctx** out, uint32_t m, uint32_t n, uint32_t nsamp
     if (c->fused_covevd) c->stage_name[BAZ_MUSIC_STAGE_COV] = "bazmusic::cov4_evd_kernel";
     snprintf(buf, sizeof(buf), m <= 4 ? "bazmusic::evd_proj_kernel<%u>" : "bazmusic::evd_proj_lds_kernel<%u>", m);
     c->stage_name[BAZ_MUSIC_STAGE_EVD] = buf;
-    snprintf(buf, sizeof(buf), i8_active(c) ? "bazmusic::scan_i8_kernel<%u," : "bazmusic::scan_mfma_kernel<%u,", m);
-    c->stage_name[BAZ_MUSIC_STAGE_SCAN] = buf;
     snprintf(buf, sizeof(buf), "bazmusic::topn_merge_kernel<%u>", topn_list_len(n));
     c->stage_name[BAZ_MUSIC_STAGE_MERGE] = buf;
-    snprintf(c->scan_names[0], sizeof(c->scan_names[0]), "bazmusic::scan_mfma_kernel<%u,", m);
-    snprintf(c->scan_names[1], sizeof(c->scan_names[1]), "bazmusic::scan_i8_kernel<%u,", m);
-    snprintf(c->scan_names[2], sizeof(c->scan_names[2]), "bazmusic::scan_coarse_kernel<%u,", m);
-    snprintf(c->scan_names[3], sizeof(c->scan_names[3]), "bazmusic::scan_i8p_kernel<%u,", m);
+    static const char* const scan_kernels[4] = {"scan_mfma_kernel", "scan_i8_kernel", "scan_coarse_kernel", "scan_i8p_kernel"};   // by ScanKind
+    for (int k = 0; k < 4; ++k) snprintf(c->scan_names[k], sizeof(c->scan_names[k]), "bazmusic::%s<%u,", scan_kernels[k], m);
     *out = c;
     return BAZ_MUSIC_OK;
 }
@@ -3096,8 +3106,7 @@ const char* baz_music_stage_name(baz_music_ctx* c, int stage)
         // before the first launch: what a call with the spectrum port would take
         // (the four names are formatted once, in baz_music_create: the pointer handed out stays valid for the context's life)
         std::lock_guard<std::mutex> lk(c->mtx);
-        const int kind = c->scan_kind >= 0 ? c->scan_kind : (i8_active(c) ? 1 : (i8p_active(c) ? 3 : 0));
-        return c->scan_names[kind >= 0 && kind < 4 ? kind : 0];
+        return c->scan_names[c->scan_kind >= 0 ? c->scan_kind : (int)scan_form(c, true).kind];
     }
     return c->stage_name[stage].c_str();
 }
@@ -3146,18 +3155,16 @@ int baz_music_debug_coarse_margin(baz_music_ctx* c, const void* d_in, uint32_t b
     r = launch_frontend(c, d_in, batch, c->dQ, qstride);
     if (r) return r;
     HIP_TRY(c, hipMemsetAsync(c->dMargin, 0, sizeof(unsigned long long), c->stream));
-    const ScanRefine rf = scan_refine_validation(c);
     const bool big = c->m > 4;                   // (m >= 5: the RG = 2, TPP = 4 instantiation, like the scan's)
     const uint32_t per_group = big ? 64u * (uint32_t)coarse_rg_wide((int)c->m, 2) : 256u;
-    const uint32_t groups = (batch + per_group - 1) / per_group, nph = c->cs_tiles / (big ? 4 : 8);
+    // one range per row: every (item, bin) in both forms
+    CoarseLaunch L{(batch + per_group - 1) / per_group, c->cs_tiles / (big ? 4u : 8u), 1u, scan_refine_validation(c), c->dMargin};
     float* d_dump = nullptr;                     // lab (BAZ_MUSIC_DEBUG_DUMP=<file>): every ratio, [item][bin] float32
     const char* dump_path = BAZ_LAB_ENV("BAZ_MUSIC_DEBUG_DUMP");
     if (dump_path && dev_malloc((void**)&d_dump, (size_t)batch * c->res * sizeof(float)) != hipSuccess) d_dump = nullptr;
     if (d_dump) (void)hipMemsetAsync(d_dump, 0, (size_t)batch * c->res * sizeof(float), c->stream);
-#define BAZ_VAL(MV, NV, RGV, TPV)                                                                                           \
-    hipLaunchKernelGGL((scan_coarse_kernel<MV, NV, RGV, TPV, true>), dim3(groups), dim3(256), 0, c->stream, c->dQ, c->tab.dCS, \
-                       c->tab.dCS + (size_t)(c->cs_tiles + 1) * cs_c_units(MV), c->dCand,                                                  \
-                       batch, c->res, qstride, nph, 1u, c->keep_mask, c->n, rf, c->tab.cs, c->dMargin, d_dump)
+    L.val_dump = d_dump;
+#define BAZ_VAL(MV, NV, RGV, TPV) coarse_launch<MV>(c, &scan_coarse_kernel<MV, NV, RGV, TPV, true>, L, batch, qstride)
     const bool n2 = c->n <= 2;
     switch (c->m) {
         case 2: BAZ_VAL(2, 2, 4, 8); break;
@@ -3236,14 +3243,9 @@ int baz_music_debug_i8_margin(baz_music_ctx* c, const void* d_in, uint32_t batch
         r = launch_frontend(c, d_in, batch, c->dQ, qstride);
         if (r) return r;
         HIP_TRY(c, hipMemsetAsync(c->dI8Stat + 2, 0, 3 * sizeof(unsigned long long), c->stream));
-        const ScanRefine rf = scan_refine_validation(c);
         const ScanGeom G = scan_geometry(batch, c->fb_steps, c->nclass, 1, c->m);
-        const uint4* p1 = c->tab.dIP + I8P_STEP_UNITS;
-        const uint4* p2 = p1 + i8p_operand_units(c->fb_steps);
-#define BAZ_VALP(MV)                                                                                                          \
-    case MV: hipLaunchKernelGGL((scan_i8p_kernel<MV, 2, false, false, true>), dim3(G.blocks), dim3(256), 0, c->stream, c->dQ, p1, p2, \
-                                c->tab.dFB + c->fb_step_elems, nullptr, c->dCand, batch, c->res, qstride, 1u, c->nclass, G.rows_per_class, \
-                                c->keep_mask, c->n, rf, c->tab.i8, nullptr, c->dI8Stat + 2); break;
+        const I8Launch L{G.blocks, 1u, c->n, nullptr, scan_refine_validation(c), nullptr, c->dI8Stat + 2};
+#define BAZ_VALP(MV) case MV: i8p_launch(c, &scan_i8p_kernel<MV, 2, false, false, true>, L, G.rows_per_class, batch, qstride); break;
         switch (c->m) {
 #ifndef BAZ_MUSIC_QUICK
             BAZ_VALP(2) BAZ_VALP(3)
@@ -3268,12 +3270,8 @@ int baz_music_debug_i8_margin(baz_music_ctx* c, const void* d_in, uint32_t batch
     c->i8_on = on;
     if (r) return r;
     HIP_TRY(c, hipMemsetAsync(c->dI8Stat + 2, 0, 3 * sizeof(unsigned long long), c->stream));
-    const ScanRefine rf = scan_refine_validation(c);
-    const uint32_t blocks = (batch + 63) / 64;
-#define BAZ_VAL8(MV)                                                                                                      \
-    case MV: hipLaunchKernelGGL((scan_i8_kernel<MV, 2, false, false, true>), dim3(blocks), dim3(256), 0, c->stream, c->dQ, \
-                                c->tab.dIB, c->tab.dIB + i8_image_bytes5(c->m, c->fb_steps) / 16, c->tab.dFB + c->fb_step_elems, nullptr, c->dCand, \
-                                batch, c->res, qstride, 1u, c->keep_mask, c->n, rf, c->tab.i8, nullptr, c->dI8Stat + 2); break;
+    const I8Launch L{(batch + 63) / 64, 1u, c->n, nullptr, scan_refine_validation(c), nullptr, c->dI8Stat + 2};
+#define BAZ_VAL8(MV) case MV: i8_launch(c, &scan_i8_kernel<MV, 2, false, false, true>, L, batch, qstride); break;
     switch (c->m) {
         BAZ_VAL8(6) BAZ_VAL8(7) BAZ_VAL8(8) BAZ_VAL8(9) BAZ_VAL8(10) BAZ_VAL8(11) BAZ_VAL8(12) BAZ_VAL8(13) BAZ_VAL8(14)
         BAZ_VAL8(15) BAZ_VAL8(16)
