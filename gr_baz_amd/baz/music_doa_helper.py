@@ -151,6 +151,13 @@ def _set_refine_mode(h, parabolic):
     h.impl.set_refine_mode(bool(parabolic))
 
 
+def _set_averaging(h, window, forgetting):
+    # EXTENSION, no reference counterpart: the covariance of every item averaged over the last `window` items of the stream
+    # (weights forgetting ** age), see include/baz_music_hip.h.  Stays in force across set_frequency(): covariances do not
+    # depend on the table, so the history survives a retune as well.
+    h.impl.set_averaging(int(window), float(forgetting))
+
+
 if _HAVE_GR:
 
     class music_doa_helper(gr.hier_block2):
@@ -189,6 +196,11 @@ if _HAVE_GR:
             reference's grid angles).  Best with the wrapped block's set_peak_mode(True)."""
             _set_refine_mode(self, parabolic)
 
+        def set_averaging(self, window, forgetting=1.0):
+            """Opt-in (not reference behaviour): estimate every item from the covariances of the last `window` items, weighted
+            forgetting ** age (window 1: off).  Raises ValueError unless 1 <= window <= 64 and 0 < forgetting <= 1."""
+            _set_averaging(self, window, forgetting)
+
 else:
 
     class music_doa_helper(object):
@@ -220,6 +232,11 @@ else:
             """Opt-in (not reference behaviour): angles between the grid's bins by a parabolic fit of the null (False: the
             reference's grid angles).  Best with the wrapped block's set_peak_mode(True)."""
             _set_refine_mode(self, parabolic)
+
+        def set_averaging(self, window, forgetting=1.0):
+            """Opt-in (not reference behaviour): estimate every item from the covariances of the last `window` items, weighted
+            forgetting ** age (window 1: off).  Raises ValueError unless 1 <= window <= 64 and 0 < forgetting <= 1."""
+            _set_averaging(self, window, forgetting)
 
         def work(self, items):
             """Runs the wrapped block on (k, nsamples) complex64 items: returns (ang, lvl[, spectrum])."""

@@ -39,7 +39,10 @@ SYMBOLS = [
     "baz_music_set_order_mode", "baz_music_get_order_mode", "baz_music_last_orders", "baz_music_last_orders_device",
     "baz_music_order_estimate",
     "baz_music_set_refine_mode", "baz_music_get_refine_mode", "baz_music_last_refine_offsets", "baz_music_refine_estimate",
+    "baz_music_set_averaging", "baz_music_get_averaging", "baz_music_reset_averaging", "baz_music_averaging_weights",
+    "baz_music_debug_average",
 ]
+MAX_AVG_WINDOW = 64                 # BAZ_MUSIC_MAX_AVG_WINDOW
 ORDER_MODES = {None: 0, "mdl": 1, "aic": 2}   # baz_music_set_order_mode: criterion by name
 SMOOTH_WORKSPACE_BYTES = 128 << 20  # BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES: re-stacked items per chunk while smoothing is on
 
@@ -193,6 +196,17 @@ def _bind(L):
     L.baz_music_order_estimate.argtypes = [_u32, _u32, _u32, ctypes.c_int, ctypes.POINTER(ctypes.c_double), _u32,
                                            ctypes.POINTER(ctypes.c_uint8)]
     L.baz_music_smoothing_check.argtypes = [_u32, _u32, _f32p, _u32, ctypes.c_int, ctypes.POINTER(ctypes.c_uint8)]
+    L.baz_music_set_averaging.restype = ctypes.c_int
+    L.baz_music_set_averaging.argtypes = [_vp, _u32, ctypes.c_double]
+    L.baz_music_get_averaging.restype = ctypes.c_int
+    L.baz_music_get_averaging.argtypes = [_vp, ctypes.POINTER(_u32), ctypes.POINTER(ctypes.c_double)]
+    L.baz_music_reset_averaging.restype = ctypes.c_int
+    L.baz_music_reset_averaging.argtypes = [_vp]
+    L.baz_music_averaging_weights.restype = ctypes.c_int
+    L.baz_music_averaging_weights.argtypes = [_u32, ctypes.c_double, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                              ctypes.POINTER(ctypes.c_double)]
+    L.baz_music_debug_average.restype = ctypes.c_int
+    L.baz_music_debug_average.argtypes = [_vp, _vp, _u32, _vp]
     return L
 
 
@@ -422,6 +436,26 @@ class Context:
             self._chk(r, "baz_music_last_refine_offsets")
         return out[:r].copy()
 
+    def set_averaging(self, window, forgetting=1.0):
+        """Opt-in extension (not reference behaviour): every item's covariance becomes the weighted mean over the last `window`
+        items of this context's stream, weights forgetting ** age (include/baz_music_hip.h).  window 1: off."""
+        self._chk(self._L.baz_music_set_averaging(self._h, int(window), float(forgetting)), "baz_music_set_averaging")
+
+    def get_averaging(self):
+        """(window, forgetting) in force; (1, 1.0) for a context never set."""
+        w, b = _u32(0), ctypes.c_double(0.0)
+        self._chk(self._L.baz_music_get_averaging(self._h, ctypes.byref(w), ctypes.byref(b)), "baz_music_get_averaging")
+        return int(w.value), float(b.value)
+
+    def reset_averaging(self):
+        """Forgets the averaging history: the next item is the first of its stream."""
+        self._chk(self._L.baz_music_reset_averaging(self._h), "baz_music_reset_averaging")
+
+    def debug_average(self, d_R_in, batch, d_R_out):
+        """The averaging stage alone on `batch` caller-supplied covariances (device pointers); advances the history like a
+        process call of `batch` items."""
+        self._chk(self._L.baz_music_debug_average(self._h, _vp(d_R_in), int(batch), _vp(d_R_out)), "baz_music_debug_average")
+
     def set_stream(self, hip_stream):
         self._chk(self._L.baz_music_set_stream(self._h, _vp(hip_stream) if hip_stream else None),
                   "baz_music_set_stream")
@@ -498,6 +532,20 @@ def order_estimate(m, nsnap, n_max, criterion, eigvals_ascending):
     if r != OK:
         raise ValueError("baz_music_order_estimate: %s" % lib().baz_music_strerror(r).decode())
     return out[:ev.shape[0]].copy()
+
+
+def averaging_weights(window, forgetting=1.0):
+    """HOST-ONLY: (w[window], inv_norm[window + 1], n_eff) of baz_music_set_averaging(window, forgetting): the table the library
+    hands its averaging kernel (needs no device).  inv_norm[c] normalises an item with c taps; inv_norm[0] is 0."""
+    W = int(window)
+    w = np.zeros(max(W, 1), np.float64)
+    inv = np.zeros(max(W, 1) + 1, np.float64)
+    ne = ctypes.c_double(0.0)
+    dp = ctypes.POINTER(ctypes.c_double)
+    r = lib().baz_music_averaging_weights(W, float(forgetting), w.ctypes.data_as(dp), inv.ctypes.data_as(dp), ctypes.byref(ne))
+    if r != OK:
+        raise ValueError("baz_music_averaging_weights: %s" % lib().baz_music_strerror(r).decode())
+    return w[:W].copy(), inv[:W + 1].copy(), float(ne.value)
 
 
 def refine_estimate(y3):

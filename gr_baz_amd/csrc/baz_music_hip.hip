@@ -16,6 +16,7 @@
 #include "table_kernels.hip.h"
 #include "smoothing_kernels.hip.h"
 #include "refine_kernels.hip.h"
+#include "average_kernels.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -309,6 +310,18 @@ struct baz_music_ctx {
     size_t ref_off_cap = 0;         // doubles
     uint32_t ref_count = 0;         // items of the call in flight recorded so far (the next chunk's offset)
     bool ref_on = false;            // whether the last process*() call ran with the mode on (else every offset is 0)
+    // Opt-in covariance averaging across the items of the stream (baz_music_set_averaging; NOT reference behaviour; average_kernels.hip.h,
+    // DESIGN.md 8e).  While avg_window is 1 none of the mode's kernels is launched and nothing below is allocated.
+    uint32_t avg_window = 1;        // W: 1 = off (the reference)
+    double avg_beta = 1.0;          // forgetting factor (1: boxcar)
+    double avg_neff = 1.0;          // effective items of a full window: the emitter-count criterion's N is K * avg_neff
+    bazavg::AvgTable avg_tab = {};  // weights and normalisations of (W, beta): handed to average_kernel by value
+    uint32_t avg_hist = 0;          // plain covariances of the stream so far that the history holds: min(t, W - 1), t = items since create / reset
+    int avg_parity = 0;             // dAvgHist[avg_parity] is the history the next launch reads; it writes the other one
+    double2* dAvgHist[2] = {nullptr, nullptr};   // [W - 1][m*m] each: the last W - 1 plain covariances, oldest first
+    size_t avg_hist_cap[2] = {0, 0};             // double2 elements
+    double2* dRavg = nullptr;       // averaged covariances of the launch in flight (what the EVD reads while the mode is on)
+    size_t ravg_cap = 0;            // double2 elements
     size_t chunk_bytes = 0;   // host-fed path: traffic per pipelined chunk (BAZ_MUSIC_CHUNK_MIB); 0 = by buffer kind
     // host-fed path: page ranges of the caller's buffers this context has page-locked (baz_music_host_register)
     struct HostPin { uintptr_t lo, hi; uint32_t asked; };   // [lo, hi): the caller's exact bytes
@@ -776,6 +789,7 @@ int order_args(baz_music_ctx* c, uint32_t batch, OrderArgs& oa)
     }
     oa.crit = c->order_mode;
     oa.nsnap = (double)(c->order_nsnap ? c->order_nsnap : c->K);
+    if (c->avg_window > 1) oa.nsnap *= c->avg_neff;      // averaging on: the effective snapshots of a full window
     return BAZ_MUSIC_OK;
 }
 
@@ -915,11 +929,61 @@ int launch_evd(baz_music_ctx* c, const double2* dR, uint32_t batch, double* dQ, 
 #undef BAZ_CALL
 }
 
+// ---- opt-in covariance averaging across the items of the stream (average_kernels.hip.h) ------------------------------------------
+int refuse_null(baz_music_ctx* c, const void* p, const char* name);     // (below, next to process_device_locked)
+
+// The mode's buffers: both history buffers for a window of W items (zero-filled on the launch stream when they are allocated, so
+// slots in front of the stream's start hold defined values; they are never taps) and, for `items` > 0, the averaged covariances.
+// Growing a history buffer loses its contents: only a change of W does that, and it resets the history anyway.
+int ensure_average(baz_music_ctx* c, uint32_t W, uint32_t items)
+{
+    const size_t E = (size_t)c->m * c->m, need = (size_t)(W - 1) * E;
+    for (int k = 0; k < 2; ++k) {
+        if (need <= c->avg_hist_cap[k]) continue;
+        const int r = grow(c, c->dAvgHist[k], c->avg_hist_cap[k], need);
+        if (r) return r;
+        HIP_TRY(c, hipMemsetAsync(c->dAvgHist[k], 0, need * sizeof(double2), c->stream));
+    }
+    return items ? grow(c, c->dRavg, c->ravg_cap, (size_t)round_up(items, 64) * E) : BAZ_MUSIC_OK;
+}
+
+// The averaging stage of one launch sequence: dRout[i] = R-bar of item i of `batch` plain covariances dRin, then the history of the
+// next launch (the other buffer), then the host's stream position.  The stream orders the two kernels behind the covariance
+// kernel and in front of the EVD; the next launch's kernels read the new history behind this one's writes.
+int launch_average(baz_music_ctx* c, const double2* dRin, uint32_t batch, double2* dRout)
+{
+    ProfScope ps(c, BAZ_MUSIC_STAGE_COV);
+    const uint32_t E = c->m * c->m, W = c->avg_window;
+    const double2* const Ho = c->dAvgHist[c->avg_parity];
+    double2* const Hn = c->dAvgHist[c->avg_parity ^ 1];
+    if (!Ho || !Hn || !dRin || !dRout || c->avg_hist_cap[0] < (size_t)(W - 1) * E || c->avg_hist_cap[1] < (size_t)(W - 1) * E)
+        return refuse_null(c, nullptr, "dAvgHist / dRavg (ensure_average)");
+    // items per lane: 8 up to a window of 8 (R is read at most 15/8 times), 16 beyond (79/16 times at W = 64)
+    const uint32_t T = W <= 8 ? 8u : 16u;
+    const uint64_t threads = (uint64_t)((batch + T - 1) / T) * E;
+    const dim3 grid((unsigned)((threads + bazavg::AVG_THREADS - 1) / bazavg::AVG_THREADS));
+    if (T == 8) hipLaunchKernelGGL((bazavg::average_kernel<8>), grid, dim3(bazavg::AVG_THREADS), 0, c->stream, dRin, Ho, dRout, c->avg_tab, batch, E, W, c->avg_hist);
+    else hipLaunchKernelGGL((bazavg::average_kernel<16>), grid, dim3(bazavg::AVG_THREADS), 0, c->stream, dRin, Ho, dRout, c->avg_tab, batch, E, W, c->avg_hist);
+    HIP_TRY(c, hipGetLastError());
+    const uint32_t hthreads = (W - 1) * E;
+    hipLaunchKernelGGL(bazavg::average_history_kernel, dim3((hthreads + bazavg::AVG_THREADS - 1) / bazavg::AVG_THREADS), dim3(bazavg::AVG_THREADS), 0,
+                       c->stream, dRin, Ho, Hn, batch, E, W);
+    HIP_TRY(c, hipGetLastError());
+    c->avg_parity ^= 1;
+    c->avg_hist = (uint32_t)std::min<uint64_t>((uint64_t)c->avg_hist + batch, W - 1);
+    return BAZ_MUSIC_OK;
+}
+
 // Covariance + EVD of `batch` items: the projector coefficients into `dQ` (the workspace's c->dQ, or a debug tap's own buffer), the
 // noise eigenvectors into c->dG.  The fused kernel where it applies, else two kernels through c->dR.  ensure_workspace() came first.
 int launch_frontend(baz_music_ctx* c, const void* d_in, uint32_t batch, double* dQ, uint32_t qstride)
 {
     const float* in = static_cast<const float*>(d_in);
+    if (c->avg_window > 1) {   // opt-in averaging: always two kernels through c->dR, the averaging stage between them (ensure_average() came first)
+        int ra = launch_cov(c, in, batch, c->dR);
+        if (ra == BAZ_MUSIC_OK) ra = launch_average(c, c->dR, batch, c->dRavg);
+        return ra ? ra : launch_evd(c, c->dRavg, batch, dQ, qstride, c->dG);
+    }
     if (c->fused_covevd) return launch_covevd(c, in, batch, dQ, qstride, c->dG);
     const int r = launch_cov(c, in, batch, c->dR);
     return r ? r : launch_evd(c, c->dR, batch, dQ, qstride, c->dG);
@@ -1560,6 +1624,10 @@ int process_wide_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, void
     const uint32_t pass = std::min(batch, wide_pass_items(c));
     int r = ensure_wide_workspace(c, pass);
     if (r) return r;
+    if (c->avg_window > 1) {
+        r = ensure_average(c, c->avg_window, pass);
+        if (r) return r;
+    }
     r = check_launch_pointers(c);
     if (r) return r;
     const float* in = static_cast<const float*>(d_in);
@@ -1571,6 +1639,12 @@ int process_wide_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, void
         const uint32_t nb = std::min(pass, batch - off);
         r = launch_cov_wide(c, in + (size_t)off * c->nsamples * 2, nb, c->dR);
         if (r) return r;
+        const double2* Rw = c->dR;             // what the EVD reads: the pass's plain covariances, or their averages (the history runs from pass to pass)
+        if (c->avg_window > 1) {
+            r = launch_average(c, c->dR, nb, c->dRavg);
+            if (r) return r;
+            Rw = c->dRavg;
+        }
         {
             ProfScope ps(c, BAZ_MUSIC_STAGE_EVD);
             const uint8_t* only = nullptr;
@@ -1580,8 +1654,8 @@ int process_wide_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, void
                 const size_t lds = ((tri ? (size_t)c->m * (c->m + 1) / 2 : (size_t)c->m * (c->m + 1)) + (size_t)c->n * 64) * sizeof(double2);
 #define BAZ_SUB_WIDE(P)                                                                                                          \
     do {                                                                                                                         \
-        if (tri) hipLaunchKernelGGL((bazwide::sub_wide_kernel<P, true>), dim3(nb), dim3(64), lds, c->stream, c->dR, c->dGw, c->dSw, c->dRedo, c->m);  \
-        else hipLaunchKernelGGL((bazwide::sub_wide_kernel<P, false>), dim3(nb), dim3(64), lds, c->stream, c->dR, c->dGw, c->dSw, c->dRedo, c->m);     \
+        if (tri) hipLaunchKernelGGL((bazwide::sub_wide_kernel<P, true>), dim3(nb), dim3(64), lds, c->stream, Rw, c->dGw, c->dSw, c->dRedo, c->m);  \
+        else hipLaunchKernelGGL((bazwide::sub_wide_kernel<P, false>), dim3(nb), dim3(64), lds, c->stream, Rw, c->dGw, c->dSw, c->dRedo, c->m);     \
     } while (0)
                 switch (c->n) {
                     case 1: BAZ_SUB_WIDE(1); break;
@@ -1597,7 +1671,7 @@ int process_wide_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, void
                 HIP_TRY(c, hipGetLastError());
                 only = c->dRedo;
             }
-            hipLaunchKernelGGL(bazwide::evd_wide_kernel, dim3(nb), dim3(bazwide::WB), wide_evd_lds(c->m), c->stream, c->dR,
+            hipLaunchKernelGGL(bazwide::evd_wide_kernel, dim3(nb), dim3(bazwide::WB), wide_evd_lds(c->m), c->stream, Rw,
                                c->dGw, c->dSw, c->m, c->n, only);
             HIP_TRY(c, hipGetLastError());
         }
@@ -2128,6 +2202,7 @@ int check_launch_pointers(baz_music_ctx* c)
     BAZ_REQUIRE(c, dRefined);
     BAZ_REQUIRE(c, dR);
     BAZ_REQUIRE(c, dRedo);
+    if (c->avg_window > 1) { BAZ_REQUIRE(c, dRavg); BAZ_REQUIRE(c, dAvgHist[0]); BAZ_REQUIRE(c, dAvgHist[1]); }
     if (c->wide) {
         BAZ_REQUIRE(c, dGw); BAZ_REQUIRE(c, dWS); BAZ_REQUIRE(c, dSw); BAZ_REQUIRE_TAB(c, dTA); BAZ_REQUIRE_TAB(c, dA2);
         if (c->wide_mfma) { BAZ_REQUIRE_TAB(c, dTB); BAZ_REQUIRE_TAB(c, dA2p); }
@@ -2177,8 +2252,19 @@ int launch_refine(baz_music_ctx* c, uint32_t batch, uint32_t qstride, float* d_a
 #undef BAZ_CALL
 }
 
+int process_device_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void* d_ang, void* d_lvl, void* d_spec);
+
+// One launch sequence over `batch` items.  Averaging on: a sequence that fails forgets the history (the stream position the host
+// keeps no longer describes what the device holds); the next item is t = 0.
 int process_device_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, void* d_ang, void* d_lvl,
                           void* d_spec)
+{
+    const int r = process_device_body(c, d_in, batch, d_ang, d_lvl, d_spec);
+    if (r != BAZ_MUSIC_OK) c->avg_hist = 0;
+    return r;
+}
+
+int process_device_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void* d_ang, void* d_lvl, void* d_spec)
 {
     if (c->wide) {
         const int rw = process_wide_locked(c, d_in, batch, d_ang, d_lvl, d_spec);
@@ -2189,6 +2275,10 @@ int process_device_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, vo
     if (r) return r;
     r = reserve_candidates(c, batch);
     if (r) return r;
+    if (c->avg_window > 1) {
+        r = ensure_average(c, c->avg_window, batch);
+        if (r) return r;
+    }
     r = check_launch_pointers(c);
     if (r) return r;
     const uint32_t qstride = baz_music_q_stride(batch);
@@ -2707,6 +2797,9 @@ void baz_music_destroy(baz_music_ctx* c)
         if (c->dOrdTap) (void)dev_free(c->dOrdTap);
         if (c->dRefAl) (void)dev_free(c->dRefAl);
         if (c->dRefOff) (void)dev_free(c->dRefOff);
+        if (c->dRavg) (void)dev_free(c->dRavg);
+        if (c->dAvgHist[0]) (void)dev_free(c->dAvgHist[0]);
+        if (c->dAvgHist[1]) (void)dev_free(c->dAvgHist[1]);
         if (c->dCand) (void)dev_free(c->dCand);
         if (c->dR) (void)dev_free(c->dR);
         if (c->dQ) (void)dev_free(c->dQ);
@@ -2796,6 +2889,10 @@ int baz_music_reserve(baz_music_ctx* c, uint32_t max_batch)
         const uint32_t chunk = smooth_chunk(c, max_batch);
         const int rs = grow(c, c->sm.dY, c->sm.y_cap, (size_t)chunk * c->sm.Kp * c->sm.ms);
         return rs ? rs : baz_music_reserve(c->sm.inner, chunk);
+    }
+    if (c->avg_window > 1) {     // averaging: both history buffers and the averaged covariances of the largest launch
+        const int ra = ensure_average(c, c->avg_window, c->wide ? std::min(max_batch, wide_pass_items(c)) : max_batch);
+        if (ra) return ra;
     }
     if (c->wide) {
         const uint32_t pass = std::min(max_batch, wide_pass_items(c));
@@ -3028,6 +3125,7 @@ int baz_music_process(baz_music_ctx* c, const float* in_ri, uint32_t batch, floa
             if (lvl) memcpy(lvl + (size_t)done * c->n, img + cnt, cnt * 4);
         }
     }
+    if (rc != BAZ_MUSIC_OK) c->avg_hist = 0;       // (averaging: a failed call forgets the history, also when a copy failed)
     return rc ? rc : (int)batch;
 }
 
@@ -3100,6 +3198,8 @@ const char* baz_music_stage_name(baz_music_ctx* c, int stage)
     {
         std::lock_guard<std::mutex> lk(c->mtx);
         if (c->sm.inner) return "";   // smoothing on: no stage of this context runs (baz_music_set_smoothing)
+        // averaging on: the fused shape runs its two-kernel form (launch_frontend)
+        if (stage == BAZ_MUSIC_STAGE_COV && c->fused_covevd && c->avg_window > 1) return "bazmusic::cov4_x4_kernel";
     }
     if (stage == BAZ_MUSIC_STAGE_SCAN && !c->wide) {
         // the kernel the LAST scan launch took (it depends on the wiring of the call and on the table in force: ADVICE r4);
@@ -3133,6 +3233,7 @@ int baz_music_debug_q(baz_music_ctx* c, const void* d_in, uint32_t batch, void* 
     std::lock_guard<std::mutex> lk(c->mtx);
     DeviceGuard guard(c->device);
     if (c->wide || c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;   // the wide path forms no projector (literal form straight from G)
+    if (c->avg_window > 1) return BAZ_MUSIC_E_UNSUPPORTED;        // (averaging on: the tap would consume history)
     int r = ensure_workspace(c, batch);
     if (r) return r;
     return launch_frontend(c, d_in, batch, static_cast<double*>(d_Q), baz_music_q_stride(batch));
@@ -3147,6 +3248,7 @@ int baz_music_debug_coarse_margin(baz_music_ctx* c, const void* d_in, uint32_t b
     std::lock_guard<std::mutex> lk(c->mtx);
     DeviceGuard guard(c->device);
     if (c->wide || c->m > 8 || c->n > 4 || !c->tab.cs_ok || c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;
+    if (c->avg_window > 1) return BAZ_MUSIC_E_UNSUPPORTED;        // (averaging on: the tap would consume history)
     int r = ensure_workspace(c, batch);
     if (r) return r;
     r = reserve_candidates(c, batch);
@@ -3232,6 +3334,7 @@ int baz_music_debug_i8_margin(baz_music_ctx* c, const void* d_in, uint32_t batch
     std::lock_guard<std::mutex> lk(c->mtx);
     DeviceGuard guard(c->device);
     if (c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;
+    if (c->avg_window > 1) return BAZ_MUSIC_E_UNSUPPORTED;        // (averaging on: the tap would consume history)
 #ifdef BAZ_MUSIC_LAB
     if (!c->wide && c->m <= 4 && c->m >= 2 && c->n <= 4 && c->tab.dIP && c->tab.i8_ok) {
         // 2 .. 4 antennas: the level-packed form (scan_i8p_kernels.hip.h), VAL instantiation, one bin range per row
@@ -3660,6 +3763,7 @@ int baz_music_set_smoothing(baz_music_ctx* c, uint32_t subarray, int forward_bac
             old = c->sm.inner;
             c->sm.inner = nullptr;
             c->sm.ms = 0; c->sm.L = 1; c->sm.Kp = 0; c->sm.fb = 0;
+            c->avg_hist = 0;                      // (averaging: the shape of R changes, the history starts over)
         }
         baz_music_destroy(old);                   // (drains the stream first: batches in flight may still use it)
         return BAZ_MUSIC_OK;
@@ -3679,6 +3783,7 @@ int baz_music_set_smoothing(baz_music_ctx* c, uint32_t subarray, int forward_bac
         if (r == BAZ_MUSIC_OK) r = baz_music_set_peak_mode(inner, c->peak_mode);
         if (r == BAZ_MUSIC_OK) r = baz_music_set_order_mode(inner, c->order_mode);
         if (r == BAZ_MUSIC_OK) r = baz_music_set_refine_mode(inner, c->refine_mode);
+        if (r == BAZ_MUSIC_OK) r = baz_music_set_averaging(inner, c->avg_window, c->avg_beta);   // (a new inner context: an empty history)
         if (r == BAZ_MUSIC_OK) {
             inner->order_nsnap = c->K;            // N of the criterion: this context's snapshots, not the K' re-stacked columns
             inner->ord_driven = true;
@@ -3801,6 +3906,67 @@ int baz_music_refine_estimate(const double* y3, uint32_t count, double* delta_ou
     if (count && (!y3 || !delta_out)) return BAZ_MUSIC_E_INVALID;
     for (uint32_t k = 0; k < count; ++k) delta_out[k] = bazrefine::refine_decide(y3[3 * (size_t)k], y3[3 * (size_t)k + 1], y3[3 * (size_t)k + 2]);
     return BAZ_MUSIC_OK;
+}
+
+int baz_music_set_averaging(baz_music_ctx* c, uint32_t window, double forgetting)
+{
+    if (!c || window == 0 || window > BAZ_MUSIC_MAX_AVG_WINDOW || !(forgetting > 0.0) || !(forgetting <= 1.0)) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    DeviceGuard guard(c->device);
+    if (c->sm.inner) {            // smoothing on: the inner context averages (and keeps the history); this one only remembers the mode
+        const int r = baz_music_set_averaging(c->sm.inner, window, forgetting);
+        if (r != BAZ_MUSIC_OK) return r;
+    } else if (window > 1) {      // the history buffers, before anything changes: after an error the previous mode and history stay in force
+        const int r = ensure_average(c, window, 0);
+        if (r != BAZ_MUSIC_OK) return r;
+    }
+    if (window == c->avg_window && forgetting == c->avg_beta) return BAZ_MUSIC_OK;    // nothing changes: the history stays
+    c->avg_window = window;
+    c->avg_beta = forgetting;
+    c->avg_neff = bazavg::averaging_table(window, forgetting, c->avg_tab);
+    c->avg_hist = 0;
+    return BAZ_MUSIC_OK;
+}
+
+int baz_music_get_averaging(const baz_music_ctx* c, uint32_t* window, double* forgetting)
+{
+    if (!c) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(const_cast<baz_music_ctx*>(c)->mtx);
+    if (window) *window = c->avg_window;
+    if (forgetting) *forgetting = c->avg_beta;
+    return BAZ_MUSIC_OK;
+}
+
+int baz_music_reset_averaging(baz_music_ctx* c)
+{
+    if (!c) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    c->avg_hist = 0;
+    return c->sm.inner ? baz_music_reset_averaging(c->sm.inner) : BAZ_MUSIC_OK;
+}
+
+int baz_music_averaging_weights(uint32_t window, double forgetting, double* w, double* inv_norm, double* n_eff)
+{
+    if (window == 0 || window > BAZ_MUSIC_MAX_AVG_WINDOW || !(forgetting > 0.0) || !(forgetting <= 1.0)) return BAZ_MUSIC_E_INVALID;
+    bazavg::AvgTable t;
+    const double ne = bazavg::averaging_table(window, forgetting, t);
+    if (w) std::memcpy(w, t.w, window * sizeof(double));
+    if (inv_norm) std::memcpy(inv_norm, t.inv_norm, ((size_t)window + 1) * sizeof(double));
+    if (n_eff) *n_eff = ne;
+    return BAZ_MUSIC_OK;
+}
+
+int baz_music_debug_average(baz_music_ctx* c, const void* d_R_in, uint32_t batch, void* d_R_out)
+{
+    if (!c || !d_R_in || !d_R_out || d_R_in == d_R_out || batch == 0) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    DeviceGuard guard(c->device);
+    if (c->sm.inner || c->avg_window <= 1) return BAZ_MUSIC_E_UNSUPPORTED;
+    (void)hipGetLastError();
+    int r = ensure_average(c, c->avg_window, 0);
+    if (r == BAZ_MUSIC_OK) r = launch_average(c, static_cast<const double2*>(d_R_in), batch, static_cast<double2*>(d_R_out));
+    if (r != BAZ_MUSIC_OK) c->avg_hist = 0;
+    return r;
 }
 
 int baz_music_get_smoothing(const baz_music_ctx* c, uint32_t* subarray, int* forward_backward)

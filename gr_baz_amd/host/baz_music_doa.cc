@@ -152,7 +152,11 @@ void baz_music_doa::set_pin_buffers(bool on)
 
 unsigned long long baz_music_doa::pinned_bytes() const { return baz_music_host_pinned_bytes(d_ctx); }
 
-bool baz_music_doa::start() { return true; }
+bool baz_music_doa::start()
+{
+    (void)baz_music_reset_averaging(d_ctx);       /* a started flowgraph is a new stream */
+    return true;
+}
 
 bool baz_music_doa::stop()
 {
@@ -186,6 +190,20 @@ void baz_music_doa::set_refine_mode(bool parabolic)
 {
     const int rc = baz_music_set_refine_mode(d_ctx, parabolic ? 1 : 0);
     if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: set_refine_mode: ") + baz_music_strerror(rc));
+}
+
+void baz_music_doa::set_averaging(unsigned int window, double forgetting)
+{
+    const int rc = baz_music_set_averaging(d_ctx, window, forgetting);
+    if (rc == BAZ_MUSIC_E_INVALID) throw std::invalid_argument("music_doa: set_averaging: 1 <= window <= 64 and 0 < forgetting <= 1 are required");
+    if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: set_averaging: ") + baz_music_strerror(rc));
+}
+
+void baz_music_doa::reset_averaging()
+{
+    const int rc = baz_music_reset_averaging(d_ctx);
+    if (rc == BAZ_MUSIC_E_INVALID) throw std::invalid_argument("music_doa: reset_averaging: no context");
+    if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: reset_averaging: ") + baz_music_strerror(rc));
 }
 
 std::vector<unsigned char> baz_music_doa::last_orders(unsigned int count)

@@ -73,6 +73,12 @@ public:
      * the MUSIC denominator at its bin and the two neighbours (baz_music_set_refine_mode, include/baz_music_hip.h); meant to be
      * used with set_peak_mode(true).  lvl and the spectrum port do not change. */
     void set_refine_mode(bool parabolic);
+    /* Extension, off by default (not in the reference): every item's covariance becomes the weighted mean over the last `window`
+     * items of the stream, weights forgetting^age (baz_music_set_averaging, include/baz_music_hip.h); window 1 is off.  The output
+     * rate does not change.  reset_averaging forgets the history (start() does).  Throws std::invalid_argument unless
+     * 1 <= window <= 64 and 0 < forgetting <= 1. */
+    void set_averaging(unsigned int window, double forgetting);
+    void reset_averaging();
 
     /* Page-locking of the scheduler's stream buffers (baz_music_set_host_pinning, include/baz_music_hip.h): work()
      * registers the ranges it is handed the first time it sees them, stop() and the destructor release them.  On by

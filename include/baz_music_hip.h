@@ -248,11 +248,11 @@ BAZ_MUSIC_API int baz_music_set_peak_mode(baz_music_ctx* ctx, int mode);
  *   WHILE ON    mode changes and set_table take effect for items submitted after they return and are serialised against
  *               process*() (a batch sees the old mode / table or the new one).  set_table must pass the mode's checks, else it
  *               returns BAZ_MUSIC_E_INVALID and keeps the old table and mode.  process, process_device, process_device_on,
- *               reserve, sync, set_stream (forwarded), set_peak_mode, set_order_mode, set_refine_mode (forwarded), host_register / set_host_pinning work; every call
+ *               reserve, sync, set_stream (forwarded), set_peak_mode, set_order_mode, set_refine_mode, set_averaging / reset_averaging (forwarded), host_register / set_host_pinning work; every call
  *               is cut into chunks whose re-stacked items fit BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES (at least one item per chunk), and
  *               the host path stages its chunks through device buffers: its results equal the device path's bit for bit.
  *               uses_i8_scan answers for the inner context.  profile, stage_ms, refined_values / refined_items and the debug_
- *               taps that run stages (cov, evd, q, coarse_margin, coarse_fired, i8_margin, i8_stats) return
+ *               taps that run stages (cov, evd, q, average, coarse_margin, coarse_fired, i8_margin, i8_stats) return
  *               BAZ_MUSIC_E_UNSUPPORTED, stage_name returns "".  table_image, bytes_per_item describe the full m-antenna table.
  * get_smoothing returns (m, 0) while off.  smoothing_check runs the checks on a table without a device: 0 or BAZ_MUSIC_E_INVALID
  * (also for m > BAZ_MUSIC_MAX_M, a NULL table, resolution 0); perm_out (m_s bytes, may be NULL) receives P (the identity without
@@ -344,6 +344,58 @@ BAZ_MUSIC_API int baz_music_set_refine_mode(baz_music_ctx* ctx, int mode);
 BAZ_MUSIC_API int baz_music_get_refine_mode(const baz_music_ctx* ctx, int* mode);
 BAZ_MUSIC_API int baz_music_last_refine_offsets(baz_music_ctx* ctx, double* out, uint32_t count);
 BAZ_MUSIC_API int baz_music_refine_estimate(const double* y3, uint32_t count, double* delta_out);
+/* OPT-IN extension, NOT reference behaviour: covariance averaging ACROSS the items of a stream.  The reference estimates every
+ * item on its own, from the K = nsamples / m snapshots of that item (lib/baz_music_doa.cc:82-85).  With the mode on the output rate stays one
+ * estimate per item and the covariance that is decomposed is a weighted mean over the last `window` items: a sliding window (forgetting == 1)
+ * or exponential forgetting truncated at `window` taps (forgetting < 1).  window = W with 1 <= W <= BAZ_MUSIC_MAX_AVG_WINDOW, forgetting =
+ * beta with 0 < beta <= 1; W == 1 is OFF whatever beta is (the default).
+ *   DEFINITION  A context is one stream: its items are numbered t = 0, 1, ... in submission order across process*() calls since create, or
+ *               since the last reset.  With R_t the item's plain covariance, exactly as computed with the mode off:
+ *                 w_0 = 1, w_j = w_{j-1} beta (fp64);   c(t) = min(W, t + 1)
+ *                 Rbar_t = (sum_{j = c(t)-1 .. 0} w_j R_{t-j}) inv_norm[c(t)],   inv_norm[c] = 1 / sum_{j < c} w_j   (summed j ascending)
+ *               Each of the m^2 complex entries is accumulated OLDEST TAP FIRST from 0 with one fp64 FMA per tap and component and then
+ *               multiplied once by inv_norm.  EVD, scan, pickers and every other mode run on Rbar_t exactly as they run on R_t with the
+ *               mode off; ports, output format and the angle grid do not change.  The operation sequence of an output depends on (t, W,
+ *               beta) alone, so AN ITEM'S BITS DO NOT DEPEND ON HOW THE STREAM WAS CUT into calls, chunks or passes, nor on whether a call
+ *               was host-fed or device-resident (no running sum, nothing is ever subtracted).  The first W - 1 items of a stream average
+ *               over the items there are.  tests/averaging_ref.py restates this in numpy.
+ *               For beta == 1, Rbar_t is a scalar multiple of the plain covariance of the concatenated item [X_{t-c+1} .. X_t] (m x c K):
+ *               what the reference itself computes for an item of c nsamples samples.  The projector ignores the scale, so the mode is
+ *               held to the reference and to the per-path error bounds of that longer item, with no tolerance of its own.
+ *   WHAT RUNS   two small kernels between the covariance and the EVD (gr_baz_amd/csrc/average_kernels.hip.h): average_kernel forms Rbar of
+ *               the launch's items from their plain covariances and the history, average_history_kernel writes the history of the next
+ *               launch.  The context keeps the last W - 1 plain covariances in device memory across calls (two buffers used in turn) and
+ *               the stream position on the host.  Their time counts under BAZ_MUSIC_STAGE_COV.  At 4 antennas with K % 256 == 0, where
+ *               covariance and EVD are otherwise one fused kernel, the two-kernel form runs while the mode is on (cov4_x4_kernel ->
+ *               averaging -> evd_proj_kernel: the fused kernel's bits for the same R; stage_name(COV) says so).  OFF launches exactly the
+ *               kernels it launched before the mode existed and is the reference bit for bit: a context never set, one set to W == 1, one
+ *               switched on and off again.
+ *   SCOPE       every antenna count, the 17 .. BAZ_MUSIC_MAX_M path included (the history runs from pass to pass).  Composes with peak mode
+ *               and refinement (they read the spectrum / Q / G of the averaged problem), with the emitter-count mode -- the criterion's N
+ *               becomes K n_eff, n_eff = (sum w)^2 / sum w^2 over the FULL window (W for a boxcar); the first W - 1 items of a stream use
+ *               that same N although they average fewer items -- and with smoothing: the mode is forwarded to the inner context, which
+ *               averages the re-stacked covariances (averaging and smoothing are both linear, so the order does not matter); the outer
+ *               context keeps no history.  An item whose R holds a NaN / Inf POISONS the up to W items whose window contains it: they
+ *               report (0, 0) and a NaN spectrum, as the poisoned item itself does with the mode off; reset_averaging ends that early.  An
+ *               all-zero item is just a zero tap.  While the mode is on, debug_q, debug_coarse_margin and debug_i8_margin return
+ *               BAZ_MUSIC_E_UNSUPPORTED (they would consume history); debug_cov keeps returning the plain R.
+ *   WHEN        set_averaging takes effect for items submitted after it returns and is serialised against process*() like set_peak_mode:
+ *               a batch sees the old mode or the new one.  It forgets the history whenever it changes W or beta (a call that changes
+ *               neither keeps it).  set_smoothing forgets it too (the shape of R changes); set_table does not (covariances do not depend
+ *               on the table); a launch sequence that fails does.  BAZ_MUSIC_E_INVALID for W == 0, W > BAZ_MUSIC_MAX_AVG_WINDOW, beta <= 0,
+ *               beta > 1, a NaN beta or a NULL context; after an error the previous mode and history stay in force.
+ * reset_averaging forgets the history: the next item is t = 0.  get_averaging returns (1, 1.0) for a context never set, else what was set.
+ * averaging_weights needs no device: the routine the library fills its kernels' table with; w receives W weights, inv_norm W + 1 values
+ * (inv_norm[0] = 0: no item has no tap), n_eff the effective number of items of a full window; each pointer may be NULL.
+ * debug_average (device pointers, batch * m*m complex128 each, d_R_out != d_R_in): the averaging stage alone on caller-supplied covariances;
+ * it advances the history exactly as a process call of `batch` items would.  The counterpart of debug_evd, but offered for every antenna count;
+ * BAZ_MUSIC_E_UNSUPPORTED while the mode is off or smoothing is on. */
+#define BAZ_MUSIC_MAX_AVG_WINDOW 64u
+BAZ_MUSIC_API int baz_music_set_averaging(baz_music_ctx* ctx, uint32_t window, double forgetting);
+BAZ_MUSIC_API int baz_music_get_averaging(const baz_music_ctx* ctx, uint32_t* window, double* forgetting);
+BAZ_MUSIC_API int baz_music_reset_averaging(baz_music_ctx* ctx);
+BAZ_MUSIC_API int baz_music_averaging_weights(uint32_t window, double forgetting, double* w, double* inv_norm, double* n_eff);
+BAZ_MUSIC_API int baz_music_debug_average(baz_music_ctx* ctx, const void* d_R_in, uint32_t batch, void* d_R_out);
 /* Statistic: how many (item, bin) values of the LAST process call were recomputed in the reference's literal form
  * ||G^H a||^2 because the projector form a^H Q a put them at or below ~m 1e-8 max||a||^2 (near-nulls of the noise
  * subspace, SNR >~ 55 dB); blocks until that call is done (a host-fed call cut into chunks reports their sum).
