@@ -151,6 +151,14 @@ def _set_refine_mode(h, parabolic):
     h.impl.set_refine_mode(bool(parabolic))
 
 
+def _set_power_mode(h, mode):
+    # EXTENSION, no reference counterpart: a Capon power estimate 1 / Re(a^H R^-1 a) per reported entry (1: behind last_powers(),
+    # 2: also on the lvl port), see include/baz_music_hip.h.  Stays in force across set_frequency().
+    if mode not in (0, 1, 2):
+        raise ValueError("power mode must be 0, 1 or 2, not %r" % (mode,))
+    h.impl.set_power_mode(int(mode))
+
+
 def _set_averaging(h, window, forgetting):
     # EXTENSION, no reference counterpart: the covariance of every item averaged over the last `window` items of the stream
     # (weights forgetting ** age), see include/baz_music_hip.h.  Stays in force across set_frequency(): covariances do not
@@ -196,6 +204,15 @@ if _HAVE_GR:
             reference's grid angles).  Best with the wrapped block's set_peak_mode(True)."""
             _set_refine_mode(self, parabolic)
 
+        def set_power_mode(self, power_mode=1):
+            """Opt-in (not reference behaviour): a Capon power estimate per reported entry, in the units of the covariance
+            (1: behind last_powers(); 2: also on the lvl port; 0: off).  The constructor keeps the reference's signature."""
+            _set_power_mode(self, power_mode)
+
+        def last_powers(self, count):
+            """The float64 power estimates of the first `count` (item, slot) entries of the last work() call."""
+            return numpy.asarray(self.impl.last_powers(int(count)), dtype=numpy.float64)
+
         def set_averaging(self, window, forgetting=1.0):
             """Opt-in (not reference behaviour): estimate every item from the covariances of the last `window` items, weighted
             forgetting ** age (window 1: off).  Raises ValueError unless 1 <= window <= 64 and 0 < forgetting <= 1."""
@@ -232,6 +249,15 @@ else:
             """Opt-in (not reference behaviour): angles between the grid's bins by a parabolic fit of the null (False: the
             reference's grid angles).  Best with the wrapped block's set_peak_mode(True)."""
             _set_refine_mode(self, parabolic)
+
+        def set_power_mode(self, power_mode=1):
+            """Opt-in (not reference behaviour): a Capon power estimate per reported entry, in the units of the covariance
+            (1: behind last_powers(); 2: also on the lvl port; 0: off).  The constructor keeps the reference's signature."""
+            _set_power_mode(self, power_mode)
+
+        def last_powers(self, count):
+            """The float64 power estimates of the first `count` (item, slot) entries of the last work() call."""
+            return numpy.asarray(self.impl.last_powers(int(count)), dtype=numpy.float64)
 
         def set_averaging(self, window, forgetting=1.0):
             """Opt-in (not reference behaviour): estimate every item from the covariances of the last `window` items, weighted

@@ -39,6 +39,7 @@ SYMBOLS = [
     "baz_music_set_order_mode", "baz_music_get_order_mode", "baz_music_last_orders", "baz_music_last_orders_device",
     "baz_music_order_estimate",
     "baz_music_set_refine_mode", "baz_music_get_refine_mode", "baz_music_last_refine_offsets", "baz_music_refine_estimate",
+    "baz_music_set_power_mode", "baz_music_get_power_mode", "baz_music_last_powers", "baz_music_power_estimate",
     "baz_music_set_averaging", "baz_music_get_averaging", "baz_music_reset_averaging", "baz_music_averaging_weights",
     "baz_music_debug_average",
 ]
@@ -190,6 +191,15 @@ def _bind(L):
     L.baz_music_get_refine_mode.argtypes = [_vp, ctypes.POINTER(ctypes.c_int)]
     L.baz_music_last_refine_offsets.restype = ctypes.c_int
     L.baz_music_last_refine_offsets.argtypes = [_vp, ctypes.POINTER(ctypes.c_double), _u32]
+    L.baz_music_set_power_mode.restype = ctypes.c_int
+    L.baz_music_set_power_mode.argtypes = [_vp, ctypes.c_int]
+    L.baz_music_get_power_mode.restype = ctypes.c_int
+    L.baz_music_get_power_mode.argtypes = [_vp, ctypes.POINTER(ctypes.c_int)]
+    L.baz_music_last_powers.restype = ctypes.c_int
+    L.baz_music_last_powers.argtypes = [_vp, ctypes.POINTER(ctypes.c_double), _u32]
+    L.baz_music_power_estimate.restype = ctypes.c_int
+    L.baz_music_power_estimate.argtypes = [_u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), _u32,
+                                           ctypes.POINTER(ctypes.c_double)]
     L.baz_music_refine_estimate.restype = ctypes.c_int
     L.baz_music_refine_estimate.argtypes = [ctypes.POINTER(ctypes.c_double), _u32, ctypes.POINTER(ctypes.c_double)]
     L.baz_music_order_estimate.restype = ctypes.c_int
@@ -456,6 +466,25 @@ class Context:
         process call of `batch` items."""
         self._chk(self._L.baz_music_debug_average(self._h, _vp(d_R_in), int(batch), _vp(d_R_out)), "baz_music_debug_average")
 
+    def set_power_mode(self, mode):
+        """Opt-in extension (not reference behaviour): 1 computes a Capon power estimate 1 / Re(a^H R^-1 a) per reported entry
+        (last_powers; every port unchanged), 2 additionally puts (float)P on the lvl port (include/baz_music_hip.h); 0 (default): off."""
+        self._chk(self._L.baz_music_set_power_mode(self._h, int(mode)), "baz_music_set_power_mode")
+
+    def get_power_mode(self):
+        mode = ctypes.c_int(0)
+        self._chk(self._L.baz_music_get_power_mode(self._h, ctypes.byref(mode)), "baz_music_get_power_mode")
+        return int(mode.value)
+
+    def last_powers(self, count):
+        """Capon powers (float64, in the units of R) of the first `count` (item, slot) entries of the last process*() call; zeros for
+        a call made with the mode off."""
+        out = np.zeros(max(int(count), 1), np.float64)
+        r = self._L.baz_music_last_powers(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(count))
+        if r < 0:
+            self._chk(r, "baz_music_last_powers")
+        return out[:r].copy()
+
     def set_stream(self, hip_stream):
         self._chk(self._L.baz_music_set_stream(self._h, _vp(hip_stream) if hip_stream else None),
                   "baz_music_set_stream")
@@ -546,6 +575,23 @@ def averaging_weights(window, forgetting=1.0):
     if r != OK:
         raise ValueError("baz_music_averaging_weights: %s" % lib().baz_music_strerror(r).decode())
     return w[:W].copy(), inv[:W + 1].copy(), float(ne.value)
+
+
+def power_estimate(R, a):
+    """HOST-ONLY: the Capon powers 1 / Re(a^H R^-1 a) the library's definition gives for one covariance R (m x m complex) and the
+    steering rows a (count x m complex64) (needs no device).  Returns a float64 array, one power per row."""
+    R = np.ascontiguousarray(R, dtype=np.complex128)
+    if R.ndim != 2 or R.shape[0] != R.shape[1]:
+        raise ValueError("power_estimate: R must be a square matrix")
+    m = R.shape[0]
+    a = np.ascontiguousarray(a, dtype=np.complex64).reshape(-1, m) if m else np.zeros((0, 0), np.complex64)
+    out = np.zeros(max(a.shape[0], 1), np.float64)
+    r = lib().baz_music_power_estimate(m, R.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                       a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), a.shape[0],
+                                       out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    if r != OK:
+        raise ValueError("baz_music_power_estimate: %s" % lib().baz_music_strerror(r).decode())
+    return out[:a.shape[0]].copy()
 
 
 def refine_estimate(y3):

@@ -16,6 +16,7 @@
 #include "table_kernels.hip.h"
 #include "smoothing_kernels.hip.h"
 #include "refine_kernels.hip.h"
+#include "power_kernels.hip.h"
 #include "average_kernels.hip.h"
 
 #include <algorithm>
@@ -310,6 +311,14 @@ struct baz_music_ctx {
     size_t ref_off_cap = 0;         // doubles
     uint32_t ref_count = 0;         // items of the call in flight recorded so far (the next chunk's offset)
     bool ref_on = false;            // whether the last process*() call ran with the mode on (else every offset is 0)
+    // Opt-in per-emitter Capon power (baz_music_set_power_mode; NOT reference behaviour; power_kernels.hip.h).  While
+    // power_mode is 0 its kernel is not launched and nothing below is allocated.  The pickers' staging buffer is dRefAl, shared with
+    // the refinement: one buffer with either mode or both on.
+    int power_mode = 0;             // 0: off (the reference); 1: the estimates behind baz_music_last_powers; 2: ... and lvl carries (float)P
+    double* dPow = nullptr;         // P per (item, slot) of the last process*() call, in call order (all chunks)
+    size_t pow_cap = 0;             // doubles
+    uint32_t pow_count = 0;         // items of the call in flight recorded so far (the next chunk's offset)
+    bool pow_on = false;            // whether the last process*() call ran with the mode on (else every power is 0)
     // Opt-in covariance averaging across the items of the stream (baz_music_set_averaging; NOT reference behaviour; average_kernels.hip.h,
     // DESIGN.md 8e).  While avg_window is 1 none of the mode's kernels is launched and nothing below is allocated.
     uint32_t avg_window = 1;        // W: 1 = off (the reference)
@@ -762,8 +771,8 @@ int grow(baz_music_ctx* c, T*& p, size_t& cap, size_t need)
 // ---- emitter-count mode: bookkeeping --------------------------------------------------------------------------------------------
 int grow_bytes(baz_music_ctx* c, uint8_t*& p, size_t& cap, size_t need) { return grow(c, p, cap, (need + 255) / 256 * 256); }
 
-// Opens a process*() call of `items` items for baz_music_last_orders and baz_music_last_refine_offsets: the counts / offsets of all
-// its chunks land in dOrd / dRefOff in call order.  With both modes off this is five stores.
+// Opens a process*() call of `items` items for baz_music_last_orders, baz_music_last_refine_offsets and baz_music_last_powers: the
+// counts / offsets / powers of all its chunks land in dOrd / dRefOff / dPow in call order.  With the modes off this is seven stores.
 int order_begin(baz_music_ctx* c, uint32_t items)
 {
     c->ord_count = 0;
@@ -773,6 +782,12 @@ int order_begin(baz_music_ctx* c, uint32_t items)
     c->ref_on = c->refine_mode != 0;
     if (c->ref_on) {
         const int r = grow(c, c->dRefOff, c->ref_off_cap, (size_t)items * c->n);
+        if (r) return r;
+    }
+    c->pow_count = 0;
+    c->pow_on = c->power_mode != 0;
+    if (c->pow_on) {
+        const int r = grow(c, c->dPow, c->pow_cap, (size_t)items * c->n);
         if (r) return r;
     }
     return c->ord_on ? grow_bytes(c, c->dOrd, c->ord_cap, items) : BAZ_MUSIC_OK;
@@ -984,7 +999,8 @@ int launch_frontend(baz_music_ctx* c, const void* d_in, uint32_t batch, double* 
         if (ra == BAZ_MUSIC_OK) ra = launch_average(c, c->dR, batch, c->dRavg);
         return ra ? ra : launch_evd(c, c->dRavg, batch, dQ, qstride, c->dG);
     }
-    if (c->fused_covevd) return launch_covevd(c, in, batch, dQ, qstride, c->dG);
+    // (power mode on: the fused kernel also stores its R, the tap baz_music_debug_cov uses -- same kernel, same Q and G bits)
+    if (c->fused_covevd) return launch_covevd(c, in, batch, dQ, qstride, c->dG, c->power_mode ? c->dR : nullptr);
     const int r = launch_cov(c, in, batch, c->dR);
     return r ? r : launch_evd(c, c->dR, batch, dQ, qstride, c->dG);
 }
@@ -2252,6 +2268,43 @@ int launch_refine(baz_music_ctx* c, uint32_t batch, uint32_t qstride, float* d_a
 #undef BAZ_CALL
 }
 
+// Opt-in Capon power of the chunk's entries (power_kernels.hip.h), the last launch of a sequence: reads the staged ang | lvl (ang on the
+// grid, refinement or not), the covariances this sequence's EVD read and the raw image of the table in force; writes this chunk's
+// powers and whatever of the caller's ang / lvl refine_kernel has not written (d_ang / d_lvl null: nothing).
+template <int M>
+int launch_power_t(baz_music_ctx* c, const bazpower::PowerArgs& A)
+{
+    constexpr uint32_t IPB = bazpower::PowerGeom<M>::IPB;
+    hipLaunchKernelGGL((bazpower::power_kernel<M>), dim3((A.batch + IPB - 1) / IPB), dim3(256), 0, c->stream, A);
+    HIP_TRY(c, hipGetLastError());
+    return BAZ_MUSIC_OK;
+}
+
+int launch_power(baz_music_ctx* c, uint32_t batch, float* d_ang, float* d_lvl)
+{
+    ProfScope ps(c, BAZ_MUSIC_STAGE_MERGE);
+    BAZ_REQUIRE(c, dRefAl); BAZ_REQUIRE(c, dPow); BAZ_REQUIRE_TAB(c, dRW);
+    if (c->avg_window > 1) BAZ_REQUIRE(c, dRavg); else BAZ_REQUIRE(c, dR);
+    bazpower::PowerArgs A;
+    const size_t entries = (size_t)batch * c->n;
+    A.ang_in = c->dRefAl;
+    A.lvl_in = c->dRefAl + entries;
+    A.ang_out = d_ang;
+    A.lvl_out = d_lvl;
+    A.pow_out = c->dPow + (size_t)c->pow_count * c->n;
+    A.R = c->avg_window > 1 ? c->dRavg : c->dR;      // what launch_frontend handed to the EVD
+    A.raw = c->tab.dRW;
+    A.rel_floor = BAZ_MUSIC_POWER_PIVOT_FLOOR;
+    A.batch = batch; A.n = c->n; A.res = c->res;
+    A.lvl_is_power = c->power_mode == 2;
+#define BAZ_CALL(MV) launch_power_t<MV>(c, A)
+    switch (c->m) {
+        BAZ_M_CASES(BAZ_CALL)
+        default: return BAZ_MUSIC_E_UNSUPPORTED;
+    }
+#undef BAZ_CALL
+}
+
 int process_device_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void* d_ang, void* d_lvl, void* d_spec);
 
 // One launch sequence over `batch` items.  Averaging on: a sequence that fails forgets the history (the stream position the host
@@ -2297,13 +2350,16 @@ int process_device_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void
         if (r) return r;
         spec = c->dPeakSpec;
     }
-    // refinement: the pickers write ang | lvl (lvl always: it marks the real entries) into a staging buffer of this context and
-    // refine_kernel writes the caller's -- which may be host memory mapped over the link, never read back
+    // refinement / power mode: the pickers write ang | lvl (lvl always: it marks the real entries) into a staging buffer of this context
+    // and refine_kernel / power_kernel write the caller's -- which may be host memory mapped over the link, never read back
     float* ang = static_cast<float*>(d_ang);
     float* lvl = static_cast<float*>(d_lvl);
     const size_t entries = (size_t)batch * c->n;
-    if (c->refine_mode) {
-        if (!c->ref_on || !c->dRefOff || ((size_t)c->ref_count + batch) * c->n > c->ref_off_cap) return refuse_null(c, nullptr, "dRefOff (order_begin)");
+    if (c->refine_mode && (!c->ref_on || !c->dRefOff || ((size_t)c->ref_count + batch) * c->n > c->ref_off_cap))
+        return refuse_null(c, nullptr, "dRefOff (order_begin)");
+    if (c->power_mode && (!c->pow_on || !c->dPow || ((size_t)c->pow_count + batch) * c->n > c->pow_cap))
+        return refuse_null(c, nullptr, "dPow (order_begin)");
+    if (c->refine_mode || c->power_mode) {
         r = grow(c, c->dRefAl, c->ref_al_cap, entries * 2);
         if (r) return r;
         ang = c->dRefAl;
@@ -2326,9 +2382,18 @@ int process_device_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void
         c->ord_count += batch;
     }
     if (c->refine_mode) {
-        r = launch_refine(c, batch, qstride, static_cast<float*>(d_ang), static_cast<float*>(d_lvl));
+        // (with power mode 2 and port 1 wired, power_kernel writes lvl: every caller-visible word is written once)
+        const bool lvl_later = c->power_mode == 2 && d_lvl;
+        r = launch_refine(c, batch, qstride, static_cast<float*>(d_ang), lvl_later ? nullptr : static_cast<float*>(d_lvl));
         if (r) return r;
         c->ref_count += batch;
+    }
+    if (c->power_mode) {           // the last launch: ang / lvl where refine_kernel has not written them
+        float* const p_ang = c->refine_mode ? nullptr : static_cast<float*>(d_ang);
+        float* const p_lvl = (c->refine_mode && c->power_mode != 2) ? nullptr : static_cast<float*>(d_lvl);
+        r = launch_power(c, batch, p_ang, p_lvl);
+        if (r) return r;
+        c->pow_count += batch;
     }
     return BAZ_MUSIC_OK;
 }
@@ -2797,6 +2862,7 @@ void baz_music_destroy(baz_music_ctx* c)
         if (c->dOrdTap) (void)dev_free(c->dOrdTap);
         if (c->dRefAl) (void)dev_free(c->dRefAl);
         if (c->dRefOff) (void)dev_free(c->dRefOff);
+        if (c->dPow) (void)dev_free(c->dPow);
         if (c->dRavg) (void)dev_free(c->dRavg);
         if (c->dAvgHist[0]) (void)dev_free(c->dAvgHist[0]);
         if (c->dAvgHist[1]) (void)dev_free(c->dAvgHist[1]);
@@ -2885,6 +2951,11 @@ int baz_music_reserve(baz_music_ctx* c, uint32_t max_batch)
         const int rr = grow(oc, oc->dRefOff, oc->ref_off_cap, (size_t)max_batch * oc->n);
         if (rr) return rr;
     }
+    if (c->power_mode && !c->ord_driven) {   // power mode: one estimate per entry of a whole call (kept by the context that runs the kernels)
+        baz_music_ctx* const oc = c->sm.inner ? c->sm.inner : c;
+        const int rp = grow(oc, oc->dPow, oc->pow_cap, (size_t)max_batch * oc->n);
+        if (rp) return rp;
+    }
     if (c->sm.inner) {   // smoothing on: the inner context's workspace for one chunk, and the re-stacked chunk
         const uint32_t chunk = smooth_chunk(c, max_batch);
         const int rs = grow(c, c->sm.dY, c->sm.y_cap, (size_t)chunk * c->sm.Kp * c->sm.ms);
@@ -2901,7 +2972,7 @@ int baz_music_reserve(baz_music_ctx* c, uint32_t max_batch)
         return (rw || !c->wide_mfma || c->wide_literal_only) ? rw : ensure_candidates(c, wide_cand_entries(c, pass));
     }
     int r = ensure_workspace(c, max_batch);
-    if (r == BAZ_MUSIC_OK && c->refine_mode) r = grow(c, c->dRefAl, c->ref_al_cap, (size_t)max_batch * c->n * 2);   // (the pickers' staging)
+    if (r == BAZ_MUSIC_OK && (c->refine_mode || c->power_mode)) r = grow(c, c->dRefAl, c->ref_al_cap, (size_t)max_batch * c->n * 2);   // (the pickers' staging)
 #ifdef BAZ_MUSIC_LAB
     if (r == BAZ_MUSIC_OK && c->sort_mode != 0) r = ensure_sort_workspace(c, max_batch);
 #endif
@@ -3783,6 +3854,7 @@ int baz_music_set_smoothing(baz_music_ctx* c, uint32_t subarray, int forward_bac
         if (r == BAZ_MUSIC_OK) r = baz_music_set_peak_mode(inner, c->peak_mode);
         if (r == BAZ_MUSIC_OK) r = baz_music_set_order_mode(inner, c->order_mode);
         if (r == BAZ_MUSIC_OK) r = baz_music_set_refine_mode(inner, c->refine_mode);
+        if (r == BAZ_MUSIC_OK) r = baz_music_set_power_mode(inner, c->power_mode);
         if (r == BAZ_MUSIC_OK) r = baz_music_set_averaging(inner, c->avg_window, c->avg_beta);   // (a new inner context: an empty history)
         if (r == BAZ_MUSIC_OK) {
             inner->order_nsnap = c->K;            // N of the criterion: this context's snapshots, not the K' re-stacked columns
@@ -3967,6 +4039,93 @@ int baz_music_debug_average(baz_music_ctx* c, const void* d_R_in, uint32_t batch
     if (r == BAZ_MUSIC_OK) r = launch_average(c, static_cast<const double2*>(d_R_in), batch, static_cast<double2*>(d_R_out));
     if (r != BAZ_MUSIC_OK) c->avg_hist = 0;
     return r;
+}
+
+int baz_music_set_power_mode(baz_music_ctx* c, int mode)
+{
+    if (!c || mode < 0 || mode > 2) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    if (mode && c->wide) return BAZ_MUSIC_E_UNSUPPORTED;   // (power_kernel is specialised per m, like the pickers it follows)
+    if (c->sm.inner) {   // (the inner context is never wider than this one)
+        const int r = baz_music_set_power_mode(c->sm.inner, mode);
+        if (r != BAZ_MUSIC_OK) return r;
+    }
+    c->power_mode = mode;
+    return BAZ_MUSIC_OK;
+}
+
+int baz_music_get_power_mode(const baz_music_ctx* c, int* mode)
+{
+    if (!c || !mode) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(const_cast<baz_music_ctx*>(c)->mtx);
+    *mode = c->power_mode;
+    return BAZ_MUSIC_OK;
+}
+
+int baz_music_last_powers(baz_music_ctx* c, double* out, uint32_t count)
+{
+    if (!c || (!out && count)) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    if (c->sm.inner) return baz_music_last_powers(c->sm.inner, out, count);
+    DeviceGuard guard(c->device);
+    const uint64_t total = (uint64_t)(c->pow_on ? c->pow_count : c->ord_items) * c->n;
+    const uint32_t have = (uint32_t)std::min<uint64_t>(count, total);
+    if (!c->pow_on) {                              // the call ran with the mode off: nothing was estimated
+        if (have) memset(out, 0, (size_t)have * sizeof(double));
+        return (int)have;
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (have) HIP_TRY(c, hipMemcpy(out, c->dPow, (size_t)have * sizeof(double), hipMemcpyDeviceToHost));
+    return (int)have;
+}
+
+// The definition of include/baz_music_hip.h loop for loop; the degeneracy rule and the s -> P step are power_kernel's own text.
+int baz_music_power_estimate(uint32_t m, const double* R_ri, const float* a_ri, uint32_t count, double* out)
+{
+    if (m < 1 || m > BAZ_MUSIC_MAX_M) return BAZ_MUSIC_E_INVALID;
+    if (count == 0) return BAZ_MUSIC_OK;
+    if (!R_ri || !a_ri || !out) return BAZ_MUSIC_E_INVALID;
+    std::vector<double> Lr((size_t)m * m, 0.0), Li((size_t)m * m, 0.0), d(m, 0.0), zr(m), zi(m);
+    auto Rr = [&](uint32_t i, uint32_t j) { return R_ri[2 * ((size_t)i * m + j)]; };
+    auto Ri = [&](uint32_t i, uint32_t j) { return R_ri[2 * ((size_t)i * m + j) + 1]; };
+    double trace = 0.0;
+    for (uint32_t i = 0; i < m; ++i) trace += Rr(i, i);
+    const double floor = bazpower::power_pivot_floor(trace, m, BAZ_MUSIC_POWER_PIVOT_FLOOR);
+    bool ok = true;
+    for (uint32_t j = 0; j < m && ok; ++j) {
+        for (uint32_t i = j; i < m; ++i) {
+            double vr = Rr(i, j), vi = i == j ? 0.0 : Ri(i, j);
+            for (uint32_t k = 0; k < j; ++k) {     // L_ik conj(L_jk) d_k
+                const double wr = Lr[(size_t)j * m + k] * d[k], wi = Li[(size_t)j * m + k] * d[k];
+                vr -= Lr[(size_t)i * m + k] * wr + Li[(size_t)i * m + k] * wi;
+                if (i != j) vi -= Li[(size_t)i * m + k] * wr - Lr[(size_t)i * m + k] * wi;
+            }
+            if (i == j) {
+                d[j] = vr;
+                ok = bazpower::power_pivot_ok(vr, floor);
+                if (!ok) break;
+            } else {
+                Lr[(size_t)i * m + j] = vr / d[j];
+                Li[(size_t)i * m + j] = vi / d[j];
+            }
+        }
+    }
+    for (uint32_t e = 0; e < count; ++e) {
+        if (!ok) { out[e] = 0.0; continue; }
+        const float* a = a_ri + 2 * (size_t)e * m;
+        double s = 0.0;
+        for (uint32_t i = 0; i < m; ++i) {
+            double xr = (double)a[2 * i], xi = (double)a[2 * i + 1];
+            for (uint32_t k = 0; k < i; ++k) {
+                xr -= Lr[(size_t)i * m + k] * zr[k] - Li[(size_t)i * m + k] * zi[k];
+                xi -= Lr[(size_t)i * m + k] * zi[k] + Li[(size_t)i * m + k] * zr[k];
+            }
+            zr[i] = xr; zi[i] = xi;
+            s += (xr * xr + xi * xi) / d[i];
+        }
+        out[e] = bazpower::power_from_s(s);
+    }
+    return BAZ_MUSIC_OK;
 }
 
 int baz_music_get_smoothing(const baz_music_ctx* c, uint32_t* subarray, int* forward_backward)

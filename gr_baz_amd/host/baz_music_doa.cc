@@ -192,6 +192,22 @@ void baz_music_doa::set_refine_mode(bool parabolic)
     if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: set_refine_mode: ") + baz_music_strerror(rc));
 }
 
+void baz_music_doa::set_power_mode(int mode)
+{
+    const int rc = baz_music_set_power_mode(d_ctx, mode);
+    if (rc == BAZ_MUSIC_E_INVALID) throw std::invalid_argument("music_doa: set_power_mode: mode must be 0 (off), 1 (estimates) or 2 (estimates on the lvl port)");
+    if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: set_power_mode: ") + baz_music_strerror(rc));
+}
+
+std::vector<double> baz_music_doa::last_powers(unsigned int count)
+{
+    std::vector<double> out(count);
+    const int rc = baz_music_last_powers(d_ctx, out.data(), count);
+    if (rc < 0) throw std::runtime_error(std::string("music_doa: last_powers: ") + baz_music_strerror(rc));
+    out.resize((size_t)rc);
+    return out;
+}
+
 void baz_music_doa::set_averaging(unsigned int window, double forgetting)
 {
     const int rc = baz_music_set_averaging(d_ctx, window, forgetting);

@@ -73,6 +73,12 @@ public:
      * the MUSIC denominator at its bin and the two neighbours (baz_music_set_refine_mode, include/baz_music_hip.h); meant to be
      * used with set_peak_mode(true).  lvl and the spectrum port do not change. */
     void set_refine_mode(bool parabolic);
+    /* Extension, off by default (not in the reference): a Capon power estimate 1 / Re(a^H R^-1 a) per reported entry, in the units
+     * of the covariance (baz_music_set_power_mode, include/baz_music_hip.h).  mode 1 computes them and leaves every port as it is,
+     * mode 2 additionally puts them on the lvl port; last_powers: the estimates of the first `count` (item, slot) entries of the
+     * last work() call in fp64. */
+    void set_power_mode(int mode);
+    std::vector<double> last_powers(unsigned int count);
     /* Extension, off by default (not in the reference): every item's covariance becomes the weighted mean over the last `window`
      * items of the stream, weights forgetting^age (baz_music_set_averaging, include/baz_music_hip.h); window 1 is off.  The output
      * rate does not change.  reset_averaging forgets the history (start() does).  Throws std::invalid_argument unless

@@ -243,6 +243,8 @@ PYBIND11_MODULE(_baz_music, mod)
              py::arg("subarray"), py::arg("forward_backward") = false)
         .def("set_order_mode", [](music_doa_handle& h, int criterion) { h.blk->set_order_mode(criterion); }, py::arg("criterion"))
         .def("set_refine_mode", [](music_doa_handle& h, bool on) { h.blk->set_refine_mode(on); }, py::arg("parabolic"))
+        .def("set_power_mode", [](music_doa_handle& h, int mode) { h.blk->set_power_mode(mode); }, py::arg("mode"))
+        .def("last_powers", [](music_doa_handle& h, unsigned int count) { return h.blk->last_powers(count); }, py::arg("count"))
         .def("set_averaging", [](music_doa_handle& h, unsigned int window, double forgetting) { h.blk->set_averaging(window, forgetting); },
              py::arg("window"), py::arg("forgetting") = 1.0)
         .def("reset_averaging", [](music_doa_handle& h) { h.blk->reset_averaging(); })

@@ -248,7 +248,7 @@ BAZ_MUSIC_API int baz_music_set_peak_mode(baz_music_ctx* ctx, int mode);
  *   WHILE ON    mode changes and set_table take effect for items submitted after they return and are serialised against
  *               process*() (a batch sees the old mode / table or the new one).  set_table must pass the mode's checks, else it
  *               returns BAZ_MUSIC_E_INVALID and keeps the old table and mode.  process, process_device, process_device_on,
- *               reserve, sync, set_stream (forwarded), set_peak_mode, set_order_mode, set_refine_mode, set_averaging / reset_averaging (forwarded), host_register / set_host_pinning work; every call
+ *               reserve, sync, set_stream (forwarded), set_peak_mode, set_order_mode, set_refine_mode, set_power_mode, set_averaging / reset_averaging (forwarded), host_register / set_host_pinning work; every call
  *               is cut into chunks whose re-stacked items fit BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES (at least one item per chunk), and
  *               the host path stages its chunks through device buffers: its results equal the device path's bit for bit.
  *               uses_i8_scan answers for the inner context.  profile, stage_ms, refined_values / refined_items and the debug_
@@ -396,6 +396,58 @@ BAZ_MUSIC_API int baz_music_get_averaging(const baz_music_ctx* ctx, uint32_t* wi
 BAZ_MUSIC_API int baz_music_reset_averaging(baz_music_ctx* ctx);
 BAZ_MUSIC_API int baz_music_averaging_weights(uint32_t window, double forgetting, double* w, double* inv_norm, double* n_eff);
 BAZ_MUSIC_API int baz_music_debug_average(baz_music_ctx* ctx, const void* d_R_in, uint32_t batch, void* d_R_out);
+/* OPT-IN extension, NOT reference behaviour: a received-power estimate per reported entry.  lvl is the MUSIC pseudo-spectrum
+ * 1 / ||G^H a||^2: it has no unit, depends on SNR and snapshot count and only ranks the entries of an item.  The Capon (minimum-variance)
+ * estimate P = 1 / Re(a^H R^-1 a) is a power in the units of R; it needs only the covariance, no eigenvalues, projector or noise vectors, and
+ * it is defined entry by entry, so it stays well-posed under the reference's top-n picker whose entries are usually neighbouring bins (a joint
+ * least-squares estimate is singular there).  mode: 0 = off (the default, the reference), 1 = compute the estimates, every port bit for bit
+ * unchanged, 2 = additionally the lvl port carries (float)P instead of 1 / d; anything else BAZ_MUSIC_E_INVALID.
+ *   DEFINITION  for every reported REAL entry (item, slot) -- lvl != 0 after the merge, the peak picker or the count truncation:
+ *                 b   the entry's bin on the steering grid -- the grid bin even with sub-bin refinement on (recovered from the staged,
+ *                     unrefined ang as refine_kernel does it);
+ *                 a   row b of the table in force for that batch, widened exactly from complex64 to fp64;
+ *                 R   the m x m covariance the item's EVD decomposes: what baz_music_debug_cov returns; Rbar_t with averaging on; with
+ *                     smoothing on the inner context's R, a taken from the first m_s columns, like every statement about that mode.
+ *               P = 1 / Re(a^H R^-1 a) in fp64 by an UNPIVOTED LDL^H of R from the lower triangle as stored, the imaginary part of the
+ *               diagonal ignored:
+ *                 d_j  = Re R_jj - sum_{k<j} |L_jk|^2 d_k
+ *                 L_ij = (R_ij - sum_{k<j} L_ik conj(L_jk) d_k) / d_j        (i > j)
+ *                 z_i  = a_i - sum_{k<i} L_ik z_k
+ *                 s    = sum_i |z_i|^2 / d_i
+ *                 P    = 1 / s
+ *               An item is DEGENERATE when some d_j is not finite or d_j <= BAZ_MUSIC_POWER_PIVOT_FLOOR (sum_i Re R_ii) / m (2^-40, the
+ *               clamp of the emitter-count mode): an all-zero item, an item with K < m snapshots, an R that holds NaN or Inf.  All entries of
+ *               a degenerate item get P = 0; an entry whose s is 0 or not finite gets P = 0; missing entries get 0.  P is linear in R:
+ *               R -> sR gives sP, exactly so for s a power of two.  tests/power_ref.py restates this in numpy.
+ *   RAW         P is the raw Capon estimate.  Its known finite-sample factor (K - m + 1) / K (it reads LOW by that factor) is NOT divided
+ *               out, and the noise term sigma^2 / ||a||^2 it carries on top of the emitter's power is NOT subtracted.  No noise floor is
+ *               estimated.
+ *   MODE 2      lvl = (float)P.  ang and the spectrum do not change; entry order stays the pickers' order, by MUSIC strength; a missing
+ *               entry stays (0, 0); a degenerate item's entries keep ang and report lvl = 0 (lvl[i] == spectrum[b] no longer holds).  With
+ *               lvl == NULL mode 2 behaves as mode 1.
+ *   WHAT RUNS   one kernel (gr_baz_amd/csrc/power_kernels.hip.h), the last launch of a sequence (after refinement where that is on): one
+ *               item per group of 4 / 8 / 16 lanes, R read and factorised once per item.  While the mode is on the pickers write into the
+ *               staging buffer refinement uses (one buffer with both on) and the final kernels write the caller's ang / lvl, every word
+ *               once (refinement and mode 2 together: refine_kernel writes ang, power_kernel lvl).  Its time counts under
+ *               BAZ_MUSIC_STAGE_MERGE.  At 4 antennas with K % 256 == 0 the fused covariance + EVD kernel keeps running and also stores
+ *               its R (the tap of debug_cov).  Steering rows come from the image of the table set in force: a batch sees the old table
+ *               or the new one, for P too.  Mode 0 launches exactly the kernels it launched before the mode existed, allocates nothing
+ *               new and is the reference bit for bit: a context never set, one set to 0, one switched on and off again.
+ *   SCOPE       up to BAZ_MUSIC_FAST_M antennas (BAZ_MUSIC_E_UNSUPPORTED beyond), like the other modes.  Composes with peak mode, the
+ *               emitter-count mode, refinement and averaging; under smoothing it is forwarded to the inner context.
+ *   WHEN        set_power_mode takes effect for items submitted after it returns and is serialised against process*() like
+ *               set_peak_mode: a batch sees the old mode or the new one.  The previous mode stays in force after any error.
+ * last_powers: P of the entries of the LAST process*() call in call order ([item][slot]), at most `count` of them (a host-fed
+ * call cut into chunks, or a smoothing call, reports all its items); blocks until that call is done; returns how many were written, or
+ * < 0.  A call that ran with the mode off reports zeros.  The buffer behind it (8 n bytes per item) is allocated only by calls made with
+ * the mode on.  power_estimate needs no device: one R (m*m complex128, row-major, re / im interleaved) and `count` steering rows (m
+ * complex64 each) give `count` powers by the definition above, the degeneracy rule and the s -> P step being the kernel's own text;
+ * 1 <= m <= BAZ_MUSIC_MAX_M; BAZ_MUSIC_E_INVALID for m out of range or a NULL array with count > 0. */
+#define BAZ_MUSIC_POWER_PIVOT_FLOOR (1.0 / 1099511627776.0)   /* 2^-40 */
+BAZ_MUSIC_API int baz_music_set_power_mode(baz_music_ctx* ctx, int mode);
+BAZ_MUSIC_API int baz_music_get_power_mode(const baz_music_ctx* ctx, int* mode);
+BAZ_MUSIC_API int baz_music_last_powers(baz_music_ctx* ctx, double* out, uint32_t count);
+BAZ_MUSIC_API int baz_music_power_estimate(uint32_t m, const double* R_ri, const float* a_ri, uint32_t count, double* out);
 /* Statistic: how many (item, bin) values of the LAST process call were recomputed in the reference's literal form
  * ||G^H a||^2 because the projector form a^H Q a put them at or below ~m 1e-8 max||a||^2 (near-nulls of the noise
  * subspace, SNR >~ 55 dB); blocks until that call is done (a host-fed call cut into chunks reports their sum).
