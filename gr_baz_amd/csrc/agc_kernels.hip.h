@@ -60,11 +60,20 @@ __device__ __forceinline__ float2 agc_apply(const float2 x, const double gain)
     return make_float2((float)re, (float)im);
 }
 
+// fma(A, S1, S) for a map coefficient A = a^k and an earlier state or partial sum S1.  With a > 0 (apos) the exact a^k is
+// positive, so A * inf is inf even where the double A has underflowed to 0.0 -- fma(0, inf, .) would be NaN, while the
+// reference's envelope stays inf for good after an inf sample (.cc:82).  S1 is a sum of magnitudes, never -inf.  For a
+// finite or NaN S1 this is the plain fma, the same bits as ever.
+__device__ __forceinline__ double agc_map_fma(const double A, const double S1, const double S, const bool apos)
+{
+    return (apos && S1 == __builtin_inf()) ? S1 + S : fma(A, S1, S);
+}
+
 // (A2,S2) o (A1,S1): apply 1 first, then 2
-__device__ __forceinline__ void compose(double& A, double& S, const double A1, const double S1)
+__device__ __forceinline__ void compose(double& A, double& S, const double A1, const double S1, const bool apos)
 {
     // (A,S) := (A,S) o (A1,S1)
-    S = fma(A, S1, S);
+    S = agc_map_fma(A, S1, S, apos);
     A = A * A1;
 }
 
@@ -79,8 +88,11 @@ constexpr int AGC_CARRY_THREADS = 1024;
 __global__ __launch_bounds__(AGC_CARRY_THREADS) void agc_carry_kernel(const float2* __restrict__ in, uint64_t stride,
                                                                        const double2* __restrict__ chunk_pair,
                                                                        double* __restrict__ carry_in, uint32_t nchunks,
-                                                                       const double* __restrict__ env_state, int first)
+                                                                       const double* __restrict__ env_state, int first,
+                                                                       int apos_)
 {
+    const bool apos = apos_ != 0;          // a > 0: see agc_map_fma
+
     __shared__ double wA[AGC_CARRY_THREADS / 64], wS[AGC_CARRY_THREADS / 64];
     const uint32_t stream = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -98,27 +110,27 @@ __global__ __launch_bounds__(AGC_CARRY_THREADS) void agc_carry_kernel(const floa
     double A = 1.0, S = 0.0;
     for (uint32_t c = c0; c < c1; ++c) {
         const double2 p = cp[c];
-        S = fma(p.x, S, p.y);
+        S = agc_map_fma(p.x, S, p.y, apos);
         A *= p.x;
     }
     double Ai = A, Si = S;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         const double Ap = __shfl_up(Ai, d, 64), Sp = __shfl_up(Si, d, 64);
-        if (lane >= d) compose(Ai, Si, Ap, Sp);
+        if (lane >= d) compose(Ai, Si, Ap, Sp, apos);
     }
     if (lane == 63) { wA[wave] = Ai; wS[wave] = Si; }
     __syncthreads();
     double Ae = __shfl_up(Ai, 1, 64), Se = __shfl_up(Si, 1, 64);
     if (lane == 0) { Ae = 1.0; Se = 0.0; }
     double Aw = 1.0, Sw = 0.0;              // map of all earlier waves
-    for (int w = 0; w < wave; ++w) { const double a2 = wA[w], s2 = wS[w]; Sw = fma(a2, Sw, s2); Aw *= a2; }
-    compose(Ae, Se, Aw, Sw);                // thread-exclusive map of the whole block prefix
-    double e = fma(Ae, e0, Se);             // state entering this thread's slice
+    for (int w = 0; w < wave; ++w) { const double a2 = wA[w], s2 = wS[w]; Sw = agc_map_fma(a2, Sw, s2, apos); Aw *= a2; }
+    compose(Ae, Se, Aw, Sw, apos);          // thread-exclusive map of the whole block prefix
+    double e = agc_map_fma(Ae, e0, Se, apos);   // state entering this thread's slice
     for (uint32_t c = c0; c < c1; ++c) {
         ci[c] = e;
         const double2 p = cp[c];
-        e = fma(p.x, e, p.y);
+        e = agc_map_fma(p.x, e, p.y, apos);
     }
 }
 
@@ -298,7 +310,7 @@ __global__ __launch_bounds__(1024) void agc_tile_kernel(const float2* __restrict
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
             const double Ap = __shfl_up(Ai, d, 64), Sp = __shfl_up(Si, d, 64);
-            if (lane >= d) compose(Ai, Si, Ap, Sp);
+            if (lane >= d) compose(Ai, Si, Ap, Sp, P.a > 0.0);
         }
         if constexpr (MODE == 0) {
             if (lane == 63) chunk_pair[(size_t)stream * ntiles + t] = make_double2(Ai, Si);
@@ -306,7 +318,7 @@ __global__ __launch_bounds__(1024) void agc_tile_kernel(const float2* __restrict
         } else {
             double Ae = __shfl_up(Ai, 1, 64), Se = __shfl_up(Si, 1, 64);
             if (lane == 0) { Ae = 1.0; Se = 0.0; }
-            e = fma(Ae, carry, Se);                               // state entering this lane's run
+            e = agc_map_fma(Ae, carry, Se, P.a > 0.0);            // state entering this lane's run
 #pragma unroll
             for (int j = 0; j < AGC_IE; ++j) {
                 y[j] = make_float2(0.f, 0.f);

@@ -81,7 +81,7 @@ int process_device_locked(baz_agc_ctx* c, const void* d_in, uint64_t n, uint64_t
                        (const double*)nullptr, ntiles, (float2*)nullptr, (double*)nullptr, c->nstreams, (float*)nullptr,
                        (float*)nullptr);
     hipLaunchKernelGGL(agc_carry_kernel, dim3(c->nstreams), dim3(AGC_CARRY_THREADS), 0, c->stream, in, stride, c->d_pair,
-                       c->d_carry, ntiles, c->d_env, c->count == 0 ? 1 : 0);
+                       c->d_carry, ntiles, c->d_env, c->count == 0 ? 1 : 0, c->P.a > 0.0 ? 1 : 0);
     hipLaunchKernelGGL((agc_tile_kernel<2, true>), grid, block, 0, c->stream, in, n, stride, c->P, c->d_pair,
                        c->d_carry, ntiles, static_cast<float2*>(d_out), c->d_env, c->nstreams, static_cast<float*>(d_env),
                        static_cast<float*>(d_mul));
@@ -105,7 +105,7 @@ int process_device_interleaved_locked(baz_agc_ctx* c, const void* d_in, uint64_t
     hipLaunchKernelGGL((agc_tile_kernel<0>), dim3(ntiles), block, 0, c->stream, in, n, stride, c->P, c->d_pair,
                        (const double*)nullptr, ntiles, (float2*)nullptr, (double*)nullptr, c->nstreams);
     hipLaunchKernelGGL(agc_carry_kernel, dim3(c->nstreams), dim3(AGC_CARRY_THREADS), 0, c->stream, in, stride, c->d_pair, c->d_carry,
-                       ntiles, c->d_env, c->count == 0 ? 1 : 0);
+                       ntiles, c->d_env, c->count == 0 ? 1 : 0, c->P.a > 0.0 ? 1 : 0);
     hipLaunchKernelGGL((agc_tile_kernel<1>), dim3(ntiles), block, lds, c->stream, in, n, stride, c->P, c->d_pair,
                        c->d_carry, ntiles, static_cast<float2*>(d_items), c->d_env, c->nstreams);
     AGC_TRY(hipGetLastError());

@@ -86,10 +86,10 @@ __global__ __launch_bounds__(RS_BLOCK) void resamp_kernel(const float2* __restri
 // the phase chain over an LDS window of the ratio input (the other lanes of the workgroup only fetch that window) and
 // records (ii_o, imu_o) per output; the interpolation itself then runs in parallel from that table
 // (resamp_table_kernel).  A float ratio >= 2^-41 (24-bit significand: its last bit is >= 2^-64) and a phase with <= 64
-// fractional bits add exactly in 64.64 fixed point; that equals the reference's x87 sequence whenever the x87 sum
-// s = mu + inc is itself exact in its 64-bit significand -- always for ratios below 1, and for larger ones as long as
-// mu + inc needs no more than 64 significant bits (a ratio >= 1 pushes mu's last bits out: the two then differ by
-// < 2^-63 in mu, which moves imu only when mu * 128 sits that close to a rounding boundary).  Smaller ratios
+// fractional bits add exactly in 64.64 fixed point.  The reference's x87 sum s = mu + inc has a 64-bit significand: below 1
+// it holds every bit of that sum, from 1 up its k integer bits leave 64 - k for the fraction -- a ratio of 9000.25 pushes
+// the last 14 bits of mu out.  The walk rounds the fraction of such a sum the same way (to nearest, ties to even, carry
+// into the integer part), so ii and mu are the reference's, bit for bit, for every such ratio and phase.  Smaller ratios
 // (0 < r < 2^-41) are truncated to 2^-64 (the x87 sum rounds them instead).  The walk stops early -- fewer outputs, like a
 // short input -- at a ratio sample that is not a finite number in (0, 2^31]: zero, negative, NaN, inf (the reference
 // would stand still, walk backwards or index with garbage there); a call that STARTS on such a sample is an error
@@ -135,8 +135,15 @@ __global__ __launch_bounds__(256) void resamp_walk_kernel(const float* __restric
                 const double rd = (double)r;
                 const uint64_t ip = (uint64_t)rd;
                 const uint64_t fr = (uint64_t)((rd - (double)ip) * 18446744073709551616.0);   // exact from 2^-41 up (<= 24 significant bits), else truncated
-                const uint64_t nf = frac + fr;
-                ii += ip + (nf < frac ? 1u : 0u);                                      // s = mu + inc; ii += floor(s), .cc:209-213
+                uint64_t nf = frac + fr;
+                uint64_t step = ip + (nf < frac ? 1u : 0u);                            // s = mu + inc, .cc:209
+                if (step) {                                                            // s >= 1: 64 - k fraction bits survive the x87 sum
+                    const int k = 64 - __clzll((long long)step);
+                    const uint64_t unit = 1ull << k, rem = nf & (unit - 1u), half = unit >> 1;
+                    nf -= rem;
+                    if (rem > half || (rem == half && (nf & unit))) { nf += unit; if (nf == 0) ++step; }
+                }
+                ii += step;                                                            // ii += floor(s), .cc:210-213
                 frac = nf;                                                             // d_mu = s - floor(s)
             }
             s_ii = ii; s_frac = frac; s_o = o; s_last = last;

@@ -33,6 +33,30 @@ def close(a, b, rtol=1e-5):
     return bool(np.all(np.abs(a[fin] - b[fin]) <= rtol * np.maximum(np.abs(b[fin]), 1e-30) + 1e-37))
 
 
+def close_strict(a, b, rtol=1e-5):
+    """close() and, beyond it, what its isfinite masks cannot tell apart: the same NaN, +inf and -inf positions, and the
+    reference's sign bit wherever the reference is +0 or -0."""
+    a = np.ascontiguousarray(a); b = np.ascontiguousarray(b)
+    if np.iscomplexobj(a):
+        a = a.view(np.float32); b = b.view(np.float32)
+    if not close(a, b, rtol):
+        return False
+    zero = b == 0
+    return bool(np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(np.isposinf(a), np.isposinf(b))
+                and np.array_equal(np.isneginf(a), np.isneginf(b))
+                and np.array_equal(a[zero] == 0, b[zero] == 0) and np.array_equal(np.signbit(a[zero]), np.signbit(b[zero])))
+
+
+def ulp_flips(got, ref):
+    """(largest difference of the float32 bit patterns, number of differing floats, floats compared) where ref is finite."""
+    got = np.ascontiguousarray(got); ref = np.ascontiguousarray(ref)
+    if np.iscomplexobj(ref):
+        got = got.view(np.float32); ref = ref.view(np.float32)
+    fin = np.isfinite(ref)
+    u = np.abs(got.view(np.int32).astype(np.int64) - ref.view(np.int32).astype(np.int64))[fin]
+    return (int(u.max()) if u.size else 0), int(np.count_nonzero(u)), int(u.size)
+
+
 def run_calls(blk, x, calls):
     outs, envs, muls = [], [], []
     pos = 0
@@ -225,3 +249,240 @@ def test_fast_and_general_tile_paths_agree(gpu_device, monkeypatch):
     for s in range(S):
         o, e, m = ar.Agc(1e-3, 2.0).work(x[s])
         assert close(outs["1"][1][s], e) and close(outs["1"][0][s].view(np.complex64), o)
+
+
+# --------------------------------------------------------------------------- the carry scan past its first level
+# agc_carry_kernel: 1,024 threads per stream; thread t composes a slice of per = ceil(ntiles / 1024) tile maps, a 64-lane
+# wave scan, then the 16 wave totals.  Shapes at the thresholds: one wave exactly, a second wave, several waves, per = 1
+# with every thread busy, per = 2, per = 3 with a ragged tail.
+SCAN_SHAPES = [256 * 64, 256 * 64 + 1, 256 * 200 + 77, 256 * 1024, 256 * 1024 + 1, 256 * 2049 + 77]
+SCAN_REFERENCE = 1.5
+_scan_cache = {}
+
+
+def scan_input(S, n):
+    """Noise whose amplitude changes from tile to tile (2^0 .. 2^6, cycling, shifted per stream) on a slow ramp: a carry
+    taken from the wrong tile, wave or slice moves the envelope by percent.  Tiles 70-72 and 1023-1025 are zero (general-path
+    tiles between fast-path ones; short enough for the envelope to stay an ordinary number)."""
+    key = ("x", S, n)
+    if key not in _scan_cache:
+        rng = np.random.default_rng(1000 + S)
+        t = np.arange(n)
+        x = np.empty((S, n), np.complex64)
+        for s in range(S):
+            amp = np.ldexp(0.5 + t / n, ((t // 256 + s) % 7).astype(np.int32))
+            x[s] = ((rng.standard_normal(n) + 1j * rng.standard_normal(n)) * amp).astype(np.complex64)
+        x[:, 256 * 70:256 * 73] = 0
+        x[:, 256 * 1023:256 * 1026] = 0
+        x.setflags(write=False)
+        _scan_cache[key] = x
+    return _scan_cache[key]
+
+
+def scan_oracle(S, n, rate):
+    """(out, env, mul) of the sequential loop, one oracle instance per stream; computed once per shape."""
+    key = ("ref", S, n, rate)
+    if key not in _scan_cache:
+        x = scan_input(S, n)
+        r = [ar.Agc(rate, SCAN_REFERENCE).work(x[s]) for s in range(S)]
+        ref = tuple(np.stack([q[i] for q in r]) for i in range(3))
+        for a in ref:
+            a.setflags(write=False)
+        _scan_cache[key] = ref
+    return _scan_cache[key]
+
+
+def hip_planar(blk, x, dev, calls=None):
+    """process_device with the env and mul ports over the call lengths `calls` (default: one call); row stride = n."""
+    import torch
+    S, n = x.shape
+    d_in = torch.from_numpy(np.array(x).view(np.float32)).to(dev)        # (a copy: the cached inputs are read-only)
+    d_out = torch.zeros_like(d_in)
+    d_env = torch.zeros(S, n, dtype=torch.float32, device=dev)
+    d_mul = torch.zeros_like(d_env)
+    torch.cuda.synchronize()                       # the engine runs on its own stream: fills first
+    lo = 0
+    for c in (calls or (n,)):
+        blk.process_device(d_in.data_ptr() + lo * 8, c, n, d_out.data_ptr() + lo * 8, d_env.data_ptr() + lo * 4,
+                           d_mul.data_ptr() + lo * 4)
+        lo += c
+    assert lo == n
+    blk.sync()
+    return d_out.cpu().numpy().view(np.complex64), d_env.cpu().numpy(), d_mul.cpu().numpy()
+
+
+def hip_interleaved(blk, x, dev):
+    """process_device_interleaved: items[t * S + s] -> (S, n) complex64."""
+    import torch
+    S, n = x.shape
+    d_in = torch.from_numpy(np.array(x).view(np.float32)).to(dev)        # (a copy: the cached inputs are read-only)
+    d_items = torch.zeros(n, S, 2, dtype=torch.float32, device=dev)
+    torch.cuda.synchronize()
+    blk.process_device_interleaved(d_in.data_ptr(), n, n, d_items.data_ptr())
+    blk.sync()
+    return np.ascontiguousarray(d_items.cpu().numpy().transpose(1, 0, 2)).view(np.complex64).reshape(S, n)
+
+
+def assert_agc_parity(what, got, ref):
+    """The project's bounds (test_hip_agc_matches_golden): 1e-5 relative, and on the float32 bit patterns at most 1 ulp in
+    at most 1e-5 of the floats.  Prints the measured flip share first."""
+    for name, g, r in zip(("out", "env", "mul"), got, ref):
+        if g is None:
+            continue
+        worst, flips, size = ulp_flips(g, r)
+        print("agc flips %s %s: %d of %d floats (share %.2e), largest %d ulp" % (what, name, flips, size, flips / max(size, 1), worst))
+        assert close(g, r, rtol=1e-5), (what, name)
+        assert worst <= 1 and flips <= max(1, 1e-5 * size), (what, name, worst, flips, size)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rate", [1e-4, 1e-2])
+@pytest.mark.parametrize("n", SCAN_SHAPES)
+def test_hip_agc_carry_scan_levels_planar(n, rate, gpu_device):
+    """process_device with env and mul, S = 2, against the sequential loop.  At rate 1e-2 the map coefficient A = a^(256 k)
+    underflows to 0 on finite data within the 2,050-tile shape: legitimate, and without effect on the result."""
+    from gr_baz_amd import agc
+    S = 2
+    x = scan_input(S, n)
+    with agc.Agc(rate, SCAN_REFERENCE, nstreams=S) as blk:
+        got = hip_planar(blk, x, gpu_device)
+        assert blk.count == n
+    assert_agc_parity("planar S=%d n=%d rate=%g" % (S, n, rate), got, scan_oracle(S, n, rate))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rate", [1e-4, 1e-2])
+@pytest.mark.parametrize("n", [256 * 64 + 1, 256 * 1024 + 1])
+@pytest.mark.parametrize("S", [16, 5])
+def test_hip_agc_carry_scan_levels_interleaved(S, n, rate, gpu_device):
+    """process_device_interleaved (the form the benchmark's chain runs): S = 16 takes the float4 write-out, S = 5 the
+    scalar one; 65 tiles (a second wave) and 1,025 tiles (per = 2)."""
+    from gr_baz_amd import agc
+    x = scan_input(S, n)
+    with agc.Agc(rate, SCAN_REFERENCE, nstreams=S) as blk:
+        out = hip_interleaved(blk, x, gpu_device)
+        assert blk.count == n
+    assert_agc_parity("interleaved S=%d n=%d rate=%g" % (S, n, rate), (out, None, None), scan_oracle(S, n, rate))
+
+
+@pytest.mark.gpu
+def test_hip_agc_carry_scan_levels_general_tile_path(gpu_device, monkeypatch):
+    """BAZ_AGC_FAST=0: every tile map comes from the general path's (A, S) pair scan and feeds the same carry kernel
+    (1,025 tiles: waves and per = 2), both output forms."""
+    from gr_baz_amd import agc
+    monkeypatch.setenv("BAZ_AGC_FAST", "0")
+    S, n, rate = 2, 256 * 1024 + 1, 1e-4
+    x = scan_input(S, n)
+    with agc.Agc(rate, SCAN_REFERENCE, nstreams=S) as blk:
+        got = hip_planar(blk, x, gpu_device)
+        blk.reset()
+        items = hip_interleaved(blk, x, gpu_device)
+    ref = scan_oracle(S, n, rate)
+    assert_agc_parity("general path planar n=%d" % n, got, ref)
+    assert_agc_parity("general path interleaved n=%d" % n, (items, None, None), ref)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path", ["host", "device"])
+def test_hip_agc_stateful_calls_across_scan_levels(path, gpu_device):
+    """One context, calls of 300, 256*1100 + 5, 17,000 and 1 samples: the second call regrows the per-tile tables while the
+    first call's launches may still be in flight and runs per = 2; the third enters with the state a multi-level call left."""
+    from gr_baz_amd import agc
+    calls = (300, 256 * 1100 + 5, 17000, 1)
+    n, rate = sum(calls), 1e-4
+    S = 1 if path == "host" else 2
+    x = scan_input(S, n)
+    ref = [run_calls(ar.Agc(rate, SCAN_REFERENCE), x[s], calls) for s in range(S)]
+    ref = tuple(np.stack([q[i] for q in ref]) for i in range(3))
+    with agc.Agc(rate, SCAN_REFERENCE, nstreams=S) as blk:
+        if path == "host":
+            got = tuple(a[None, :] for a in run_calls(blk, x[0], calls))
+        else:
+            got = hip_planar(blk, x, gpu_device, calls)
+        assert blk.count == n
+    assert_agc_parity("stateful %s path" % path, got, ref)
+
+
+# --------------------------------------------------------------------------- non-finite samples
+# The reference (oracle/agc_ref.c, .cc:79-100): an inf sample makes env = inf for good, so gain = 0 and every later
+# finite sample comes out as (signed) 0; a NaN sample makes everything after it NaN.  Stream 0 carries the special
+# sample, stream 1 is finite throughout (nothing may leak across streams).
+def nonfinite_case(case):
+    """-> (rate, [x of call 0, x of call 1, ...]) each x of shape (2, n)."""
+    rng = np.random.default_rng(77)
+    noise = lambda n: ((rng.standard_normal((2, n)) + 1j * rng.standard_normal((2, n))) * 0.7).astype(np.complex64)
+    if case == "a_inf_rate0.5":
+        x = noise(256 * 12); x[0, 10] = np.inf
+        return 0.5, [x]
+    if case == "b_neg_inf_imag_rate1e-2":
+        x = noise(256 * 400); x[0, 256 * 3 + 9] = complex(0, -np.inf)
+        return 1e-2, [x]
+    if case == "c_inf_state_enters_call":
+        x0 = noise(600); x0[0, 5] = np.inf
+        return 0.5, [x0, noise(256 * 70)]
+    if case == "d_inf_first_sample":
+        x = noise(256 * 12); x[0, 0] = np.inf
+        return 0.5, [x]
+    if case == "e_nan":
+        x = noise(256 * 12); x[0, 256 * 2 + 100] = complex(np.nan, 0.25)
+        return 0.5, [x]
+    raise KeyError(case)
+
+
+def nonfinite_run(blk, form, xs, dev):
+    """-> per call (out, env | None, mul | None), each (2, n)."""
+    if form == "planar":
+        return [blk.work(x) for x in xs]
+    return [(hip_interleaved(blk, x, dev), None, None) for x in xs]
+
+
+def nonfinite_oracle(rate, xs):
+    orc = [ar.Agc(rate, 1.0) for _ in range(2)]
+    res = []
+    for x in xs:
+        r = [orc[s].work(x[s]) for s in range(2)]
+        res.append(tuple(np.stack([q[i] for q in r]) for i in range(3)))
+    return res
+
+
+def assert_strict(what, got, ref):
+    for name, g, r in zip(("out", "env", "mul"), got, ref):
+        if g is not None:
+            for s in range(r.shape[0]):
+                assert close_strict(g[s], r[s]), (what, name, "stream %d" % s)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", ["planar", "interleaved"])
+@pytest.mark.parametrize("case", ["a_inf_rate0.5", "b_neg_inf_imag_rate1e-2", "c_inf_state_enters_call",
+                                  "d_inf_first_sample", "e_nan"])
+def test_hip_agc_non_finite_samples_behave_like_the_reference(case, form, gpu_device):
+    from gr_baz_amd import agc
+    rate, xs = nonfinite_case(case)
+    ref = nonfinite_oracle(rate, xs)
+    if case == "a_inf_rate0.5":       # what the oracle itself says: env = inf, mul = 0, outputs exactly 0, one NaN float
+        o, e, m = ref[0]
+        assert np.all(np.isposinf(e[0, 10:])) and np.all(m[0, 10:] == 0) and np.all(o[0, 11:] == 0)
+        assert np.count_nonzero(np.isnan(o[0].view(np.float32))) == 1 and np.isnan(o[0, 10].real)
+    with agc.Agc(rate, 1.0, nstreams=2) as blk:
+        got = nonfinite_run(blk, form, xs, gpu_device)
+        assert blk.count == sum(x.shape[1] for x in xs)
+    for i, (g, r) in enumerate(zip(got, ref)):
+        assert_strict("%s %s call %d" % (case, form, i), g, r)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", ["planar", "interleaved"])
+def test_hip_agc_reset_revives_a_stream_after_an_inf_sample(form, gpu_device):
+    from gr_baz_amd import agc
+    rate, xs = nonfinite_case("a_inf_rate0.5")
+    fresh = np.ascontiguousarray(xs[0][:, 1000:])            # finite
+    with agc.Agc(rate, 1.0, nstreams=2) as blk:
+        got = nonfinite_run(blk, form, xs, gpu_device)
+        assert_strict("before reset, " + form, got[0], nonfinite_oracle(rate, xs)[0])
+        blk.reset()
+        assert blk.count == 0
+        got = nonfinite_run(blk, form, [fresh], gpu_device)
+    ref = nonfinite_oracle(rate, [fresh])                    # fresh oracle instances
+    assert np.all(np.isfinite(ref[0][1])) and np.all(ref[0][2] > 0)
+    assert_strict("after reset, " + form, got[0], ref[0])

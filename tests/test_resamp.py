@@ -348,6 +348,129 @@ def test_hip_two_input_branch_stops_at_the_end_of_the_input_and_at_unusable_rati
             assert n == 1000 and ko == k and np.array_equal(got[s].view(np.uint32), o.view(np.uint32))
 
 
+# ---- the two-input walk across its LDS windows (resamp_walk_kernel, RS_WALK_WIN = 8192 ratio samples per window) ----
+# The oracle does not know the input length: it always gets the full buffers and the output count expected of it.
+WALK_WIN = 8192
+
+
+def walk_data(S, L, seed):
+    rng = np.random.default_rng(seed)
+    return (rng.standard_normal((S, L)) + 1j * rng.standard_normal((S, L))).astype(np.complex64)
+
+
+def assert_walk_calls_equal_oracle(x, ratio, phase, calls):
+    """Host path, stateful: outputs bit for bit, consumed count, mu, ratio state after every call.  -> consumed per call."""
+    from gr_baz_amd import resamp
+    S = x.shape[0]
+    consumed = []
+    with resamp.Resampler(phase, 1.0, nstreams=S) as blk:
+        oracles = [rr.Resampler(phase, 1.0) for _ in range(S)]
+        pos = 0
+        for c in calls:
+            out, k = blk.work(x[:, pos:], c, rr=ratio[pos:])
+            assert out.shape == (S, c)
+            for s in range(S):
+                o, ks = oracles[s].work(x[s, pos:], c, rr=ratio[pos:])
+                assert ks == k and np.array_equal(out[s].view(np.uint32), o.view(np.uint32))
+            assert blk.mu() == oracles[0].mu() and blk.resamp_ratio() == oracles[0].resamp_ratio()
+            pos += k
+            consumed.append(k)
+        assert blk.phase_exact()
+    return consumed
+
+
+@pytest.mark.gpu
+def test_hip_two_input_walk_reloads_its_window_and_carries_the_state_on(gpu_device):
+    """Ratios in [0.9, 1.6]: the first call consumes about 17,400 samples (three windows: two reloads, each handing over the
+    input index, the phase, the output count and the last ratio); the second call starts from that state."""
+    S, calls = 3, (14000, 3000)
+    L = int(sum(calls) * 1.6) + 64
+    ratio = np.random.default_rng(78).uniform(0.9, 1.6, L).astype(np.float32)
+    consumed = assert_walk_calls_equal_oracle(walk_data(S, L, 79), ratio, 0.37, calls)
+    assert 2 * WALK_WIN < consumed[0] <= 3 * WALK_WIN
+
+
+@pytest.mark.gpu
+def test_hip_two_input_walk_step_lands_exactly_on_the_window_end(gpu_device):
+    """Ratio 1.0, phase 0: the step out of input sample 8191 lands on 8192 = the end of the first window."""
+    n = WALK_WIN + 300
+    L = n + 64
+    consumed = assert_walk_calls_equal_oracle(walk_data(1, L, 80), np.ones(L, np.float32), 0.0, (n,))
+    assert consumed == [n]
+
+
+@pytest.mark.gpu
+def test_hip_two_input_walk_two_outputs_per_input_sample(gpu_device):
+    """Ratio 0.5: the first window ends at output 16,384 with the phase back at 0."""
+    n = 20000
+    L = n // 2 + 64
+    consumed = assert_walk_calls_equal_oracle(walk_data(1, L, 81), np.full(L, 0.5, np.float32), 0.0, (n,))
+    assert consumed == [n // 2] and n // 2 > WALK_WIN
+
+
+@pytest.mark.gpu
+def test_hip_two_input_walk_steps_longer_than_a_window(gpu_device):
+    """Ratios near 1 with a 9000.25 at every 1000th and a 4000.5 at every 1000th + 500 sample: steps that jump over a whole
+    window, or land deep inside the next one.  The x87 sum mu + 9000.25 keeps 50 fraction bits: the last bits of the phase
+    0.3 (a double: bits down to 2^-54) are rounded away there, and mu() has to show the same."""
+    L, n = 200000, 5000
+    ratio = np.random.default_rng(82).uniform(0.9, 1.1, L).astype(np.float32)
+    ratio[::1000] = 9000.25
+    ratio[500::1000] = 4000.5
+    consumed = assert_walk_calls_equal_oracle(walk_data(1, L, 83), ratio, 0.3, (n,))
+    assert consumed[0] > 10 * WALK_WIN and consumed[0] + 8 <= L          # long jumps were taken; the input did not run out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ninput", [8192, 8195, 8199, 8200, 8201])
+def test_hip_two_input_walk_input_ends_in_the_second_window(ninput, gpu_device):
+    """Ratio 1.0: outputs exist while 8 samples from the input index on are there, i.e. exactly ninput - 7 of them --
+    whether the input ends with the first window, less than 8 samples into the second one, or a little later."""
+    import torch
+    from gr_baz_amd import resamp
+    L = 8300
+    x = walk_data(2, L, 84)
+    ratio = np.ones(L, np.float32)
+    want = [rr.Resampler(0.0, 1.0).work(x[s], ninput - 7, rr=ratio) for s in range(2)]
+    with resamp.Resampler(0.0, 1.0, nstreams=2) as blk:
+        out, k = blk.work(x[:, :ninput], 20000, rr=ratio[:ninput])
+        assert out.shape == (2, ninput - 7)
+        for s in range(2):
+            assert k == want[s][1] == ninput - 7 and np.array_equal(out[s].view(np.uint32), want[s][0].view(np.uint32))
+        assert blk.mu() == 0.0 and blk.resamp_ratio() == 1.0 and blk.phase_exact()
+    if ninput == 8200:                                        # device buffers: row stride L > ninput
+        with resamp.Resampler(0.0, 1.0, nstreams=2) as blk:
+            xd = torch.from_numpy(x.view(np.float32)).to(gpu_device)
+            rd = torch.from_numpy(ratio).to(gpu_device)
+            od = torch.zeros(2, 2 * 20000, dtype=torch.float32, device=gpu_device)
+            torch.cuda.synchronize()
+            n, k = blk.process2_device(xd.data_ptr(), L, ninput, rd.data_ptr(), od.data_ptr(), 20000, 20000)
+            got = od.cpu().numpy().view(np.complex64)
+            assert n == ninput - 7 and k == ninput - 7 and blk.mu() == 0.0 and blk.resamp_ratio() == 1.0
+            for s in range(2):
+                assert np.array_equal(got[s, :n].view(np.uint32), want[s][0].view(np.uint32))
+                assert not got[s, n:].any()                   # nothing written past the outputs produced
+
+
+@pytest.mark.gpu
+def test_hip_two_input_walk_stops_at_an_unusable_ratio_in_the_second_window(gpu_device):
+    """ratio[9000] = NaN: output 9000 is still delivered (it is formed before the ratio is read), 9,000 samples are
+    consumed, and the call that starts ON the unusable sample is an error -- the rule of the first-window test above."""
+    from gr_baz_amd import resamp
+    L = 12000
+    x = walk_data(1, L, 85)[0]
+    ratio = np.ones(L, np.float32)
+    bad = ratio.copy()
+    bad[9000] = np.nan
+    with resamp.Resampler(0.0, 1.0) as blk:
+        out, k = blk.work(x, 11000, rr=bad)
+        o, _ = rr.Resampler(0.0, 1.0).work(x, 9001, rr=ratio)
+        assert out.shape[0] == 9001 and k == 9000 and np.array_equal(out.view(np.uint32), o.view(np.uint32))
+        assert blk.mu() == 0.0 and blk.resamp_ratio() == 1.0 and blk.phase_exact()
+        with pytest.raises(resamp.ResampError):
+            blk.work(x[9000:], 500, rr=bad[9000:])
+
+
 @pytest.mark.gpu
 def test_hip_rejects_what_the_reference_rejects(gpu_device):
     from gr_baz_amd import resamp
