@@ -799,6 +799,9 @@ __global__ __launch_bounds__(64) void evd_sub_kernel(const double2* __restrict__
     bool ok = orth(z, y) && !(poison != poison);
     bool conv = false;
     double d2prev = __builtin_huge_val();
+    double tl[P];
+#pragma unroll
+    for (int c = 0; c < P; ++c) tl[c] = 0.0;
     for (int it = 0; it < MAX_IT; ++it) {
         wave_lds_fence();
 #pragma unroll
@@ -814,6 +817,9 @@ __global__ __launch_bounds__(64) void evd_sub_kernel(const double2* __restrict__
                 z[c].x += Rrow[k].x * yk.x - Rrow[k].y * yk.y;
                 z[c].y += Rrow[k].x * yk.y + Rrow[k].y * yk.x;
             }
+        double tn[P];                                       // this row's terms of diag(Y^H R Y), for the dominance check
+#pragma unroll
+        for (int c = 0; c < P; ++c) tn[c] = z[c].x * y[c].x + z[c].y * y[c].y;
         double2 yn[P];
         const bool ok2 = orth(z, yn);
         // D = Y' - Y (Y^H Y'): the part of the new basis outside the old subspace
@@ -834,12 +840,32 @@ __global__ __launch_bounds__(64) void evd_sub_kernel(const double2* __restrict__
         if (!conv && ok) {                                  // (a frozen or failed item keeps its y)
             ok = ok2 && (d2 == d2);
 #pragma unroll
-            for (int c = 0; c < P; ++c) y[c] = yn[c];
+            for (int c = 0; c < P; ++c) { y[c] = yn[c]; tl[c] = tn[c]; }
             if (ok && d2 <= TOL2) conv = true;
             else if (it >= 2 && d2 > 100.0 * TOL2 && d2 > BAIL2 * d2prev) ok = false;   // too slow: the Jacobi is cheaper
             d2prev = d2;
         }
         if (__all(conv || !ok || !item_ok)) break;
+    }
+    // ---- dominance check.  A basis that stopped moving spans AN invariant subspace: R Y = Y Theta.  It is the dominant one
+    // only if the start had a component along every dominant eigenvector, and the start is columns of R: exact zeros in R
+    // (an antenna uncorrelated with the rest, a diagonal or block-diagonal R) can keep it out.  The deflated matrix
+    // R - Y Theta Y^H has the diagonal r_j = R_jj - sum_c Re(conj(y_c[j]) (R y_c)[j]) and its largest eigenvalue is
+    // >= max_j r_j, so max_j r_j > min_c Theta_cc (>= Theta's smallest eigenvalue) proves that an eigenvalue outside Y beats
+    // one inside: the item goes to the Jacobi.  A correctly converged item has max_j r_j <= lambda_{n+1} < lambda_n <=
+    // min_c Theta_cc and keeps its y, bit for bit.  tl = this row's terms of Y^H R Y from the step that converged (its R Y
+    // and the basis it started from, which the new one equals to 4e-15).  Necessary, not sufficient: DESIGN.md 2.1.
+    if (__any(conv && item_ok)) {
+        double rj = 0.0, thmin = __builtin_huge_val();
+#pragma unroll
+        for (int k = 0; k < M; ++k) rj = (k == jc) ? Rrow[k].x : rj;
+#pragma unroll
+        for (int c = 0; c < P; ++c) {
+            thmin = fmin(thmin, group_allsum<GS>(tl[c]));
+            rj -= tl[c];
+        }
+        const double rmax = group_allmax<GS>(row ? rj : -__builtin_huge_val());
+        if (rmax > thmin) conv = false;
     }
     if (item_ok && j == 0) redo[item] = conv ? 0 : 1;
     if (!__any(conv && item_ok)) return;

@@ -539,6 +539,9 @@ __global__ __launch_bounds__(64) void sub_wide_kernel(const double2* __restrict_
     bool ok = orth(z, y) && !(poison != poison);
     bool conv = false;
     double d2prev = __builtin_huge_val();
+    double tl[P];
+#pragma unroll
+    for (int c = 0; c < P; ++c) tl[c] = 0.0;
     for (int it = 0; it < MAX_IT && ok && !conv; ++it) {   // (one item per wave: the conditions are wave-uniform)
         bazmusic::wave_lds_fence();
 #pragma unroll
@@ -557,6 +560,8 @@ __global__ __launch_bounds__(64) void sub_wide_kernel(const double2* __restrict_
                 }
             }
         }
+#pragma unroll
+        for (int c = 0; c < P; ++c) tl[c] = z[c].x * y[c].x + z[c].y * y[c].y;   // this row's terms of diag(Y^H R Y)
         double2 yn[P];
         const bool ok2 = orth(z, yn);
         double dloc = 0.0;
@@ -579,6 +584,17 @@ __global__ __launch_bounds__(64) void sub_wide_kernel(const double2* __restrict_
         if (ok && d2 <= TOL2) conv = true;
         else if (it >= 2 && d2 > 100.0 * TOL2 && d2 > BAIL2 * d2prev) ok = false;
         d2prev = d2;
+    }
+    if (conv) {
+        // dominance check, as evd_sub_kernel: max_j r_j of the deflated matrix's diagonal against min_c Theta_cc
+        double rj = row ? elem((uint32_t)j).x : 0.0, thmin = __builtin_huge_val();
+#pragma unroll
+        for (int c = 0; c < P; ++c) {
+            thmin = fmin(thmin, wave_allsum(tl[c]));
+            rj -= tl[c];
+        }
+        const double rmax = wave_allmax(row ? rj : -__builtin_huge_val());
+        if (rmax > thmin) conv = false;
     }
     if (j == 0) redo[item] = conv ? 0 : 1;
     if (!conv) return;
