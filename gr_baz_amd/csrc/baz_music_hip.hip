@@ -242,6 +242,7 @@ struct baz_music_ctx {
     int sub_evd = 1;               // signal subspace by orthogonal iteration where n <= 4 (run-time-m kernels: n <= 8) (lab: BAZ_MUSIC_SUB_EVD=0)
     int fused_covevd = 0;          // m = 4, K % 256 == 0: covariance + EVD in one kernel (BAZ_MUSIC_FUSE=0: lab, two kernels)
     uint32_t covevd_blocks = 512u; // grid of cov4_evd_kernel: the workgroups resident at once (2 per CU)
+    uint32_t covevd_park = 0;      // tasks a wave of cov4_evd_kernel holds in registers before it rotates: 0 = one rotation phase per task (shipped); lab (BAZ_MUSIC_COVEVD_DEFER=1): COVEVD_PARK
     int covevd_task_items = 0;     // lab (BAZ_MUSIC_COVEVD_TASK_ITEMS = 64 / 32 / 16): items per wave task of cov4_evd_kernel, 0 = by batch size
     uint32_t cov4_resident_blocks = 256u;        // grid of cov4_x4_kernel (persistent waves): one workgroup per CU
     // coarse-gated scan (scan_coarse_kernels.hip.h): m <= 8, spectrum port not wired
@@ -923,12 +924,12 @@ int launch_covevd(baz_music_ctx* c, const float* d_in, uint32_t batch, double* d
         const int ro = order_args(c, batch, oa);
         if (ro) return ro;
         hipLaunchKernelGGL(cov4_evd_order_kernel, dim3(blocks), dim3(256), 0, c->stream, d_in, dQ, dG, d_R_dbg, batch, c->K, c->n,
-                           qstride, ti, oa);
+                           qstride, ti, c->covevd_park, oa);
         HIP_TRY(c, hipGetLastError());
         return BAZ_MUSIC_OK;
     }
     hipLaunchKernelGGL(cov4_evd_kernel, dim3(blocks), dim3(256), 0, c->stream, d_in, dQ, dG, d_R_dbg, batch, c->K, c->n,
-                       qstride, ti);
+                       qstride, ti, c->covevd_park);
     HIP_TRY(c, hipGetLastError());
     return BAZ_MUSIC_OK;
 }
@@ -2762,6 +2763,10 @@ int baz_music_create(baz_music_ctx** out, uint32_t m, uint32_t n, uint32_t nsamp
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cov4_evd_kernel, 256, 0) == hipSuccess && per_cu > 0)
                 c->covevd_blocks = (uint32_t)per_cu * (uint32_t)std::max(1, prop.multiProcessorCount);
             else (void)hipGetLastError();
+            // lab: a smaller grid gives a wave several tasks at a test's batch size (else only from 131,073 items on)
+            if (const char* v = BAZ_LAB_ENV("BAZ_MUSIC_COVEVD_BLOCKS")) { if (atoi(v) > 0) c->covevd_blocks = std::min(c->covevd_blocks, (uint32_t)atoi(v)); }
+            // lab: 1 = the deferred rotation (measured: no gain in a step's time that clears the run-to-run spread, profiles/r06_covevd_deferred.txt)
+            if (const char* v = BAZ_LAB_ENV("BAZ_MUSIC_COVEVD_DEFER")) c->covevd_park = atoi(v) > 0 ? (uint32_t)COVEVD_PARK : 0u;
         }
         if (const char* v = BAZ_LAB_ENV("BAZ_MUSIC_SIG_SCAN")) c->sig_scan = atoi(v);                  // lab / tests
         if (const char* v = getenv("BAZ_MUSIC_COARSE")) c->coarse = atoi(v);                      // A/B, tests

@@ -5,18 +5,26 @@
 __global__ __launch_bounds__(256) void cov4_evd_order_kernel(const float* __restrict__ in, double* __restrict__ Qs,
                                                              double* __restrict__ Gs, double2* __restrict__ Rdbg,
                                                              uint32_t batch, uint32_t K, uint32_t n, uint32_t qstride,
-                                                             uint32_t task_items, const OrderArgs oa)
+                                                             uint32_t task_items, uint32_t park, const OrderArgs oa)
 {
 #else
 __global__ __launch_bounds__(256) void cov4_evd_kernel(const float* __restrict__ in, double* __restrict__ Qs,
                                                        double* __restrict__ Gs, double2* __restrict__ Rdbg,
                                                        uint32_t batch, uint32_t K, uint32_t n, uint32_t qstride,
-                                                       uint32_t task_items = 64)
+                                                       uint32_t task_items, uint32_t park)
 {
 #endif
     // task_items (64, 32 or 16; round 5): items per wave task.  64 fills the lane-per-item EVD; a SMALL batch -- a host-fed work() call of
     // 1,024 items is 16 tasks of 64 = 16 waves with 8 KiB in flight each, too little to keep a PCIe link (or HBM) busy -- is cut into more,
     // shorter tasks (the EVD then runs on fewer lanes: its latency is what it was).  Items are independent: no result depends on it.
+    //
+    // park (<= COVEVD_PARK; deferred rotation, lab: BAZ_MUSIC_COVEVD_DEFER=1): how many streamed tasks a wave may HOLD -- each lane its
+    // item's R, 16 doubles in registers -- while it goes straight on to its next task.  The rotation passes of the held tasks and of
+    // the task still in rtab then run back to back where the wave's work ends (or where the held set is full), so a wave with T tasks
+    // stops its read stream ceil(T / (park + 1)) times instead of T times.  0 = one rotation phase per task: what the product launches
+    // (the deferred form gained nothing that clears a step's spread, music_kernels.hip.h 2a).  Only the globally last task can be
+    // short, and it is always some wave's last task: a held task is therefore always full (task_items items).  Same function on the
+    // same values: no result depends on park.
     constexpr int RSD = 34;                       // see cov4_x4_kernel
     constexpr int RING = 8;                       // chunk loads in flight per wave (8 KiB)
     __shared__ double stage[4][2][8 * RSD];       // per wave, double-buffered
@@ -39,11 +47,24 @@ __global__ __launch_bounds__(256) void cov4_evd_kernel(const float* __restrict__
     // pair (a < b) -> 4 + 2p (re), 5 + 2p (im), p = index of (a, b) in (0,1)(0,2)(0,3)(1,2)(1,3)(2,3)
     const int ea = (lane >> 2) & 3, eb = lane & 3;
     const int pidx = (ea == 0) ? eb - 1 : (ea == 1 ? eb + 1 : 5);
+    // getR of evd_project_lane over 16 values in rtab's slot order
+    auto slotR = [](auto slot, int i, int j) -> double2 {
+        if (i == j) return make_double2(slot(i), 0.0);
+        const int lo = i < j ? i : j, hi2 = i < j ? j : i;
+        const int p = (lo == 0) ? hi2 - 1 : (lo == 1 ? hi2 + 1 : 5);
+        const double re = slot(4 + 2 * p), im = slot(5 + 2 * p);
+        return make_double2(re, i < j ? im : -im);
+    };
+    auto rotate = [&](auto getR, const bool valid, const uint32_t item) {
+#if BAZ_EVD_ORDER
+        evd_project_lane<4, decltype(getR), true>(getR, valid, item, n, qstride, Qs, Gs, oa);
+#else
+        evd_project_lane<4>(getR, valid, item, n, qstride, Qs, Gs);
+#endif
+    };
 
-    for (uint32_t task = blockIdx.x * 4 + wave; task < ntasks; task += tstride) {
-        __builtin_amdgcn_s_setprio(3);
-        const uint32_t item0 = task * task_items;
-        const uint32_t nit = (batch - item0 < task_items) ? batch - item0 : task_items;
+    // streams one task: the covariances of its nit items into the wave's rtab (and the Rdbg tap)
+    auto stream = [&](const uint32_t item0, const uint32_t nit) {
         // the stream of this task: nit items x chunks, contiguous in HBM; ring slot u holds the chunks q = u (mod 8)
         const v4f32* __restrict__ src = reinterpret_cast<const v4f32*>(in + (size_t)item0 * K * 8) + lane;
         const uint32_t total = nit * chunks;                 // multiple of 8
@@ -101,23 +122,49 @@ __global__ __launch_bounds__(256) void cov4_evd_kernel(const float* __restrict__
             }
             wave_lds_fence();
         }
-        // EVD of the task's items, one per lane (lanes beyond nit redo the last item and write nothing), at low priority
-        __builtin_amdgcn_s_setprio(0);
-        {
-            const int li = ((uint32_t)lane < nit) ? lane : (int)nit - 1;
-            auto getR = [&](int i, int j) -> double2 {
-                if (i == j) return make_double2(rt[i][li], 0.0);
-                const int lo = i < j ? i : j, hi2 = i < j ? j : i;
-                const int p = (lo == 0) ? hi2 - 1 : (lo == 1 ? hi2 + 1 : 5);
-                const double re = rt[4 + 2 * p][li], im = rt[5 + 2 * p][li];
-                return make_double2(re, i < j ? im : -im);
-            };
-#if BAZ_EVD_ORDER
-            evd_project_lane<4, decltype(getR), true>(getR, (uint32_t)lane < nit, item0 + lane, n, qstride, Qs, Gs, oa);
-#else
-            evd_project_lane<4>(getR, (uint32_t)lane < nit, item0 + lane, n, qstride, Qs, Gs);
-#endif
+    };
+
+    uint32_t task = blockIdx.x * 4 + wave;
+    while (task < ntasks) {
+        // one group: up to `park` tasks streamed and held, one more streamed into rtab, then their rotation passes back to back
+        __builtin_amdgcn_s_setprio(3);
+        double held[COVEVD_PARK][16];                 // R of this lane's item of each held task, in rtab's slot order
+        uint32_t held_item0[COVEVD_PARK];             // (wave-uniform)
+        uint32_t nheld = 0;
+        const int lfull = ((uint32_t)lane < task_items) ? lane : (int)task_items - 1;
+#pragma unroll
+        for (int h = 0; h < COVEVD_PARK; ++h) {
+            held_item0[h] = 0;
+#pragma unroll
+            for (int s = 0; s < 16; ++s) held[h][s] = 0.0;
+            // more to stream and room to hold: the task's R moves from rtab (the next task rewrites it) into registers and the
+            // wave streams on at once -- no rotation phase, no Q/G burst in the middle of its read stream.  (Not the wave's last
+            // task, so not the globally last one: it is full.)
+            if (nheld == (uint32_t)h && (uint32_t)h < park && task + tstride < ntasks) {
+                held_item0[h] = task * task_items;
+                stream(held_item0[h], task_items);
+#pragma unroll
+                for (int s = 0; s < 16; ++s) held[h][s] = rt[s][lfull];
+                wave_lds_fence();
+                nheld = h + 1;
+                task += tstride;
+            }
         }
+        const uint32_t item0 = task * task_items;
+        const uint32_t nit = (batch - item0 < task_items) ? batch - item0 : task_items;
+        stream(item0, nit);
+        const int li = ((uint32_t)lane < nit) ? lane : (int)nit - 1;     // lanes beyond nit redo the last item and write nothing
+        // EVD of the held tasks' items and then of this task's, one item per lane, at low priority
+        __builtin_amdgcn_s_setprio(0);
+#pragma unroll
+        for (int h = 0; h < COVEVD_PARK; ++h)
+            if ((uint32_t)h < nheld) {
+                const double(&hr)[16] = held[h];
+                rotate([&](int i, int j) { return slotR([&](int s) { return hr[s]; }, i, j); }, (uint32_t)lane < task_items,
+                       held_item0[h] + lane);
+            }
+        rotate([&](int i, int j) { return slotR([&](int s) { return rt[s][li]; }, i, j); }, (uint32_t)lane < nit, item0 + lane);
         wave_lds_fence();
+        task += tstride;
     }
 }

@@ -628,12 +628,25 @@ __global__ __launch_bounds__(64) void evd_proj_order_kernel(const double2* __res
 //     Jacobi of evd_project_lane on the 64 of them and writes Q (and G).  R never touches HBM, and nothing is written
 //     while the wave streams: the stand-alone covariance lost 0.06 ms to its 67 MB of 256-B R stores interleaved with
 //     the read stream (its arithmetic is free at 2 waves/SIMD), see profiles/r02_fused_covevd_priorities.txt.
-//     The EVD is NOT hidden: every wave streams at the same rate, so all of them reach their EVD phase together --
-//     2 x (153 us of stream + 40 us of rotations) per 262,144 items.  Staggered phases and a rotation-per-item state
-//     machine were measured slower (the rotations' fp64 VALU work and the stream's fp64 MFMAs share the DP pipe).
-//     A streaming wave runs at s_setprio 3, an EVD phase at 0 (worth 0.04 ms against equal priorities once the waves
-//     drift apart).
+//     The EVD is NOT hidden: every wave streams at the same rate, so all of them reach their EVD phase together.
+//     Staggered phases and a rotation-per-item state machine were measured slower (the rotations' fp64 VALU work and
+//     the stream's fp64 MFMAs share the DP pipe).  A streaming wave runs at s_setprio 3, an EVD phase at 0 (worth
+//     0.04 ms against equal priorities once the waves drift apart).
+//     DEFERRED ROTATION (lab: BAZ_MUSIC_COVEVD_DEFER=1; the product launches with park = 0, one phase per task): a wave with
+//     another task to come takes the finished task's R out of LDS into registers (COVEVD_PARK tasks of 16 doubles per
+//     lane; the stream loop leaves that room) and streams on; the rotation passes of the held tasks and of the one still
+//     in LDS run back to back where the wave's work ends: one stop per COVEVD_PARK + 1 tasks.  Same function on the same
+//     values: the bits do not change (tests/test_covevd_deferred_gpu.py).  The expectation was that a phase in the
+//     MIDDLE of a wave's work costs 35-40 us more than one at its end (all read streams stop at once, HBM drains, the
+//     Q/G stores go out in one burst, the streams start cold again).  Measured at 262,144 items, same binary: 0-13 us by
+//     box, inside the spread of a step's time -- a second pass at the end costs about what the one in the middle did
+//     (a likely reading: one end phase is cheap because it runs under the waves that still stream, and two passes no
+//     longer fit under them).  No spill, no scratch (profiles/r06_covevd_deferred.txt).
 // -------------------------------------------------------------------------------------
+// tasks a wave of cov4_evd_kernel may hold in registers (32 VGPRs each) before it has to rotate, where the launch asks for it
+// (park; lab).  1 keeps the kernel at the 192 VGPRs of the Jacobi alone (a held set is dead once its pass has loaded it); with
+// 2 the second set is live through the first pass: 224 VGPRs.  1 is also all that the largest launch (two tasks per wave) can use.
+constexpr int COVEVD_PARK = 1;
 #define BAZ_EVD_ORDER 0
 #include "cov4_evd_kernel.inc.h"     // cov4_evd_kernel
 #undef BAZ_EVD_ORDER
