@@ -159,6 +159,16 @@ def _set_power_mode(h, mode):
     h.impl.set_power_mode(int(mode))
 
 
+def _set_beam_mode(h, mode, loading):
+    # EXTENSION, no reference counterpart: the MVDR beamformer output y = w^H X per reported entry over the item's own snapshots
+    # (behind last_beams()), see include/baz_music_hip.h.  Stays in force across set_frequency().
+    if mode not in (0, 1):
+        raise ValueError("beam mode must be 0 or 1, not %r" % (mode,))
+    if not (loading >= 0.0 and loading < float("inf")):
+        raise ValueError("loading must be finite and >= 0, not %r" % (loading,))
+    h.impl.set_beam_mode(int(mode), float(loading))
+
+
 def _set_averaging(h, window, forgetting):
     # EXTENSION, no reference counterpart: the covariance of every item averaged over the last `window` items of the stream
     # (weights forgetting ** age), see include/baz_music_hip.h.  Stays in force across set_frequency(): covariances do not
@@ -213,6 +223,16 @@ if _HAVE_GR:
             """The float64 power estimates of the first `count` (item, slot) entries of the last work() call."""
             return numpy.asarray(self.impl.last_powers(int(count)), dtype=numpy.float64)
 
+        def set_beam_mode(self, beam_mode=1, loading=0.0):
+            """Opt-in (not reference behaviour): the MVDR beamformer output of every reported entry over the item's own snapshots,
+            w = R^-1 a / (a^H R^-1 a) with `loading` times the mean diagonal added to R's diagonal (1: behind last_beams(); 0: off).
+            Not available with set_smoothing.  The constructor keeps the reference's signature."""
+            _set_beam_mode(self, beam_mode, loading)
+
+        def last_beams(self, items):
+            """The complex64 beams of the first `items` items of the last work() call, shape (items, n, K)."""
+            return numpy.asarray(self.impl.last_beams(int(items)), dtype=numpy.complex64)
+
         def set_averaging(self, window, forgetting=1.0):
             """Opt-in (not reference behaviour): estimate every item from the covariances of the last `window` items, weighted
             forgetting ** age (window 1: off).  Raises ValueError unless 1 <= window <= 64 and 0 < forgetting <= 1."""
@@ -258,6 +278,16 @@ else:
         def last_powers(self, count):
             """The float64 power estimates of the first `count` (item, slot) entries of the last work() call."""
             return numpy.asarray(self.impl.last_powers(int(count)), dtype=numpy.float64)
+
+        def set_beam_mode(self, beam_mode=1, loading=0.0):
+            """Opt-in (not reference behaviour): the MVDR beamformer output of every reported entry over the item's own snapshots,
+            w = R^-1 a / (a^H R^-1 a) with `loading` times the mean diagonal added to R's diagonal (1: behind last_beams(); 0: off).
+            Not available with set_smoothing.  The constructor keeps the reference's signature."""
+            _set_beam_mode(self, beam_mode, loading)
+
+        def last_beams(self, items):
+            """The complex64 beams of the first `items` items of the last work() call, shape (items, n, K)."""
+            return numpy.asarray(self.impl.last_beams(int(items)), dtype=numpy.complex64)
 
         def set_averaging(self, window, forgetting=1.0):
             """Opt-in (not reference behaviour): estimate every item from the covariances of the last `window` items, weighted

@@ -40,6 +40,8 @@ SYMBOLS = [
     "baz_music_order_estimate",
     "baz_music_set_refine_mode", "baz_music_get_refine_mode", "baz_music_last_refine_offsets", "baz_music_refine_estimate",
     "baz_music_set_power_mode", "baz_music_get_power_mode", "baz_music_last_powers", "baz_music_power_estimate",
+    "baz_music_set_beam_mode", "baz_music_get_beam_mode", "baz_music_last_beams", "baz_music_last_beams_device",
+    "baz_music_last_beam_weights", "baz_music_beam_weights",
     "baz_music_set_averaging", "baz_music_get_averaging", "baz_music_reset_averaging", "baz_music_averaging_weights",
     "baz_music_debug_average",
 ]
@@ -200,6 +202,19 @@ def _bind(L):
     L.baz_music_power_estimate.restype = ctypes.c_int
     L.baz_music_power_estimate.argtypes = [_u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), _u32,
                                            ctypes.POINTER(ctypes.c_double)]
+    L.baz_music_set_beam_mode.restype = ctypes.c_int
+    L.baz_music_set_beam_mode.argtypes = [_vp, ctypes.c_int, ctypes.c_double]
+    L.baz_music_get_beam_mode.restype = ctypes.c_int
+    L.baz_music_get_beam_mode.argtypes = [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]
+    L.baz_music_last_beams.restype = ctypes.c_int
+    L.baz_music_last_beams.argtypes = [_vp, ctypes.POINTER(ctypes.c_float), _u32]
+    L.baz_music_last_beams_device.restype = ctypes.c_int
+    L.baz_music_last_beams_device.argtypes = [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_u32)]
+    L.baz_music_last_beam_weights.restype = ctypes.c_int
+    L.baz_music_last_beam_weights.argtypes = [_vp, ctypes.POINTER(ctypes.c_double), _u32]
+    L.baz_music_beam_weights.restype = ctypes.c_int
+    L.baz_music_beam_weights.argtypes = [_u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), _u32, ctypes.c_double,
+                                         ctypes.POINTER(ctypes.c_double)]
     L.baz_music_refine_estimate.restype = ctypes.c_int
     L.baz_music_refine_estimate.argtypes = [ctypes.POINTER(ctypes.c_double), _u32, ctypes.POINTER(ctypes.c_double)]
     L.baz_music_order_estimate.restype = ctypes.c_int
@@ -485,6 +500,44 @@ class Context:
             self._chk(r, "baz_music_last_powers")
         return out[:r].copy()
 
+    def set_beam_mode(self, mode, loading=0.0):
+        """Opt-in extension (not reference behaviour): 1 computes the MVDR weights w = R^-1 a / (a^H R^-1 a) of every reported entry
+        and the beam y = w^H X over the item's snapshots (last_beams, last_beam_weights; every port unchanged); `loading` adds
+        loading * mean diagonal to R's diagonal (include/baz_music_hip.h); 0 (default): off."""
+        self._chk(self._L.baz_music_set_beam_mode(self._h, int(mode), float(loading)), "baz_music_set_beam_mode")
+
+    def get_beam_mode(self):
+        """(mode, loading) in force."""
+        mode, loading = ctypes.c_int(0), ctypes.c_double(0.0)
+        self._chk(self._L.baz_music_get_beam_mode(self._h, ctypes.byref(mode), ctypes.byref(loading)), "baz_music_get_beam_mode")
+        return int(mode.value), float(loading.value)
+
+    def last_beams(self, items):
+        """Beams (complex64, shape (items, n, K)) of the first `items` items of the last process*() call; zeros for a call made with
+        the mode off."""
+        K = self.nsamples // self.m
+        out = np.zeros((max(int(items), 1), self.n, K), np.complex64)
+        r = self._L.baz_music_last_beams(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), int(items))
+        if r < 0:
+            self._chk(r, "baz_music_last_beams")
+        return out[:r].copy()
+
+    def last_beam_weights(self, items):
+        """MVDR weights (complex128, shape (items, n, m)) of the first `items` items of the last process*() call; zeros for a call
+        made with the mode off."""
+        out = np.zeros((max(int(items), 1), self.n, self.m), np.complex128)
+        r = self._L.baz_music_last_beam_weights(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(items))
+        if r < 0:
+            self._chk(r, "baz_music_last_beam_weights")
+        return out[:r].copy()
+
+    def last_beams_device(self):
+        """(device pointer, items) of the buffer behind last_beams, [item][slot][K] complex64: ordered on the context's stream, valid
+        until the next process*(), set_* or destroy; (0, 0) after a call made with the mode off.  Does not synchronise."""
+        p, items = _vp(None), _u32(0)
+        self._chk(self._L.baz_music_last_beams_device(self._h, ctypes.byref(p), ctypes.byref(items)), "baz_music_last_beams_device")
+        return int(p.value or 0), int(items.value)
+
     def set_stream(self, hip_stream):
         self._chk(self._L.baz_music_set_stream(self._h, _vp(hip_stream) if hip_stream else None),
                   "baz_music_set_stream")
@@ -591,6 +644,23 @@ def power_estimate(R, a):
                                        out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
     if r != OK:
         raise ValueError("baz_music_power_estimate: %s" % lib().baz_music_strerror(r).decode())
+    return out[:a.shape[0]].copy()
+
+
+def beam_weights(R, a, loading=0.0):
+    """HOST-ONLY: the MVDR weights w = R_l^-1 a / (a^H R_l^-1 a) the library's definition gives for one covariance R (m x m complex),
+    the steering rows a (count x m complex64) and the diagonal loading (needs no device).  Returns a complex128 array (count, m)."""
+    R = np.ascontiguousarray(R, dtype=np.complex128)
+    if R.ndim != 2 or R.shape[0] != R.shape[1]:
+        raise ValueError("beam_weights: R must be a square matrix")
+    m = R.shape[0]
+    a = np.ascontiguousarray(a, dtype=np.complex64).reshape(-1, m) if m else np.zeros((0, 0), np.complex64)
+    out = np.zeros((max(a.shape[0], 1), max(m, 1)), np.complex128)
+    r = lib().baz_music_beam_weights(m, R.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                     a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), a.shape[0], float(loading),
+                                     out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    if r != OK:
+        raise ValueError("baz_music_beam_weights: %s" % lib().baz_music_strerror(r).decode())
     return out[:a.shape[0]].copy()
 
 

@@ -17,6 +17,7 @@
 #include "smoothing_kernels.hip.h"
 #include "refine_kernels.hip.h"
 #include "power_kernels.hip.h"
+#include "beam_kernels.hip.h"
 #include "average_kernels.hip.h"
 
 #include <algorithm>
@@ -320,6 +321,16 @@ struct baz_music_ctx {
     size_t pow_cap = 0;             // doubles
     uint32_t pow_count = 0;         // items of the call in flight recorded so far (the next chunk's offset)
     bool pow_on = false;            // whether the last process*() call ran with the mode on (else every power is 0)
+    // Opt-in MVDR beamformer output per reported entry (baz_music_set_beam_mode; NOT reference behaviour; beam_kernels.hip.h, DESIGN.md
+    // 8g).  While beam_mode is 0 its two kernels are not launched and nothing below is allocated.  The pickers' staging buffer is dRefAl.
+    int beam_mode = 0;              // 0: off (the reference); 1: MVDR
+    double beam_loading = 0.0;      // diagonal loading, in units of the mean diagonal of R
+    float2* dBeam = nullptr;        // y per (item, slot, snapshot) of the last process*() call, in call order (all chunks)
+    size_t beam_cap = 0;            // complex64
+    double2* dBeamW = nullptr;      // w per (item, slot, antenna) of the last process*() call, in call order (all chunks)
+    size_t beam_w_cap = 0;          // complex128
+    uint32_t beam_count = 0;        // items of the call in flight recorded so far (the next chunk's offset)
+    bool beam_on = false;           // whether the last process*() call ran with the mode on (else every beam is 0)
     // Opt-in covariance averaging across the items of the stream (baz_music_set_averaging; NOT reference behaviour; average_kernels.hip.h,
     // DESIGN.md 8e).  While avg_window is 1 none of the mode's kernels is launched and nothing below is allocated.
     uint32_t avg_window = 1;        // W: 1 = off (the reference)
@@ -791,6 +802,13 @@ int order_begin(baz_music_ctx* c, uint32_t items)
         const int r = grow(c, c->dPow, c->pow_cap, (size_t)items * c->n);
         if (r) return r;
     }
+    c->beam_count = 0;
+    c->beam_on = c->beam_mode != 0;
+    if (c->beam_on) {
+        int r = grow(c, c->dBeam, c->beam_cap, (size_t)items * c->n * c->K);
+        if (r == BAZ_MUSIC_OK) r = grow(c, c->dBeamW, c->beam_w_cap, (size_t)items * c->n * c->m);
+        if (r) return r;
+    }
     return c->ord_on ? grow_bytes(c, c->dOrd, c->ord_cap, items) : BAZ_MUSIC_OK;
 }
 
@@ -1000,8 +1018,8 @@ int launch_frontend(baz_music_ctx* c, const void* d_in, uint32_t batch, double* 
         if (ra == BAZ_MUSIC_OK) ra = launch_average(c, c->dR, batch, c->dRavg);
         return ra ? ra : launch_evd(c, c->dRavg, batch, dQ, qstride, c->dG);
     }
-    // (power mode on: the fused kernel also stores its R, the tap baz_music_debug_cov uses -- same kernel, same Q and G bits)
-    if (c->fused_covevd) return launch_covevd(c, in, batch, dQ, qstride, c->dG, c->power_mode ? c->dR : nullptr);
+    // (power / beam mode on: the fused kernel also stores its R, the tap baz_music_debug_cov uses -- same kernel, same Q and G bits)
+    if (c->fused_covevd) return launch_covevd(c, in, batch, dQ, qstride, c->dG, (c->power_mode || c->beam_mode) ? c->dR : nullptr);
     const int r = launch_cov(c, in, batch, c->dR);
     return r ? r : launch_evd(c, c->dR, batch, dQ, qstride, c->dG);
 }
@@ -2306,6 +2324,81 @@ int launch_power(baz_music_ctx* c, uint32_t batch, float* d_ang, float* d_lvl)
 #undef BAZ_CALL
 }
 
+// Opt-in MVDR weights of the chunk's entries (beam_kernels.hip.h), behind refine_kernel / power_kernel: reads what launch_power reads
+// (on R plus the loading), writes this chunk's weights and whatever of the caller's ang / lvl no earlier kernel has written.
+template <int M>
+int launch_beam_weights_t(baz_music_ctx* c, const bazbeam::BeamWeightsArgs& A)
+{
+    constexpr uint32_t IPB = bazbeam::BeamGeom<M>::IPB;
+    hipLaunchKernelGGL((bazbeam::beam_weights_kernel<M>), dim3((A.batch + IPB - 1) / IPB), dim3(bazbeam::BeamGeom<M>::THREADS), 0, c->stream, A);
+    HIP_TRY(c, hipGetLastError());
+    return BAZ_MUSIC_OK;
+}
+
+int launch_beam_weights(baz_music_ctx* c, uint32_t batch, float* d_ang, float* d_lvl)
+{
+    ProfScope ps(c, BAZ_MUSIC_STAGE_MERGE);
+    BAZ_REQUIRE(c, dRefAl); BAZ_REQUIRE(c, dBeamW); BAZ_REQUIRE_TAB(c, dRW);
+    if (c->avg_window > 1) BAZ_REQUIRE(c, dRavg); else BAZ_REQUIRE(c, dR);
+    bazbeam::BeamWeightsArgs A;
+    const size_t entries = (size_t)batch * c->n;
+    A.ang_in = c->dRefAl;
+    A.lvl_in = c->dRefAl + entries;
+    A.ang_out = d_ang;
+    A.lvl_out = d_lvl;
+    A.w_out = c->dBeamW + (size_t)c->beam_count * c->n * c->m;
+    A.R = c->avg_window > 1 ? c->dRavg : c->dR;      // what launch_frontend handed to the EVD
+    A.raw = c->tab.dRW;
+    A.rel_floor = BAZ_MUSIC_POWER_PIVOT_FLOOR;
+    A.loading = c->beam_loading;
+    A.batch = batch; A.n = c->n; A.res = c->res;
+#define BAZ_CALL(MV) launch_beam_weights_t<MV>(c, A)
+    switch (c->m) {
+        BAZ_M_CASES(BAZ_CALL)
+        default: return BAZ_MUSIC_E_UNSUPPORTED;
+    }
+#undef BAZ_CALL
+}
+
+// y = w^H X of the chunk (beam_kernels.hip.h), the last launch of a sequence: reads the chunk's input a second time (d_in: device
+// memory, or the caller's mapped input on the zero-copy path) and the weights launch_beam_weights just wrote.
+template <int M>
+int launch_beam_apply_t(baz_music_ctx* c, const bazbeam::BeamApplyArgs& A)
+{
+    const uint64_t units = (uint64_t)A.batch * A.nseg;
+    const dim3 grid((unsigned)((units + bazbeam::APPLY_WAVES - 1) / bazbeam::APPLY_WAVES));
+    const size_t lds = (size_t)bazbeam::APPLY_WAVES * A.n * (M * sizeof(double2) + sizeof(uint32_t));   // the waves' weights, then their flags
+    if constexpr (M % 2 == 0) {
+        if (((uintptr_t)A.x & 15u) == 0) {
+            hipLaunchKernelGGL((bazbeam::beam_apply_kernel<M, true>), grid, dim3(bazbeam::APPLY_THREADS), lds, c->stream, A);
+            HIP_TRY(c, hipGetLastError());
+            return BAZ_MUSIC_OK;
+        }
+    }
+    hipLaunchKernelGGL((bazbeam::beam_apply_kernel<M, false>), grid, dim3(bazbeam::APPLY_THREADS), lds, c->stream, A);
+    HIP_TRY(c, hipGetLastError());
+    return BAZ_MUSIC_OK;
+}
+
+int launch_beam_apply(baz_music_ctx* c, const void* d_in, uint32_t batch)
+{
+    ProfScope ps(c, BAZ_MUSIC_STAGE_MERGE);
+    BAZ_REQUIRE(c, dBeam); BAZ_REQUIRE(c, dBeamW);
+    bazbeam::BeamApplyArgs A;
+    A.x = static_cast<const float2*>(d_in);
+    A.w = c->dBeamW + (size_t)c->beam_count * c->n * c->m;
+    A.y = c->dBeam + (size_t)c->beam_count * c->n * c->K;
+    A.batch = batch; A.n = c->n; A.K = c->K;
+    A.nseg = (c->K + bazbeam::APPLY_SEG - 1) / bazbeam::APPLY_SEG;
+    if ((uint64_t)batch * A.nseg > 0x7fffffffull * bazbeam::APPLY_WAVES) return BAZ_MUSIC_E_UNSUPPORTED;   // (the grid's x extent)
+#define BAZ_CALL(MV) launch_beam_apply_t<MV>(c, A)
+    switch (c->m) {
+        BAZ_M_CASES(BAZ_CALL)
+        default: return BAZ_MUSIC_E_UNSUPPORTED;
+    }
+#undef BAZ_CALL
+}
+
 int process_device_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void* d_ang, void* d_lvl, void* d_spec);
 
 // One launch sequence over `batch` items.  Averaging on: a sequence that fails forgets the history (the stream position the host
@@ -2351,8 +2444,8 @@ int process_device_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void
         if (r) return r;
         spec = c->dPeakSpec;
     }
-    // refinement / power mode: the pickers write ang | lvl (lvl always: it marks the real entries) into a staging buffer of this context
-    // and refine_kernel / power_kernel write the caller's -- which may be host memory mapped over the link, never read back
+    // refinement / power / beam mode: the pickers write ang | lvl (lvl always: it marks the real entries) into a staging buffer of this context
+    // and refine_kernel / power_kernel / beam_weights_kernel write the caller's -- which may be host memory mapped over the link, never read back
     float* ang = static_cast<float*>(d_ang);
     float* lvl = static_cast<float*>(d_lvl);
     const size_t entries = (size_t)batch * c->n;
@@ -2360,7 +2453,10 @@ int process_device_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void
         return refuse_null(c, nullptr, "dRefOff (order_begin)");
     if (c->power_mode && (!c->pow_on || !c->dPow || ((size_t)c->pow_count + batch) * c->n > c->pow_cap))
         return refuse_null(c, nullptr, "dPow (order_begin)");
-    if (c->refine_mode || c->power_mode) {
+    if (c->beam_mode && (!c->beam_on || !c->dBeam || !c->dBeamW || ((size_t)c->beam_count + batch) * c->n * c->K > c->beam_cap ||
+                         ((size_t)c->beam_count + batch) * c->n * c->m > c->beam_w_cap))
+        return refuse_null(c, nullptr, "dBeam (order_begin)");
+    if (c->refine_mode || c->power_mode || c->beam_mode) {
         r = grow(c, c->dRefAl, c->ref_al_cap, entries * 2);
         if (r) return r;
         ang = c->dRefAl;
@@ -2389,12 +2485,19 @@ int process_device_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void
         if (r) return r;
         c->ref_count += batch;
     }
-    if (c->power_mode) {           // the last launch: ang / lvl where refine_kernel has not written them
+    if (c->power_mode) {           // ang / lvl where refine_kernel has not written them
         float* const p_ang = c->refine_mode ? nullptr : static_cast<float*>(d_ang);
         float* const p_lvl = (c->refine_mode && c->power_mode != 2) ? nullptr : static_cast<float*>(d_lvl);
         r = launch_power(c, batch, p_ang, p_lvl);
         if (r) return r;
         c->pow_count += batch;
+    }
+    if (c->beam_mode) {            // the last two launches: ang / lvl where neither refine_kernel nor power_kernel has written them
+        const bool earlier = c->refine_mode || c->power_mode;
+        r = launch_beam_weights(c, batch, earlier ? nullptr : static_cast<float*>(d_ang), earlier ? nullptr : static_cast<float*>(d_lvl));
+        if (r == BAZ_MUSIC_OK) r = launch_beam_apply(c, d_in, batch);
+        if (r) return r;
+        c->beam_count += batch;
     }
     return BAZ_MUSIC_OK;
 }
@@ -2868,6 +2971,8 @@ void baz_music_destroy(baz_music_ctx* c)
         if (c->dRefAl) (void)dev_free(c->dRefAl);
         if (c->dRefOff) (void)dev_free(c->dRefOff);
         if (c->dPow) (void)dev_free(c->dPow);
+        if (c->dBeam) (void)dev_free(c->dBeam);
+        if (c->dBeamW) (void)dev_free(c->dBeamW);
         if (c->dRavg) (void)dev_free(c->dRavg);
         if (c->dAvgHist[0]) (void)dev_free(c->dAvgHist[0]);
         if (c->dAvgHist[1]) (void)dev_free(c->dAvgHist[1]);
@@ -2961,6 +3066,11 @@ int baz_music_reserve(baz_music_ctx* c, uint32_t max_batch)
         const int rp = grow(oc, oc->dPow, oc->pow_cap, (size_t)max_batch * oc->n);
         if (rp) return rp;
     }
+    if (c->beam_mode) {   // beam mode (never with smoothing on): the beams and weights of a whole call
+        int rb = grow(c, c->dBeam, c->beam_cap, (size_t)max_batch * c->n * c->K);
+        if (rb == BAZ_MUSIC_OK) rb = grow(c, c->dBeamW, c->beam_w_cap, (size_t)max_batch * c->n * c->m);
+        if (rb) return rb;
+    }
     if (c->sm.inner) {   // smoothing on: the inner context's workspace for one chunk, and the re-stacked chunk
         const uint32_t chunk = smooth_chunk(c, max_batch);
         const int rs = grow(c, c->sm.dY, c->sm.y_cap, (size_t)chunk * c->sm.Kp * c->sm.ms);
@@ -2977,7 +3087,7 @@ int baz_music_reserve(baz_music_ctx* c, uint32_t max_batch)
         return (rw || !c->wide_mfma || c->wide_literal_only) ? rw : ensure_candidates(c, wide_cand_entries(c, pass));
     }
     int r = ensure_workspace(c, max_batch);
-    if (r == BAZ_MUSIC_OK && (c->refine_mode || c->power_mode)) r = grow(c, c->dRefAl, c->ref_al_cap, (size_t)max_batch * c->n * 2);   // (the pickers' staging)
+    if (r == BAZ_MUSIC_OK && (c->refine_mode || c->power_mode || c->beam_mode)) r = grow(c, c->dRefAl, c->ref_al_cap, (size_t)max_batch * c->n * 2);   // (the pickers' staging)
 #ifdef BAZ_MUSIC_LAB
     if (r == BAZ_MUSIC_OK && c->sort_mode != 0) r = ensure_sort_workspace(c, max_batch);
 #endif
@@ -3844,6 +3954,10 @@ int baz_music_set_smoothing(baz_music_ctx* c, uint32_t subarray, int forward_bac
         baz_music_destroy(old);                   // (drains the stream first: batches in flight may still use it)
         return BAZ_MUSIC_OK;
     }
+    {   // (the beam mode has no m-antenna weight vector for the inner context's re-stacked items)
+        std::lock_guard<std::mutex> lk(c->mtx);
+        if (c->beam_mode) return BAZ_MUSIC_E_UNSUPPORTED;
+    }
     bazsmooth::Perm perm = {};
     if (smoothing_check(c->m, c->res, c->hRaw, subarray, fb, perm.p) != BAZ_MUSIC_OK) return BAZ_MUSIC_E_INVALID;
     const uint32_t L = c->m - subarray + 1;
@@ -3855,7 +3969,7 @@ int baz_music_set_smoothing(baz_music_ctx* c, uint32_t subarray, int forward_bac
     if (r != BAZ_MUSIC_OK) return r;
     {
         std::lock_guard<std::mutex> lk(c->mtx);   // a batch sees the old mode or the new one
-        r = baz_music_set_stream(inner, c->stream);
+        r = c->beam_mode ? BAZ_MUSIC_E_UNSUPPORTED : baz_music_set_stream(inner, c->stream);   // (set_beam_mode may have come in between)
         if (r == BAZ_MUSIC_OK) r = baz_music_set_peak_mode(inner, c->peak_mode);
         if (r == BAZ_MUSIC_OK) r = baz_music_set_order_mode(inner, c->order_mode);
         if (r == BAZ_MUSIC_OK) r = baz_music_set_refine_mode(inner, c->refine_mode);
@@ -3864,6 +3978,8 @@ int baz_music_set_smoothing(baz_music_ctx* c, uint32_t subarray, int forward_bac
         if (r == BAZ_MUSIC_OK) {
             inner->order_nsnap = c->K;            // N of the criterion: this context's snapshots, not the K' re-stacked columns
             inner->ord_driven = true;
+            c->beam_on = false;                   // (calls under smoothing run with the beam mode off: last_beams reports zeros)
+            c->beam_count = 0;
             old = c->sm.inner;
             c->sm.inner = inner;
             c->sm.ms = subarray; c->sm.L = L; c->sm.Kp = (uint32_t)Kp; c->sm.fb = fb;
@@ -4129,6 +4245,133 @@ int baz_music_power_estimate(uint32_t m, const double* R_ri, const float* a_ri, 
             s += (xr * xr + xi * xi) / d[i];
         }
         out[e] = bazpower::power_from_s(s);
+    }
+    return BAZ_MUSIC_OK;
+}
+
+int baz_music_set_beam_mode(baz_music_ctx* c, int mode, double loading)
+{
+    if (!c || mode < 0 || mode > 1 || !(loading - loading == 0.0) || loading < 0.0) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    if (mode && c->wide) return BAZ_MUSIC_E_UNSUPPORTED;   // (the kernels are specialised per m, like the pickers they follow)
+    if (mode && c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;   // (smoothing: no m-antenna weight vector for the re-stacked items)
+    c->beam_mode = mode;
+    c->beam_loading = loading;
+    return BAZ_MUSIC_OK;
+}
+
+int baz_music_get_beam_mode(const baz_music_ctx* c, int* mode, double* loading)
+{
+    if (!c || !mode || !loading) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(const_cast<baz_music_ctx*>(c)->mtx);
+    *mode = c->beam_mode;
+    *loading = c->beam_loading;
+    return BAZ_MUSIC_OK;
+}
+
+namespace {
+// The first `items` items of the last call's beams (per = n K complex64) or weights (per = n m complex128): zeros after a mode-off call.
+int last_beam_copy(baz_music_ctx* c, void* out, const void* dev, uint32_t items, size_t item_bytes)
+{
+    DeviceGuard guard(c->device);
+    // (a mode-off call under smoothing: the inner context counted the call's items)
+    const uint32_t have = std::min<uint32_t>(items, c->beam_on ? c->beam_count : (c->sm.inner ? c->sm.inner->ord_items : c->ord_items));
+    if (!c->beam_on) {
+        if (have) memset(out, 0, (size_t)have * item_bytes);
+        return (int)have;
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (have) HIP_TRY(c, hipMemcpy(out, dev, (size_t)have * item_bytes, hipMemcpyDeviceToHost));
+    return (int)have;
+}
+}  // namespace
+
+int baz_music_last_beams(baz_music_ctx* c, float* out_ri, uint32_t items)
+{
+    if (!c || (!out_ri && items)) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    return last_beam_copy(c, out_ri, c->dBeam, items, (size_t)c->n * c->K * sizeof(float2));
+}
+
+int baz_music_last_beam_weights(baz_music_ctx* c, double* out_ri, uint32_t items)
+{
+    if (!c || (!out_ri && items)) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    return last_beam_copy(c, out_ri, c->dBeamW, items, (size_t)c->n * c->m * sizeof(double2));
+}
+
+int baz_music_last_beams_device(baz_music_ctx* c, const void** d_beams, uint32_t* items)
+{
+    if (!c || !d_beams || !items) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    *d_beams = c->beam_on ? c->dBeam : nullptr;     // (a call made with the mode off has no buffer: 0 items)
+    *items = c->beam_on ? c->beam_count : 0u;
+    return BAZ_MUSIC_OK;
+}
+
+// The definition of include/baz_music_hip.h loop for loop; the degeneracy rule and the s -> w step are the kernels' own text.
+int baz_music_beam_weights(uint32_t m, const double* R_ri, const float* a_ri, uint32_t count, double loading, double* w_ri)
+{
+    if (m < 1 || m > BAZ_MUSIC_MAX_M || !(loading - loading == 0.0) || loading < 0.0) return BAZ_MUSIC_E_INVALID;
+    if (count == 0) return BAZ_MUSIC_OK;
+    if (!R_ri || !a_ri || !w_ri) return BAZ_MUSIC_E_INVALID;
+    std::vector<double> Lr((size_t)m * m, 0.0), Li((size_t)m * m, 0.0), d(m, 0.0), dg(m), zr(m), zi(m), ur(m), ui(m);
+    auto Rr = [&](uint32_t i, uint32_t j) { return i == j ? dg[i] : R_ri[2 * ((size_t)i * m + j)]; };
+    auto Ri = [&](uint32_t i, uint32_t j) { return R_ri[2 * ((size_t)i * m + j) + 1]; };
+    double trace = 0.0;
+    for (uint32_t i = 0; i < m; ++i) trace += R_ri[2 * ((size_t)i * m + i)];
+    const double delta = loading * (trace / (double)m);
+    double trace_l = 0.0;
+    for (uint32_t i = 0; i < m; ++i) {
+        dg[i] = R_ri[2 * ((size_t)i * m + i)] + delta;
+        trace_l += dg[i];
+    }
+    const double floor = bazpower::power_pivot_floor(trace_l, m, BAZ_MUSIC_POWER_PIVOT_FLOOR);
+    bool ok = true;
+    for (uint32_t j = 0; j < m && ok; ++j) {
+        for (uint32_t i = j; i < m; ++i) {
+            double vr = Rr(i, j), vi = i == j ? 0.0 : Ri(i, j);
+            for (uint32_t k = 0; k < j; ++k) {     // L_ik conj(L_jk) d_k
+                const double wr = Lr[(size_t)j * m + k] * d[k], wi = Li[(size_t)j * m + k] * d[k];
+                vr -= Lr[(size_t)i * m + k] * wr + Li[(size_t)i * m + k] * wi;
+                if (i != j) vi -= Li[(size_t)i * m + k] * wr - Lr[(size_t)i * m + k] * wi;
+            }
+            if (i == j) {
+                d[j] = vr;
+                ok = bazpower::power_pivot_ok(vr, floor);
+                if (!ok) break;
+            } else {
+                Lr[(size_t)i * m + j] = vr / d[j];
+                Li[(size_t)i * m + j] = vi / d[j];
+            }
+        }
+    }
+    for (uint32_t e = 0; e < count; ++e) {
+        double* const w = w_ri + 2 * (size_t)e * m;
+        if (!ok) {
+            for (uint32_t i = 0; i < 2 * m; ++i) w[i] = 0.0;
+            continue;
+        }
+        const float* a = a_ri + 2 * (size_t)e * m;
+        double s = 0.0;
+        for (uint32_t i = 0; i < m; ++i) {
+            double xr = (double)a[2 * i], xi = (double)a[2 * i + 1];
+            for (uint32_t k = 0; k < i; ++k) {
+                xr -= Lr[(size_t)i * m + k] * zr[k] - Li[(size_t)i * m + k] * zi[k];
+                xi -= Lr[(size_t)i * m + k] * zi[k] + Li[(size_t)i * m + k] * zr[k];
+            }
+            zr[i] = xr; zi[i] = xi;
+            s += (xr * xr + xi * xi) / d[i];
+        }
+        for (uint32_t i = m; i-- > 0;) {
+            double xr = zr[i] / d[i], xi = zi[i] / d[i];
+            for (uint32_t k = m - 1; k > i; --k) {   // conj(L_ki) u_k
+                xr -= Lr[(size_t)k * m + i] * ur[k] + Li[(size_t)k * m + i] * ui[k];
+                xi -= Lr[(size_t)k * m + i] * ui[k] - Li[(size_t)k * m + i] * ur[k];
+            }
+            ur[i] = xr; ui[i] = xi;
+        }
+        for (uint32_t i = 0; i < m; ++i) bazbeam::beam_w_from_u(ur[i], ui[i], s, true, &w[2 * i], &w[2 * i + 1]);
     }
     return BAZ_MUSIC_OK;
 }

@@ -208,6 +208,23 @@ std::vector<double> baz_music_doa::last_powers(unsigned int count)
     return out;
 }
 
+void baz_music_doa::set_beam_mode(int mode, double loading)
+{
+    const int rc = baz_music_set_beam_mode(d_ctx, mode, loading);
+    if (rc == BAZ_MUSIC_E_INVALID) throw std::invalid_argument("music_doa: set_beam_mode: mode must be 0 (off) or 1 (MVDR), loading finite and >= 0");
+    if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: set_beam_mode: ") + baz_music_strerror(rc));
+}
+
+std::vector<gr_complex> baz_music_doa::last_beams(unsigned int items)
+{
+    const size_t per = (size_t)d_n * (d_nsamples / d_m);
+    std::vector<gr_complex> out((size_t)items * per);
+    const int rc = baz_music_last_beams(d_ctx, reinterpret_cast<float*>(out.data()), items);
+    if (rc < 0) throw std::runtime_error(std::string("music_doa: last_beams: ") + baz_music_strerror(rc));
+    out.resize((size_t)rc * per);
+    return out;
+}
+
 void baz_music_doa::set_averaging(unsigned int window, double forgetting)
 {
     const int rc = baz_music_set_averaging(d_ctx, window, forgetting);

@@ -79,6 +79,12 @@ public:
      * last work() call in fp64. */
     void set_power_mode(int mode);
     std::vector<double> last_powers(unsigned int count);
+    /* Extension, off by default (not in the reference): the MVDR beamformer output y = w^H X of every reported entry over the item's
+     * own snapshots, w = R^-1 a / (a^H R^-1 a) (baz_music_set_beam_mode, include/baz_music_hip.h).  mode 1 computes them and leaves
+     * every port as it is; loading >= 0 adds loading * mean diagonal to R's diagonal.  last_beams: the beams of the first `items`
+     * items of the last work() call, [item][slot][K].  Not available while smoothing is on. */
+    void set_beam_mode(int mode, double loading = 0.0);
+    std::vector<gr_complex> last_beams(unsigned int items);
     /* Extension, off by default (not in the reference): every item's covariance becomes the weighted mean over the last `window`
      * items of the stream, weights forgetting^age (baz_music_set_averaging, include/baz_music_hip.h); window 1 is off.  The output
      * rate does not change.  reset_averaging forgets the history (start() does).  Throws std::invalid_argument unless

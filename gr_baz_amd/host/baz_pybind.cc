@@ -9,6 +9,8 @@
 
 #include <pybind11/complex.h>
 #include <pybind11/numpy.h>
+
+#include <cstring>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
@@ -245,6 +247,15 @@ PYBIND11_MODULE(_baz_music, mod)
         .def("set_refine_mode", [](music_doa_handle& h, bool on) { h.blk->set_refine_mode(on); }, py::arg("parabolic"))
         .def("set_power_mode", [](music_doa_handle& h, int mode) { h.blk->set_power_mode(mode); }, py::arg("mode"))
         .def("last_powers", [](music_doa_handle& h, unsigned int count) { return h.blk->last_powers(count); }, py::arg("count"))
+        .def("set_beam_mode", [](music_doa_handle& h, int mode, double loading) { h.blk->set_beam_mode(mode, loading); },
+             py::arg("mode"), py::arg("loading") = 0.0)
+        .def("last_beams", [](music_doa_handle& h, unsigned int items) {
+                 const std::vector<gr_complex> v = h.blk->last_beams(items);
+                 const size_t n = h.blk->n(), K = h.blk->nsamples() / h.blk->m();
+                 py::array_t<std::complex<float>> out({v.size() / (n * K), n, K});
+                 if (!v.empty()) memcpy(out.mutable_data(), v.data(), v.size() * sizeof(gr_complex));
+                 return out;
+             }, py::arg("items"))
         .def("set_averaging", [](music_doa_handle& h, unsigned int window, double forgetting) { h.blk->set_averaging(window, forgetting); },
              py::arg("window"), py::arg("forgetting") = 1.0)
         .def("reset_averaging", [](music_doa_handle& h) { h.blk->reset_averaging(); })

@@ -448,6 +448,62 @@ BAZ_MUSIC_API int baz_music_set_power_mode(baz_music_ctx* ctx, int mode);
 BAZ_MUSIC_API int baz_music_get_power_mode(const baz_music_ctx* ctx, int* mode);
 BAZ_MUSIC_API int baz_music_last_powers(baz_music_ctx* ctx, double* out, uint32_t count);
 BAZ_MUSIC_API int baz_music_power_estimate(uint32_t m, const double* R_ri, const float* a_ri, uint32_t count, double* out);
+/* OPT-IN extension, NOT reference behaviour: the signal that arrives from every reported entry's direction, the other
+ * emitters suppressed.  The Capon power of the power mode is the output power of the minimum-variance distortionless-response (MVDR)
+ * beamformer w = R^-1 a / (a^H R^-1 a); this mode produces the weight vector itself and applies it to the item's snapshots on the device.
+ * mode: 0 = off (the default, the reference), 1 = MVDR; loading: a finite double >= 0 (default 0), the diagonal loading in units of the
+ * mean diagonal of R; anything else BAZ_MUSIC_E_INVALID and the previous setting stays in force.
+ *   DEFINITION  for every reported REAL entry (item, slot) -- lvl != 0 after the merge, the peak picker or the count truncation -- with b,
+ *               a and R taken as the power mode takes them (the GRID bin also under refinement; row b of the table in force, widened
+ *               exactly; the covariance the item's EVD decomposes, what baz_music_debug_cov returns, Rbar_t with averaging on):
+ *                 R_l  = R with loading (sum_i Re R_ii) / m added to the real diagonal (the trace summed in index order, the imaginary
+ *                        part of the diagonal ignored)
+ *               and in fp64, by the power mode's UNPIVOTED LDL^H of R_l from the lower triangle as stored, the same pivot rule against
+ *               BAZ_MUSIC_POWER_PIVOT_FLOOR times the mean diagonal of R_l:
+ *                 z_i  = a_i - sum_{k<i} L_ik z_k
+ *                 s    = sum_i |z_i|^2 / d_i
+ *                 u_i  = z_i / d_i - sum_{k>i} conj(L_ki) u_k
+ *                 w    = u / s                                      (so that w^H a = 1)
+ *                 y[c] = sum_{r<m} conj(w_r) x[c m + r]             (c = 0 .. K-1, K = nsamples / m)
+ *               x: the item's OWN K snapshots, complex64 widened exactly, also under averaging (averaging changes R, not x); the sum in
+ *               fp64 in the order r = 0 .. m-1, stored as complex64.  A DEGENERATE item (a failing pivot) gets w = 0 and y = 0 for all
+ *               its entries; an entry whose s is 0 or not finite gets w = 0 and y = 0; a missing entry gets w = 0 and y = 0.  With
+ *               loading > 0 an item with K < m snapshots is no longer degenerate (that is the point of loading); an all-zero item still
+ *               is (its trace is 0).  R -> sR leaves w unchanged, exactly so for s a power of two.  tests/beam_ref.py restates this in
+ *               numpy.  ang, lvl and the spectrum never change under this mode; the power mode keeps its own definition on the unloaded R.
+ *   WHAT RUNS   two kernels (gr_baz_amd/csrc/beam_kernels.hip.h), the last launches of a sequence (behind refinement and the power mode
+ *               where they are on): beam_weights_kernel, one item per group of 4 / 8 / 16 lanes, R read and factorised once per item; and
+ *               beam_apply_kernel, which reads the batch's input a second time and writes n K complex64 per item.  While the mode is on
+ *               the pickers write into the staging buffer refinement and the power mode use, and the final kernels write the caller's
+ *               ang / lvl, every word once (with neither of those modes on: beam_weights_kernel).  Both launches count under
+ *               BAZ_MUSIC_STAGE_MERGE.  At 4 antennas with K % 256 == 0 the fused covariance + EVD kernel keeps running and also stores
+ *               its R (the tap of debug_cov).  A host-fed call applies every chunk's weights to the chunk's device copy of the input; on
+ *               the zero-copy path (a small call on page-locked memory) the apply kernel reads the caller's mapped input a second time
+ *               over the link.  Mode 0 launches exactly the kernels it launched before the mode existed, allocates nothing new and is the
+ *               reference bit for bit: a context never set, one set to 0, one switched on and off again.
+ *   SCOPE       up to BAZ_MUSIC_FAST_M antennas (BAZ_MUSIC_E_UNSUPPORTED beyond), like the other modes.  Composes with peak mode, the
+ *               emitter-count mode (entries beyond an item's count are missing entries), refinement, the power mode and averaging.  It
+ *               does NOT compose with baz_music_set_smoothing (the inner context works on re-stacked sub-array items: there is no
+ *               m-antenna weight vector to apply): set_beam_mode(1, ..) while smoothing is on and set_smoothing(on) while this mode is on
+ *               return BAZ_MUSIC_E_UNSUPPORTED, the setting already in force stays.
+ *   WHEN        set_beam_mode takes effect for items submitted after it returns and is serialised against process*() like
+ *               set_peak_mode: a batch sees the old setting or the new one.
+ * last_beams: the beams of the first `items` items of the LAST process*() call in call order, [item][slot][K] complex64 (re / im
+ * interleaved); covers all chunks of a host-fed call; blocks until that call is done; returns the number of items written, or < 0.  A call
+ * that ran with the mode off reports zeros.  last_beams_device: the device buffer behind last_beams and its item count (NULL and 0 after a
+ * call made with the mode off), for consumers that stay on the GPU; valid until the next process*(), set_* or destroy of the context;
+ * ordered on the context's stream, it does not synchronise.  last_beam_weights: w as [item][slot][m] complex128, the call semantics of
+ * last_beams.  The buffers (8 n K and 16 n m bytes per item of the call) are allocated only by calls made with the mode on;
+ * baz_music_reserve pre-allocates them while the mode is on.  beam_weights needs no device: one R (m*m complex128, row-major, re / im
+ * interleaved) and `count` steering rows (m complex64 each) give `count` weight vectors (m complex128 each) by the definition above, the
+ * degeneracy rule and the s -> w step being the kernels' own text; 1 <= m <= BAZ_MUSIC_MAX_M; BAZ_MUSIC_E_INVALID for m out of range, a
+ * loading that is negative or not finite, or a NULL array with count > 0. */
+BAZ_MUSIC_API int baz_music_set_beam_mode(baz_music_ctx* ctx, int mode, double loading);
+BAZ_MUSIC_API int baz_music_get_beam_mode(const baz_music_ctx* ctx, int* mode, double* loading);
+BAZ_MUSIC_API int baz_music_last_beams(baz_music_ctx* ctx, float* out_ri, uint32_t items);
+BAZ_MUSIC_API int baz_music_last_beams_device(baz_music_ctx* ctx, const void** d_beams, uint32_t* items);
+BAZ_MUSIC_API int baz_music_last_beam_weights(baz_music_ctx* ctx, double* out_ri, uint32_t items);
+BAZ_MUSIC_API int baz_music_beam_weights(uint32_t m, const double* R_ri, const float* a_ri, uint32_t count, double loading, double* w_ri);
 /* Statistic: how many (item, bin) values of the LAST process call were recomputed in the reference's literal form
  * ||G^H a||^2 because the projector form a^H Q a put them at or below ~m 1e-8 max||a||^2 (near-nulls of the noise
  * subspace, SNR >~ 55 dB); blocks until that call is done (a host-fed call cut into chunks reports their sum).
