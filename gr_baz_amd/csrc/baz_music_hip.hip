@@ -21,6 +21,7 @@
 #include "average_kernels.hip.h"
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -144,6 +145,24 @@ struct StageProf {
 // (pageable caller memory: the runtime blocks in those copies anyway), all four when the whole call is enqueued without the host
 // waiting for anything (page-locked caller memory, round 6)
 constexpr int BAZ_MUSIC_NSLOT = 4;
+
+// The per-call side output of one opt-in mode: what the mode's kernels leave per item of a whole process*() call, all chunks in call
+// order, for its baz_music_last_*() reader.  One or two buffers behind one count (the beam mode: beams and weights).  Nothing is
+// allocated while the mode is off.  The steps -- open a call, refuse / place a chunk, reserve, read back -- are the side_*()
+// functions below; every mode goes through them.
+struct SideOut {
+    struct Buf {
+        uint8_t* p = nullptr;
+        size_t cap = 0;              // bytes
+        size_t item_bytes = 0;       // bytes per item of a call (baz_music_create); 0: this mode has no such buffer
+    } buf[2];
+    uint32_t count = 0;              // items of the call in flight / the last call recorded so far (the next chunk's offset)
+    bool on = false;                 // whether the last process*() call ran with the mode on (else the reader reports a constant)
+    const char* what = "";           // the name a refused chunk reports
+    // where the chunk at `count` goes in buffer k
+    template <typename T>
+    T* chunk(int k = 0) const { return reinterpret_cast<T*>(buf[k].p + (size_t)count * buf[k].item_bytes); }
+};
 
 struct baz_music_ctx {
     uint32_t m = 0, n = 0, nsamples = 0, res = 0, K = 0;
@@ -291,15 +310,12 @@ struct baz_music_ctx {
     int peak_mode = 0;      // 0: the reference's n strongest bins; 1 (opt-in extension): n strongest local maxima
     float* dPeakSpec = nullptr;   // internal spectrum when peak mode runs without the spectrum port
     size_t peak_spec_cap = 0;     // floats
+    uint32_t call_items = 0;        // items of the last process*() call: what the reader of a mode that was off reports on (the out_* below)
     // Opt-in per-item emitter count (baz_music_set_order_mode; NOT reference behaviour; order_kernels.hip.h).  While
     // order_mode is 0 none of the mode's kernels is launched and nothing below is allocated on the process path.
     int order_mode = 0;             // 0: the fixed n of the reference; 1 MDL, 2 AIC: n is the largest count
     uint32_t order_nsnap = 0;       // snapshots N of the criterion; 0: K (the smoothing mode hands its inner context the outer K)
-    uint8_t* dOrd = nullptr;        // counts of the items of the last process*() call, in call order (all chunks)
-    size_t ord_cap = 0;
-    uint32_t ord_count = 0;         // items of the call in flight / the last call recorded so far (the next chunk's offset)
-    uint32_t ord_items = 0;         // items of the last process*() call
-    bool ord_on = false;            // ... and whether it ran with the mode on (else every count is n)
+    SideOut out_ord;                // one count (uint8) per item; after a call with the mode off every count is n
     bool ord_driven = false;        // an inner context of the smoothing mode: the outer context opens the call (order_begin)
     uint8_t* ord_cur = nullptr;     // where the EVD launched next writes its counts (null: a debug tap -> dOrdTap)
     uint8_t* dOrdTap = nullptr;     // counts of the debug taps' EVD launches (never read back)
@@ -309,28 +325,19 @@ struct baz_music_ctx {
     int refine_mode = 0;            // 0: ang on the grid (the reference); 1: parabolic fit of the null
     float* dRefAl = nullptr;        // ang | lvl of the chunk in flight as the pickers leave them (refine_kernel writes the caller's)
     size_t ref_al_cap = 0;          // floats
-    double* dRefOff = nullptr;      // delta per (item, slot) of the last process*() call, in call order (all chunks)
-    size_t ref_off_cap = 0;         // doubles
-    uint32_t ref_count = 0;         // items of the call in flight recorded so far (the next chunk's offset)
-    bool ref_on = false;            // whether the last process*() call ran with the mode on (else every offset is 0)
+    SideOut out_ref;                // delta (double) per (item, slot); after a call with the mode off every offset is 0
     // Opt-in per-emitter Capon power (baz_music_set_power_mode; NOT reference behaviour; power_kernels.hip.h).  While
     // power_mode is 0 its kernel is not launched and nothing below is allocated.  The pickers' staging buffer is dRefAl, shared with
     // the refinement: one buffer with either mode or both on.
     int power_mode = 0;             // 0: off (the reference); 1: the estimates behind baz_music_last_powers; 2: ... and lvl carries (float)P
-    double* dPow = nullptr;         // P per (item, slot) of the last process*() call, in call order (all chunks)
-    size_t pow_cap = 0;             // doubles
-    uint32_t pow_count = 0;         // items of the call in flight recorded so far (the next chunk's offset)
-    bool pow_on = false;            // whether the last process*() call ran with the mode on (else every power is 0)
+    SideOut out_pow;                // P (double) per (item, slot); after a call with the mode off every power is 0
     // Opt-in MVDR beamformer output per reported entry (baz_music_set_beam_mode; NOT reference behaviour; beam_kernels.hip.h, DESIGN.md
     // 8g).  While beam_mode is 0 its two kernels are not launched and nothing below is allocated.  The pickers' staging buffer is dRefAl.
     int beam_mode = 0;              // 0: off (the reference); 1: MVDR
     double beam_loading = 0.0;      // diagonal loading, in units of the mean diagonal of R
-    float2* dBeam = nullptr;        // y per (item, slot, snapshot) of the last process*() call, in call order (all chunks)
-    size_t beam_cap = 0;            // complex64
-    double2* dBeamW = nullptr;      // w per (item, slot, antenna) of the last process*() call, in call order (all chunks)
-    size_t beam_w_cap = 0;          // complex128
-    uint32_t beam_count = 0;        // items of the call in flight recorded so far (the next chunk's offset)
-    bool beam_on = false;           // whether the last process*() call ran with the mode on (else every beam is 0)
+    enum { BEAM_Y = 0, BEAM_W = 1 };
+    SideOut out_beam;               // [BEAM_Y] y (complex64) per (item, slot, snapshot), [BEAM_W] w (complex128) per (item, slot, antenna);
+                                    // after a call with the mode off every beam and weight is 0
     // Opt-in covariance averaging across the items of the stream (baz_music_set_averaging; NOT reference behaviour; average_kernels.hip.h,
     // DESIGN.md 8e).  While avg_window is 1 none of the mode's kernels is launched and nothing below is allocated.
     uint32_t avg_window = 1;        // W: 1 = off (the reference)
@@ -780,36 +787,64 @@ int grow(baz_music_ctx* c, T*& p, size_t& cap, size_t need)
     return BAZ_MUSIC_OK;
 }
 
-// ---- emitter-count mode: bookkeeping --------------------------------------------------------------------------------------------
+// ---- the opt-in modes' per-call side outputs (SideOut) --------------------------------------------------------------------------
 int grow_bytes(baz_music_ctx* c, uint8_t*& p, size_t& cap, size_t need) { return grow(c, p, cap, (need + 255) / 256 * 256); }
 
-// Opens a process*() call of `items` items for baz_music_last_orders, baz_music_last_refine_offsets and baz_music_last_powers: the
-// counts / offsets / powers of all its chunks land in dOrd / dRefOff / dPow in call order.  With the modes off this is seven stores.
+// the four records of a context, each with whether its mode is on now
+struct SideMode { SideOut* out; bool mode_on; };
+std::array<SideMode, 4> side_modes(baz_music_ctx* c)
+{
+    return {{{&c->out_ord, c->order_mode != 0}, {&c->out_ref, c->refine_mode != 0}, {&c->out_pow, c->power_mode != 0}, {&c->out_beam, c->beam_mode != 0}}};
+}
+
+// room for a call of `items` items
+int side_grow(baz_music_ctx* c, SideOut& s, uint32_t items)
+{
+    for (SideOut::Buf& b : s.buf)
+        if (const int r = grow_bytes(c, b.p, b.cap, (size_t)items * b.item_bytes)) return r;
+    return BAZ_MUSIC_OK;
+}
+
+// Opens a process*() call of `items` items for the modes' readers: the counts / offsets / powers / beams of all its chunks land in
+// their buffers in call order.  With the modes off this is nine stores.
 int order_begin(baz_music_ctx* c, uint32_t items)
 {
-    c->ord_count = 0;
-    c->ord_items = items;
-    c->ord_on = c->order_mode != 0;
-    c->ref_count = 0;
-    c->ref_on = c->refine_mode != 0;
-    if (c->ref_on) {
-        const int r = grow(c, c->dRefOff, c->ref_off_cap, (size_t)items * c->n);
-        if (r) return r;
+    c->call_items = items;
+    for (const SideMode& md : side_modes(c)) {
+        md.out->count = 0;
+        md.out->on = md.mode_on;
+        if (const int r = md.mode_on ? side_grow(c, *md.out, items) : BAZ_MUSIC_OK) return r;
     }
-    c->pow_count = 0;
-    c->pow_on = c->power_mode != 0;
-    if (c->pow_on) {
-        const int r = grow(c, c->dPow, c->pow_cap, (size_t)items * c->n);
-        if (r) return r;
+    return BAZ_MUSIC_OK;
+}
+
+int refuse_null(baz_music_ctx* c, const void* p, const char* name);     // (below, next to process_device_locked)
+
+// A chunk of `batch` items under a mode that is on: refused unless the call was opened with the mode on (order_begin) and the chunk
+// ends inside what the call was sized for.
+int side_refuse(baz_music_ctx* c, const SideMode& md, uint32_t batch)
+{
+    if (!md.mode_on) return BAZ_MUSIC_OK;
+    bool fits = md.out->on;
+    for (const SideOut::Buf& b : md.out->buf)
+        fits = fits && (!b.item_bytes || (b.p && ((size_t)md.out->count + batch) * b.item_bytes <= b.cap));
+    return fits ? BAZ_MUSIC_OK : refuse_null(c, nullptr, md.out->what);
+}
+
+// The first `count` units of the last call's buffer k -> out, `per_item` units to an item (so a unit is item_bytes / per_item bytes);
+// returns how many there were.  After a call made with the mode off: the byte `fill` for every unit of its `off_items` items.
+int side_read(baz_music_ctx* c, const SideOut& s, int k, void* out, uint32_t count, uint32_t per_item, int fill, uint32_t off_items)
+{
+    DeviceGuard guard(c->device);
+    const size_t unit = s.buf[k].item_bytes / per_item;
+    const uint32_t have = (uint32_t)std::min<uint64_t>(count, (uint64_t)(s.on ? s.count : off_items) * per_item);
+    if (!s.on) {
+        if (have) memset(out, fill, have * unit);
+        return (int)have;
     }
-    c->beam_count = 0;
-    c->beam_on = c->beam_mode != 0;
-    if (c->beam_on) {
-        int r = grow(c, c->dBeam, c->beam_cap, (size_t)items * c->n * c->K);
-        if (r == BAZ_MUSIC_OK) r = grow(c, c->dBeamW, c->beam_w_cap, (size_t)items * c->n * c->m);
-        if (r) return r;
-    }
-    return c->ord_on ? grow_bytes(c, c->dOrd, c->ord_cap, items) : BAZ_MUSIC_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (have) HIP_TRY(c, hipMemcpy(out, s.buf[k].p, have * unit, hipMemcpyDeviceToHost));
+    return (int)have;
 }
 
 // the ORDER kernels' extra arguments for an EVD launch over `batch` items
@@ -964,8 +999,6 @@ int launch_evd(baz_music_ctx* c, const double2* dR, uint32_t batch, double* dQ, 
 }
 
 // ---- opt-in covariance averaging across the items of the stream (average_kernels.hip.h) ------------------------------------------
-int refuse_null(baz_music_ctx* c, const void* p, const char* name);     // (below, next to process_device_locked)
-
 // The mode's buffers: both history buffers for a window of W items (zero-filled on the launch stream when they are allocated, so
 // slots in front of the stream's start hold defined values; they are never taps) and, for `items` > 0, the averaged covariances.
 // Growing a history buffer loses its contents: only a change of W does that, and it resets the history anyway.
@@ -2264,14 +2297,14 @@ int launch_refine_t(baz_music_ctx* c, const bazrefine::RefineArgs& A)
 int launch_refine(baz_music_ctx* c, uint32_t batch, uint32_t qstride, float* d_ang, float* d_lvl)
 {
     ProfScope ps(c, BAZ_MUSIC_STAGE_MERGE);
-    BAZ_REQUIRE(c, dRefAl); BAZ_REQUIRE(c, dRefOff); BAZ_REQUIRE_TAB(c, dRW);
+    BAZ_REQUIRE(c, dRefAl); BAZ_REQUIRE_TAB(c, dRW);
     bazrefine::RefineArgs A;
     const size_t entries = (size_t)batch * c->n;
     A.ang_in = c->dRefAl;
     A.lvl_in = c->dRefAl + entries;
     A.ang_out = d_ang;
     A.lvl_out = d_lvl;
-    A.off_out = c->dRefOff + (size_t)c->ref_count * c->n;
+    A.off_out = c->out_ref.chunk<double>();
     // (where the scan runs its short form the EVD writes no projector coefficients, launch_evd_t: the literal form throughout)
     A.Qs = short_form_in_use(c) ? nullptr : c->dQ;
     A.Gs = c->dG;
@@ -2285,6 +2318,24 @@ int launch_refine(baz_music_ctx* c, uint32_t batch, uint32_t qstride, float* d_a
         default: return BAZ_MUSIC_E_UNSUPPORTED;
     }
 #undef BAZ_CALL
+}
+
+// What PowerArgs and BeamWeightsArgs share (capon_kernel of capon_solve.hip.h): the staged ang | lvl, the caller's ang / lvl where this
+// kernel is the one to write them (d_ang / d_lvl null: nothing), the covariances this sequence's EVD read, the raw table in force.
+template <class Args>
+int capon_args(baz_music_ctx* c, uint32_t batch, float* d_ang, float* d_lvl, Args& A)
+{
+    BAZ_REQUIRE(c, dRefAl); BAZ_REQUIRE_TAB(c, dRW);
+    if (c->avg_window > 1) BAZ_REQUIRE(c, dRavg); else BAZ_REQUIRE(c, dR);
+    A.ang_in = c->dRefAl;
+    A.lvl_in = c->dRefAl + (size_t)batch * c->n;
+    A.ang_out = d_ang;
+    A.lvl_out = d_lvl;
+    A.R = c->avg_window > 1 ? c->dRavg : c->dR;      // what launch_frontend handed to the EVD
+    A.raw = c->tab.dRW;
+    A.rel_floor = BAZ_MUSIC_POWER_PIVOT_FLOOR;
+    A.batch = batch; A.n = c->n; A.res = c->res;
+    return BAZ_MUSIC_OK;
 }
 
 // Opt-in Capon power of the chunk's entries (power_kernels.hip.h), the last launch of a sequence: reads the staged ang | lvl (ang on the
@@ -2302,19 +2353,9 @@ int launch_power_t(baz_music_ctx* c, const bazpower::PowerArgs& A)
 int launch_power(baz_music_ctx* c, uint32_t batch, float* d_ang, float* d_lvl)
 {
     ProfScope ps(c, BAZ_MUSIC_STAGE_MERGE);
-    BAZ_REQUIRE(c, dRefAl); BAZ_REQUIRE(c, dPow); BAZ_REQUIRE_TAB(c, dRW);
-    if (c->avg_window > 1) BAZ_REQUIRE(c, dRavg); else BAZ_REQUIRE(c, dR);
     bazpower::PowerArgs A;
-    const size_t entries = (size_t)batch * c->n;
-    A.ang_in = c->dRefAl;
-    A.lvl_in = c->dRefAl + entries;
-    A.ang_out = d_ang;
-    A.lvl_out = d_lvl;
-    A.pow_out = c->dPow + (size_t)c->pow_count * c->n;
-    A.R = c->avg_window > 1 ? c->dRavg : c->dR;      // what launch_frontend handed to the EVD
-    A.raw = c->tab.dRW;
-    A.rel_floor = BAZ_MUSIC_POWER_PIVOT_FLOOR;
-    A.batch = batch; A.n = c->n; A.res = c->res;
+    if (const int r = capon_args(c, batch, d_ang, d_lvl, A)) return r;
+    A.pow_out = c->out_pow.chunk<double>();
     A.lvl_is_power = c->power_mode == 2;
 #define BAZ_CALL(MV) launch_power_t<MV>(c, A)
     switch (c->m) {
@@ -2338,20 +2379,10 @@ int launch_beam_weights_t(baz_music_ctx* c, const bazbeam::BeamWeightsArgs& A)
 int launch_beam_weights(baz_music_ctx* c, uint32_t batch, float* d_ang, float* d_lvl)
 {
     ProfScope ps(c, BAZ_MUSIC_STAGE_MERGE);
-    BAZ_REQUIRE(c, dRefAl); BAZ_REQUIRE(c, dBeamW); BAZ_REQUIRE_TAB(c, dRW);
-    if (c->avg_window > 1) BAZ_REQUIRE(c, dRavg); else BAZ_REQUIRE(c, dR);
     bazbeam::BeamWeightsArgs A;
-    const size_t entries = (size_t)batch * c->n;
-    A.ang_in = c->dRefAl;
-    A.lvl_in = c->dRefAl + entries;
-    A.ang_out = d_ang;
-    A.lvl_out = d_lvl;
-    A.w_out = c->dBeamW + (size_t)c->beam_count * c->n * c->m;
-    A.R = c->avg_window > 1 ? c->dRavg : c->dR;      // what launch_frontend handed to the EVD
-    A.raw = c->tab.dRW;
-    A.rel_floor = BAZ_MUSIC_POWER_PIVOT_FLOOR;
+    if (const int r = capon_args(c, batch, d_ang, d_lvl, A)) return r;
+    A.w_out = c->out_beam.chunk<double2>(baz_music_ctx::BEAM_W);
     A.loading = c->beam_loading;
-    A.batch = batch; A.n = c->n; A.res = c->res;
 #define BAZ_CALL(MV) launch_beam_weights_t<MV>(c, A)
     switch (c->m) {
         BAZ_M_CASES(BAZ_CALL)
@@ -2383,11 +2414,10 @@ int launch_beam_apply_t(baz_music_ctx* c, const bazbeam::BeamApplyArgs& A)
 int launch_beam_apply(baz_music_ctx* c, const void* d_in, uint32_t batch)
 {
     ProfScope ps(c, BAZ_MUSIC_STAGE_MERGE);
-    BAZ_REQUIRE(c, dBeam); BAZ_REQUIRE(c, dBeamW);
     bazbeam::BeamApplyArgs A;
     A.x = static_cast<const float2*>(d_in);
-    A.w = c->dBeamW + (size_t)c->beam_count * c->n * c->m;
-    A.y = c->dBeam + (size_t)c->beam_count * c->n * c->K;
+    A.w = c->out_beam.chunk<double2>(baz_music_ctx::BEAM_W);
+    A.y = c->out_beam.chunk<float2>(baz_music_ctx::BEAM_Y);
     A.batch = batch; A.n = c->n; A.K = c->K;
     A.nseg = (c->K + bazbeam::APPLY_SEG - 1) / bazbeam::APPLY_SEG;
     if ((uint64_t)batch * A.nseg > 0x7fffffffull * bazbeam::APPLY_WAVES) return BAZ_MUSIC_E_UNSUPPORTED;   // (the grid's x extent)
@@ -2429,12 +2459,11 @@ int process_device_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void
     r = check_launch_pointers(c);
     if (r) return r;
     const uint32_t qstride = baz_music_q_stride(batch);
-    // emitter-count mode: this chunk's counts go behind those of the call's earlier chunks (order_begin sized dOrd for the call)
-    uint8_t* const ord = c->order_mode ? c->dOrd + c->ord_count : nullptr;
-    if (c->order_mode) {
-        if (!c->ord_on || !c->dOrd || (size_t)c->ord_count + batch > c->ord_cap) return refuse_null(c, nullptr, "dOrd (order_begin)");
-        c->ord_cur = ord;
-    }
+    // the modes' side outputs: this chunk's go behind those of the call's earlier chunks (order_begin sized the buffers for the call)
+    for (const SideMode& md : side_modes(c))
+        if (const int rs = side_refuse(c, md, batch)) return rs;
+    uint8_t* const ord = c->order_mode ? c->out_ord.chunk<uint8_t>() : nullptr;
+    c->ord_cur = ord;
     r = launch_frontend(c, d_in, batch, c->dQ, qstride);
     c->ord_cur = nullptr;
     if (r) return r;
@@ -2449,13 +2478,6 @@ int process_device_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void
     float* ang = static_cast<float*>(d_ang);
     float* lvl = static_cast<float*>(d_lvl);
     const size_t entries = (size_t)batch * c->n;
-    if (c->refine_mode && (!c->ref_on || !c->dRefOff || ((size_t)c->ref_count + batch) * c->n > c->ref_off_cap))
-        return refuse_null(c, nullptr, "dRefOff (order_begin)");
-    if (c->power_mode && (!c->pow_on || !c->dPow || ((size_t)c->pow_count + batch) * c->n > c->pow_cap))
-        return refuse_null(c, nullptr, "dPow (order_begin)");
-    if (c->beam_mode && (!c->beam_on || !c->dBeam || !c->dBeamW || ((size_t)c->beam_count + batch) * c->n * c->K > c->beam_cap ||
-                         ((size_t)c->beam_count + batch) * c->n * c->m > c->beam_w_cap))
-        return refuse_null(c, nullptr, "dBeam (order_begin)");
     if (c->refine_mode || c->power_mode || c->beam_mode) {
         r = grow(c, c->dRefAl, c->ref_al_cap, entries * 2);
         if (r) return r;
@@ -2476,28 +2498,28 @@ int process_device_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void
         hipLaunchKernelGGL(bazorder::order_truncate_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, c->stream,
                            ang, lvl, ord, batch, c->n);
         HIP_TRY(c, hipGetLastError());
-        c->ord_count += batch;
+        c->out_ord.count += batch;
     }
     if (c->refine_mode) {
         // (with power mode 2 and port 1 wired, power_kernel writes lvl: every caller-visible word is written once)
         const bool lvl_later = c->power_mode == 2 && d_lvl;
         r = launch_refine(c, batch, qstride, static_cast<float*>(d_ang), lvl_later ? nullptr : static_cast<float*>(d_lvl));
         if (r) return r;
-        c->ref_count += batch;
+        c->out_ref.count += batch;
     }
     if (c->power_mode) {           // ang / lvl where refine_kernel has not written them
         float* const p_ang = c->refine_mode ? nullptr : static_cast<float*>(d_ang);
         float* const p_lvl = (c->refine_mode && c->power_mode != 2) ? nullptr : static_cast<float*>(d_lvl);
         r = launch_power(c, batch, p_ang, p_lvl);
         if (r) return r;
-        c->pow_count += batch;
+        c->out_pow.count += batch;
     }
     if (c->beam_mode) {            // the last two launches: ang / lvl where neither refine_kernel nor power_kernel has written them
         const bool earlier = c->refine_mode || c->power_mode;
         r = launch_beam_weights(c, batch, earlier ? nullptr : static_cast<float*>(d_ang), earlier ? nullptr : static_cast<float*>(d_lvl));
         if (r == BAZ_MUSIC_OK) r = launch_beam_apply(c, d_in, batch);
         if (r) return r;
-        c->beam_count += batch;
+        c->out_beam.count += batch;
     }
     return BAZ_MUSIC_OK;
 }
@@ -2782,6 +2804,12 @@ int baz_music_create(baz_music_ctx** out, uint32_t m, uint32_t n, uint32_t nsamp
     baz_music_ctx* c = new (std::nothrow) baz_music_ctx;
     if (!c) return BAZ_MUSIC_E_NOMEM;
     c->m = m; c->n = n; c->nsamples = nsamples; c->res = resolution; c->K = nsamples / m;
+    c->out_ord.buf[0].item_bytes = 1;                                   c->out_ord.what = "dOrd (order_begin)";
+    c->out_ref.buf[0].item_bytes = (size_t)n * sizeof(double);          c->out_ref.what = "dRefOff (order_begin)";
+    c->out_pow.buf[0].item_bytes = (size_t)n * sizeof(double);          c->out_pow.what = "dPow (order_begin)";
+    c->out_beam.buf[baz_music_ctx::BEAM_Y].item_bytes = (size_t)n * c->K * sizeof(float2);
+    c->out_beam.buf[baz_music_ctx::BEAM_W].item_bytes = (size_t)n * m * sizeof(double2);
+    c->out_beam.what = "dBeam (order_begin)";
     c->device = dev;
     if (const char* v = BAZ_LAB_ENV("BAZ_MUSIC_SCAN_VARIANT")) c->lab_variant = atoi(v);
     if (const char* v = getenv("BAZ_MUSIC_CHUNK_MIB")) c->chunk_bytes = (size_t)std::max(1, std::min(1024, atoi(v))) << 20;
@@ -2966,13 +2994,11 @@ void baz_music_destroy(baz_music_ctx* c)
         if (c->dFire) (void)dev_free(c->dFire);
         if (c->hFire) (void)hipHostFree(c->hFire);
 #endif
-        if (c->dOrd) (void)dev_free(c->dOrd);
+        for (const SideMode& md : side_modes(c))
+            for (SideOut::Buf& b : md.out->buf)
+                if (b.p) (void)dev_free(b.p);
         if (c->dOrdTap) (void)dev_free(c->dOrdTap);
         if (c->dRefAl) (void)dev_free(c->dRefAl);
-        if (c->dRefOff) (void)dev_free(c->dRefOff);
-        if (c->dPow) (void)dev_free(c->dPow);
-        if (c->dBeam) (void)dev_free(c->dBeam);
-        if (c->dBeamW) (void)dev_free(c->dBeamW);
         if (c->dRavg) (void)dev_free(c->dRavg);
         if (c->dAvgHist[0]) (void)dev_free(c->dAvgHist[0]);
         if (c->dAvgHist[1]) (void)dev_free(c->dAvgHist[1]);
@@ -3051,25 +3077,10 @@ int baz_music_reserve(baz_music_ctx* c, uint32_t max_batch)
     std::lock_guard<std::mutex> lk(c->mtx);
     DeviceGuard guard(c->device);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->order_mode && !c->ord_driven) {   // emitter-count mode: one byte per item of a whole call (kept by the context that runs the kernels)
+    if (!c->ord_driven) {   // the modes' side outputs of a whole call, kept by the context that runs the kernels (whose modes mirror this one's)
         baz_music_ctx* const oc = c->sm.inner ? c->sm.inner : c;
-        const int ro = grow_bytes(oc, oc->dOrd, oc->ord_cap, max_batch);
-        if (ro) return ro;
-    }
-    if (c->refine_mode && !c->ord_driven) {  // refinement: one offset per entry of a whole call (kept by the context that runs the kernels)
-        baz_music_ctx* const oc = c->sm.inner ? c->sm.inner : c;
-        const int rr = grow(oc, oc->dRefOff, oc->ref_off_cap, (size_t)max_batch * oc->n);
-        if (rr) return rr;
-    }
-    if (c->power_mode && !c->ord_driven) {   // power mode: one estimate per entry of a whole call (kept by the context that runs the kernels)
-        baz_music_ctx* const oc = c->sm.inner ? c->sm.inner : c;
-        const int rp = grow(oc, oc->dPow, oc->pow_cap, (size_t)max_batch * oc->n);
-        if (rp) return rp;
-    }
-    if (c->beam_mode) {   // beam mode (never with smoothing on): the beams and weights of a whole call
-        int rb = grow(c, c->dBeam, c->beam_cap, (size_t)max_batch * c->n * c->K);
-        if (rb == BAZ_MUSIC_OK) rb = grow(c, c->dBeamW, c->beam_w_cap, (size_t)max_batch * c->n * c->m);
-        if (rb) return rb;
+        for (const SideMode& md : side_modes(oc))
+            if (const int ro = md.mode_on ? side_grow(oc, *md.out, max_batch) : BAZ_MUSIC_OK) return ro;
     }
     if (c->sm.inner) {   // smoothing on: the inner context's workspace for one chunk, and the re-stacked chunk
         const uint32_t chunk = smooth_chunk(c, max_batch);
@@ -3978,8 +3989,8 @@ int baz_music_set_smoothing(baz_music_ctx* c, uint32_t subarray, int forward_bac
         if (r == BAZ_MUSIC_OK) {
             inner->order_nsnap = c->K;            // N of the criterion: this context's snapshots, not the K' re-stacked columns
             inner->ord_driven = true;
-            c->beam_on = false;                   // (calls under smoothing run with the beam mode off: last_beams reports zeros)
-            c->beam_count = 0;
+            c->out_beam.on = false;               // (calls under smoothing run with the beam mode off: last_beams reports zeros)
+            c->out_beam.count = 0;
             old = c->sm.inner;
             c->sm.inner = inner;
             c->sm.ms = subarray; c->sm.L = L; c->sm.Kp = (uint32_t)Kp; c->sm.fb = fb;
@@ -4018,15 +4029,7 @@ int baz_music_last_orders(baz_music_ctx* c, uint8_t* out, uint32_t count)
     if (!c || (!out && count)) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
     if (c->sm.inner) return baz_music_last_orders(c->sm.inner, out, count);
-    DeviceGuard guard(c->device);
-    const uint32_t have = std::min(count, c->ord_on ? c->ord_count : c->ord_items);
-    if (!c->ord_on) {                              // the call ran with the mode off: every item used the context's n
-        if (have) memset(out, (int)c->n, have);
-        return (int)have;
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (have) HIP_TRY(c, hipMemcpy(out, c->dOrd, have, hipMemcpyDeviceToHost));
-    return (int)have;
+    return side_read(c, c->out_ord, 0, out, count, 1, (int)c->n, c->call_items);   // (mode off: every item used the context's n)
 }
 
 const void* baz_music_last_orders_device(baz_music_ctx* c)
@@ -4035,12 +4038,13 @@ const void* baz_music_last_orders_device(baz_music_ctx* c)
     std::lock_guard<std::mutex> lk(c->mtx);
     if (c->sm.inner) return baz_music_last_orders_device(c->sm.inner);
     DeviceGuard guard(c->device);
-    if (c->ord_on) return c->ord_count ? c->dOrd : nullptr;
-    if (!c->ord_items) return nullptr;
+    SideOut::Buf& b = c->out_ord.buf[0];
+    if (c->out_ord.on) return c->out_ord.count ? b.p : nullptr;
+    if (!c->call_items) return nullptr;
     // the call ran with the mode off: the same bytes as baz_music_last_orders, filled here (nothing on the process path)
-    if (grow_bytes(c, c->dOrd, c->ord_cap, c->ord_items) != BAZ_MUSIC_OK) return nullptr;
-    if (hipMemsetAsync(c->dOrd, (int)c->n, c->ord_items, c->stream) != hipSuccess) return nullptr;
-    return c->dOrd;
+    if (grow_bytes(c, b.p, b.cap, c->call_items) != BAZ_MUSIC_OK) return nullptr;
+    if (hipMemsetAsync(b.p, (int)c->n, c->call_items, c->stream) != hipSuccess) return nullptr;
+    return b.p;
 }
 
 int baz_music_order_estimate(uint32_t m, uint32_t nsnap, uint32_t n_max, int criterion, const double* eigvals_ascending,
@@ -4082,16 +4086,7 @@ int baz_music_last_refine_offsets(baz_music_ctx* c, double* out, uint32_t count)
     if (!c || (!out && count)) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
     if (c->sm.inner) return baz_music_last_refine_offsets(c->sm.inner, out, count);
-    DeviceGuard guard(c->device);
-    const uint64_t total = (uint64_t)(c->ref_on ? c->ref_count : c->ord_items) * c->n;
-    const uint32_t have = (uint32_t)std::min<uint64_t>(count, total);
-    if (!c->ref_on) {                              // the call ran with the mode off: nothing moved
-        if (have) memset(out, 0, (size_t)have * sizeof(double));
-        return (int)have;
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (have) HIP_TRY(c, hipMemcpy(out, c->dRefOff, (size_t)have * sizeof(double), hipMemcpyDeviceToHost));
-    return (int)have;
+    return side_read(c, c->out_ref, 0, out, count, c->n, 0, c->call_items);        // (mode off: nothing moved)
 }
 
 int baz_music_refine_estimate(const double* y3, uint32_t count, double* delta_out)
@@ -4188,64 +4183,17 @@ int baz_music_last_powers(baz_music_ctx* c, double* out, uint32_t count)
     if (!c || (!out && count)) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
     if (c->sm.inner) return baz_music_last_powers(c->sm.inner, out, count);
-    DeviceGuard guard(c->device);
-    const uint64_t total = (uint64_t)(c->pow_on ? c->pow_count : c->ord_items) * c->n;
-    const uint32_t have = (uint32_t)std::min<uint64_t>(count, total);
-    if (!c->pow_on) {                              // the call ran with the mode off: nothing was estimated
-        if (have) memset(out, 0, (size_t)have * sizeof(double));
-        return (int)have;
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (have) HIP_TRY(c, hipMemcpy(out, c->dPow, (size_t)have * sizeof(double), hipMemcpyDeviceToHost));
-    return (int)have;
+    return side_read(c, c->out_pow, 0, out, count, c->n, 0, c->call_items);        // (mode off: nothing was estimated)
 }
 
-// The definition of include/baz_music_hip.h loop for loop; the degeneracy rule and the s -> P step are power_kernel's own text.
+// The definition of include/baz_music_hip.h on the host (bazcapon::HostSolve); the degeneracy rule and the s -> P step are the kernel's own text.
 int baz_music_power_estimate(uint32_t m, const double* R_ri, const float* a_ri, uint32_t count, double* out)
 {
     if (m < 1 || m > BAZ_MUSIC_MAX_M) return BAZ_MUSIC_E_INVALID;
     if (count == 0) return BAZ_MUSIC_OK;
     if (!R_ri || !a_ri || !out) return BAZ_MUSIC_E_INVALID;
-    std::vector<double> Lr((size_t)m * m, 0.0), Li((size_t)m * m, 0.0), d(m, 0.0), zr(m), zi(m);
-    auto Rr = [&](uint32_t i, uint32_t j) { return R_ri[2 * ((size_t)i * m + j)]; };
-    auto Ri = [&](uint32_t i, uint32_t j) { return R_ri[2 * ((size_t)i * m + j) + 1]; };
-    double trace = 0.0;
-    for (uint32_t i = 0; i < m; ++i) trace += Rr(i, i);
-    const double floor = bazpower::power_pivot_floor(trace, m, BAZ_MUSIC_POWER_PIVOT_FLOOR);
-    bool ok = true;
-    for (uint32_t j = 0; j < m && ok; ++j) {
-        for (uint32_t i = j; i < m; ++i) {
-            double vr = Rr(i, j), vi = i == j ? 0.0 : Ri(i, j);
-            for (uint32_t k = 0; k < j; ++k) {     // L_ik conj(L_jk) d_k
-                const double wr = Lr[(size_t)j * m + k] * d[k], wi = Li[(size_t)j * m + k] * d[k];
-                vr -= Lr[(size_t)i * m + k] * wr + Li[(size_t)i * m + k] * wi;
-                if (i != j) vi -= Li[(size_t)i * m + k] * wr - Lr[(size_t)i * m + k] * wi;
-            }
-            if (i == j) {
-                d[j] = vr;
-                ok = bazpower::power_pivot_ok(vr, floor);
-                if (!ok) break;
-            } else {
-                Lr[(size_t)i * m + j] = vr / d[j];
-                Li[(size_t)i * m + j] = vi / d[j];
-            }
-        }
-    }
-    for (uint32_t e = 0; e < count; ++e) {
-        if (!ok) { out[e] = 0.0; continue; }
-        const float* a = a_ri + 2 * (size_t)e * m;
-        double s = 0.0;
-        for (uint32_t i = 0; i < m; ++i) {
-            double xr = (double)a[2 * i], xi = (double)a[2 * i + 1];
-            for (uint32_t k = 0; k < i; ++k) {
-                xr -= Lr[(size_t)i * m + k] * zr[k] - Li[(size_t)i * m + k] * zi[k];
-                xi -= Lr[(size_t)i * m + k] * zi[k] + Li[(size_t)i * m + k] * zr[k];
-            }
-            zr[i] = xr; zi[i] = xi;
-            s += (xr * xr + xi * xi) / d[i];
-        }
-        out[e] = bazpower::power_from_s(s);
-    }
+    bazcapon::HostSolve S(m, R_ri, nullptr, BAZ_MUSIC_POWER_PIVOT_FLOOR);
+    for (uint32_t e = 0; e < count; ++e) out[e] = S.ok ? bazcapon::power_from_s(S.solve(a_ri + 2 * (size_t)e * m)) : 0.0;
     return BAZ_MUSIC_OK;
 }
 
@@ -4270,19 +4218,11 @@ int baz_music_get_beam_mode(const baz_music_ctx* c, int* mode, double* loading)
 }
 
 namespace {
-// The first `items` items of the last call's beams (per = n K complex64) or weights (per = n m complex128): zeros after a mode-off call.
-int last_beam_copy(baz_music_ctx* c, void* out, const void* dev, uint32_t items, size_t item_bytes)
+// The first `items` items of the last call's beams or weights (buffer k): zeros after a mode-off call.
+int last_beam_copy(baz_music_ctx* c, void* out, int k, uint32_t items)
 {
-    DeviceGuard guard(c->device);
     // (a mode-off call under smoothing: the inner context counted the call's items)
-    const uint32_t have = std::min<uint32_t>(items, c->beam_on ? c->beam_count : (c->sm.inner ? c->sm.inner->ord_items : c->ord_items));
-    if (!c->beam_on) {
-        if (have) memset(out, 0, (size_t)have * item_bytes);
-        return (int)have;
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (have) HIP_TRY(c, hipMemcpy(out, dev, (size_t)have * item_bytes, hipMemcpyDeviceToHost));
-    return (int)have;
+    return side_read(c, c->out_beam, k, out, items, 1, 0, c->sm.inner ? c->sm.inner->call_items : c->call_items);
 }
 }  // namespace
 
@@ -4290,88 +4230,50 @@ int baz_music_last_beams(baz_music_ctx* c, float* out_ri, uint32_t items)
 {
     if (!c || (!out_ri && items)) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
-    return last_beam_copy(c, out_ri, c->dBeam, items, (size_t)c->n * c->K * sizeof(float2));
+    return last_beam_copy(c, out_ri, baz_music_ctx::BEAM_Y, items);
 }
 
 int baz_music_last_beam_weights(baz_music_ctx* c, double* out_ri, uint32_t items)
 {
     if (!c || (!out_ri && items)) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
-    return last_beam_copy(c, out_ri, c->dBeamW, items, (size_t)c->n * c->m * sizeof(double2));
+    return last_beam_copy(c, out_ri, baz_music_ctx::BEAM_W, items);
 }
 
 int baz_music_last_beams_device(baz_music_ctx* c, const void** d_beams, uint32_t* items)
 {
     if (!c || !d_beams || !items) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
-    *d_beams = c->beam_on ? c->dBeam : nullptr;     // (a call made with the mode off has no buffer: 0 items)
-    *items = c->beam_on ? c->beam_count : 0u;
+    *d_beams = c->out_beam.on ? c->out_beam.buf[baz_music_ctx::BEAM_Y].p : nullptr;     // (a call made with the mode off has no buffer: 0 items)
+    *items = c->out_beam.on ? c->out_beam.count : 0u;
     return BAZ_MUSIC_OK;
 }
 
-// The definition of include/baz_music_hip.h loop for loop; the degeneracy rule and the s -> w step are the kernels' own text.
+// The definition of include/baz_music_hip.h on the host (bazcapon::HostSolve on R plus the loading, then the back substitution); the
+// degeneracy rule and the s -> w step are the kernels' own text.
 int baz_music_beam_weights(uint32_t m, const double* R_ri, const float* a_ri, uint32_t count, double loading, double* w_ri)
 {
     if (m < 1 || m > BAZ_MUSIC_MAX_M || !(loading - loading == 0.0) || loading < 0.0) return BAZ_MUSIC_E_INVALID;
     if (count == 0) return BAZ_MUSIC_OK;
     if (!R_ri || !a_ri || !w_ri) return BAZ_MUSIC_E_INVALID;
-    std::vector<double> Lr((size_t)m * m, 0.0), Li((size_t)m * m, 0.0), d(m, 0.0), dg(m), zr(m), zi(m), ur(m), ui(m);
-    auto Rr = [&](uint32_t i, uint32_t j) { return i == j ? dg[i] : R_ri[2 * ((size_t)i * m + j)]; };
-    auto Ri = [&](uint32_t i, uint32_t j) { return R_ri[2 * ((size_t)i * m + j) + 1]; };
-    double trace = 0.0;
-    for (uint32_t i = 0; i < m; ++i) trace += R_ri[2 * ((size_t)i * m + i)];
-    const double delta = loading * (trace / (double)m);
-    double trace_l = 0.0;
-    for (uint32_t i = 0; i < m; ++i) {
-        dg[i] = R_ri[2 * ((size_t)i * m + i)] + delta;
-        trace_l += dg[i];
-    }
-    const double floor = bazpower::power_pivot_floor(trace_l, m, BAZ_MUSIC_POWER_PIVOT_FLOOR);
-    bool ok = true;
-    for (uint32_t j = 0; j < m && ok; ++j) {
-        for (uint32_t i = j; i < m; ++i) {
-            double vr = Rr(i, j), vi = i == j ? 0.0 : Ri(i, j);
-            for (uint32_t k = 0; k < j; ++k) {     // L_ik conj(L_jk) d_k
-                const double wr = Lr[(size_t)j * m + k] * d[k], wi = Li[(size_t)j * m + k] * d[k];
-                vr -= Lr[(size_t)i * m + k] * wr + Li[(size_t)i * m + k] * wi;
-                if (i != j) vi -= Li[(size_t)i * m + k] * wr - Lr[(size_t)i * m + k] * wi;
-            }
-            if (i == j) {
-                d[j] = vr;
-                ok = bazpower::power_pivot_ok(vr, floor);
-                if (!ok) break;
-            } else {
-                Lr[(size_t)i * m + j] = vr / d[j];
-                Li[(size_t)i * m + j] = vi / d[j];
-            }
-        }
-    }
+    bazcapon::HostSolve S(m, R_ri, &loading, BAZ_MUSIC_POWER_PIVOT_FLOOR);
+    std::vector<double> ur(m), ui(m);
     for (uint32_t e = 0; e < count; ++e) {
         double* const w = w_ri + 2 * (size_t)e * m;
-        if (!ok) {
+        if (!S.ok) {
             for (uint32_t i = 0; i < 2 * m; ++i) w[i] = 0.0;
             continue;
         }
-        const float* a = a_ri + 2 * (size_t)e * m;
-        double s = 0.0;
-        for (uint32_t i = 0; i < m; ++i) {
-            double xr = (double)a[2 * i], xi = (double)a[2 * i + 1];
-            for (uint32_t k = 0; k < i; ++k) {
-                xr -= Lr[(size_t)i * m + k] * zr[k] - Li[(size_t)i * m + k] * zi[k];
-                xi -= Lr[(size_t)i * m + k] * zi[k] + Li[(size_t)i * m + k] * zr[k];
-            }
-            zr[i] = xr; zi[i] = xi;
-            s += (xr * xr + xi * xi) / d[i];
-        }
+        const double s = S.solve(a_ri + 2 * (size_t)e * m);
         for (uint32_t i = m; i-- > 0;) {
-            double xr = zr[i] / d[i], xi = zi[i] / d[i];
+            double xr = S.zr[i] / S.d[i], xi = S.zi[i] / S.d[i];
             for (uint32_t k = m - 1; k > i; --k) {   // conj(L_ki) u_k
-                xr -= Lr[(size_t)k * m + i] * ur[k] + Li[(size_t)k * m + i] * ui[k];
-                xi -= Lr[(size_t)k * m + i] * ui[k] - Li[(size_t)k * m + i] * ur[k];
+                xr -= S.Lr[(size_t)k * m + i] * ur[k] + S.Li[(size_t)k * m + i] * ui[k];
+                xi -= S.Lr[(size_t)k * m + i] * ui[k] - S.Li[(size_t)k * m + i] * ur[k];
             }
             ur[i] = xr; ui[i] = xi;
         }
-        for (uint32_t i = 0; i < m; ++i) bazbeam::beam_w_from_u(ur[i], ui[i], s, true, &w[2 * i], &w[2 * i + 1]);
+        for (uint32_t i = 0; i < m; ++i) bazcapon::beam_w_from_u(ur[i], ui[i], s, true, &w[2 * i], &w[2 * i + 1]);
     }
     return BAZ_MUSIC_OK;
 }

@@ -1,28 +1,22 @@
 // beam_kernels.hip.h -- the opt-in MVDR beamformer output per reported entry (baz_music_set_beam_mode, include/baz_music_hip.h;
 // DESIGN.md 8g): w = R_l^-1 a / (a^H R_l^-1 a) for every reported entry, and y = w^H X over the item's own snapshots.
 //
-//   beam_w_from_u              the s -> w step, __host__ __device__: beam_weights_kernel and baz_music_beam_weights() compile the same
-//                              text (the degeneracy rule is power_kernels.hip.h's power_pivot_floor / power_pivot_ok, on R_l).
-//   beam_weights_kernel<M>     one item per group of W lanes (W = 4 / 8 / 16 for M <= 4 / 8 / 16), power_kernel's layout.
+//   beam_weights_kernel<M>     one item per group of W lanes (capon_solve.hip.h; its beam_w_from_u is the (u, s) -> w step).
 //   beam_apply_kernel<M>       one (item, run of 256 snapshots) per wave, one snapshot per lane and pass; the last launch of a sequence.
 //
 // DEFINITION.  R_l = R with loading (sum_i Re R_ii) / m added to the real diagonal (the trace summed in index order, the imaginary part
-// of the diagonal ignored).  Unpivoted LDL^H of R_l in fp64 from the lower triangle as stored, as power_kernels.hip.h states it, then
-//     z_i  = a_i - sum_{k<i} L_ik z_k                            (a: the table row, complex64 widened exactly)
-//     s    = sum_i |z_i|^2 / d_i
+// of the diagonal ignored).  The solve of capon_solve.hip.h on R_l (d, L, z, s, the degeneracy rule on R_l's own diagonal), then
 //     u_i  = z_i / d_i - sum_{k>i} conj(L_ki) u_k                (k = m-1 down to i+1)
 //     w    = u / s                                               (w^H a = 1)
 //     y[c] = sum_{r<m} conj(w_r) x[c m + r]                      (r = 0 .. m-1 in fp64, stored as complex64)
-// An item is DEGENERATE when some d_j is not finite or d_j <= 2^-40 (sum_i Re (R_l)_ii) / m: all its entries get w = 0.  An entry whose
-// s is 0 or not finite gets w = 0; a missing entry (lvl == 0) gets w = 0; w = 0 gives y = 0.
+// A dead entry gets w = 0; w = 0 gives y = 0.
 //
-// WEIGHTS LAYOUT.  As power_kernel: lane r of a group owns row r of R, the factorisation and the forward substitution go by width-W
-// shuffles that never leave a 16-lane row.  The back substitution needs COLUMN i of L in lane i: every lane writes its row of L into
-// LDS once per item (rows padded to an odd number of 16-byte elements: the writes of a group fall on distinct banks) and lane i reads
-// L_ki from row k -- the lanes of a group read neighbouring elements.  Each entry's back substitution then costs M - 1 broadcasts like
-// its forward one.  L^H stays in LDS (no second register copy of L: M = 16 would not fit beside the first).  A degenerate item, an
-// item beyond the batch or a lane beyond M runs the same instructions on zeros / garbage and only its stores differ: no lane leaves
-// before the last shuffle or the barrier.  Every word of the weights is written once, M contiguous complex128 per (item, slot).
+// WEIGHTS LAYOUT.  capon_kernel of capon_solve.hip.h with its beam blocks, the loading between the row load and the factorisation.  The
+// back substitution needs COLUMN i of L in lane i: every lane writes its row of L into LDS once per item (rows padded to an odd number of
+// 16-byte elements: the writes of a group fall on distinct banks) and lane i reads L_ki from row k -- the lanes of a group read
+// neighbouring elements.  Each entry's back substitution then costs M - 1 broadcasts like its forward one.  L^H stays in LDS (no
+// second register copy of L: M = 16 would not fit beside the first).  No lane leaves before the last shuffle or the barrier.  Every
+// word of the weights is written once, M contiguous complex128 per (item, slot).
 //
 // APPLY LAYOUT.  A wave works on one item at a time: its n M weights are copied into LDS once (with one flag per entry: has it
 // weights at all -- an entry without weights stores exact zeros whatever x holds) and every later read of them is a same-address
@@ -36,17 +30,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "power_kernels.hip.h"
+#include "capon_solve.hip.h"
 
 namespace bazbeam {
-
-// u, s -> w = u / s; an s that is 0 or not finite (or a dead item / missing entry: alive == false) gives w = 0
-__host__ __device__ inline void beam_w_from_u(const double ur, const double ui, const double s, const bool alive, double* wr, double* wi)
-{
-    const bool good = alive && (s - s == 0.0) && s != 0.0;
-    *wr = good ? ur / s : 0.0;
-    *wi = good ? ui / s : 0.0;
-}
 
 struct BeamWeightsArgs {
     const float* ang_in;       // [batch * n] what the merge / picker / truncation left (device staging), on the grid
@@ -63,114 +49,13 @@ struct BeamWeightsArgs {
 
 template <int M>
 struct BeamGeom {
-    static constexpr int W = bazpower::PowerGeom<M>::W;         // lanes per item
+    static constexpr int W = bazcapon::Group<M>::W;             // lanes per item
     static constexpr int THREADS = M <= 8 ? 256 : 128;          // (M > 8: half a block keeps the L^H tile under 40 KiB)
     static constexpr int IPB = THREADS / W;                     // items per block
-    static constexpr int S = M | 1;                             // row pitch of the L^H tile, in complex128
 };
 
 template <int M>
-__global__ __launch_bounds__(BeamGeom<M>::THREADS) void beam_weights_kernel(const BeamWeightsArgs A)
-{
-    using bazpower::group_bcast;
-    constexpr int W = BeamGeom<M>::W, S = BeamGeom<M>::S;
-    __shared__ double2 LT[BeamGeom<M>::IPB * M * S];
-    const uint32_t r = threadIdx.x % W;                                     // this lane's row
-    const uint64_t item = (uint64_t)blockIdx.x * BeamGeom<M>::IPB + threadIdx.x / W;
-    const bool live = item < A.batch;                                       // (uniform over the group)
-    const bool rowlane = live && r < (uint32_t)M;
-    double2* const lt = LT + (threadIdx.x / W) * (M * S);                   // this group's tile
-    // row r of R; zeros for lanes without a row
-    double lr[M], li[M];
-    {
-        const double2* __restrict__ row = A.R + ((size_t)(live ? item : 0) * M + (r < (uint32_t)M ? r : 0)) * M;
-#pragma unroll
-        for (int k = 0; k < M; ++k) {
-            const double2 v = rowlane ? row[k] : make_double2(0.0, 0.0);
-            lr[k] = v.x; li[k] = v.y;
-        }
-    }
-    // the loading, then the floor: both diagonals summed in index order (what the host routine does)
-    double trace = 0.0;
-#pragma unroll
-    for (int j = 0; j < M; ++j) trace += group_bcast(lr[j], j, W);
-    const double delta = A.loading * (trace / (double)M);
-#pragma unroll
-    for (int j = 0; j < M; ++j)
-        if (r == (uint32_t)j) lr[j] += delta;
-    double trace_l = 0.0;
-#pragma unroll
-    for (int j = 0; j < M; ++j) trace_l += group_bcast(lr[j], j, W);
-    const double floor = bazpower::power_pivot_floor(trace_l, (uint32_t)M, A.rel_floor);
-    // LDL^H, column by column (power_kernel's loop)
-    double d[M];
-    bool ok = true;
-    double dmine = 1.0;                                                     // d_r
-#pragma unroll
-    for (int j = 0; j < M; ++j) {
-        double vr = lr[j], vi = li[j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) {
-            const double pr = group_bcast(lr[k], j, W), pi = group_bcast(li[k], j, W);      // L_jk
-            const double wr = pr * d[k], wi = pi * d[k];
-            vr -= lr[k] * wr + li[k] * wi;
-            vi -= li[k] * wr - lr[k] * wi;
-        }
-        const double dj = group_bcast(vr, j, W);                            // lane j's value is the pivot (its imaginary part ignored)
-        d[j] = dj;
-        ok = ok && bazpower::power_pivot_ok(dj, floor);
-        if (r == (uint32_t)j) dmine = dj;
-        lr[j] = vr / dj;
-        li[j] = vi / dj;
-    }
-    // L^H: row r of L into the tile, read back by columns below
-    if (r < (uint32_t)M) {
-#pragma unroll
-        for (int k = 0; k < M; ++k) lt[r * S + k] = make_double2(lr[k], li[k]);
-    }
-    __syncthreads();
-    // the item's entries
-    float ang_mine = 0.0f, lvl_mine = 0.0f;                                 // lane e keeps entry e
-    for (uint32_t e = 0; e < A.n; ++e) {
-        const size_t t = (size_t)(live ? item : 0) * A.n + e;
-        const float a_in = A.ang_in[t], l_in = A.lvl_in[t];
-        // the entry's bin (refine_kernel's recovery: within 1/16 of b up to 2^20 bins)
-        uint32_t b = (uint32_t)__double2ll_rn((double)a_in * (double)A.res / 360.0);
-        b = b < A.res ? b : A.res - 1u;
-        const float2 av = r < (uint32_t)M ? A.raw[(size_t)b * M + r] : make_float2(0.0f, 0.0f);
-        double zr = (double)av.x, zi = (double)av.y;
-#pragma unroll
-        for (int k = 0; k < M - 1; ++k) {
-            const double kr = group_bcast(zr, k, W), ki = group_bcast(zi, k, W);            // z_k, final in lane k
-            if (r > (uint32_t)k) {
-                zr -= lr[k] * kr - li[k] * ki;
-                zi -= lr[k] * ki + li[k] * kr;
-            }
-        }
-        double s = r < (uint32_t)M ? (zr * zr + zi * zi) / dmine : 0.0;
-#pragma unroll
-        for (int o = W / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, W);
-        double ur = r < (uint32_t)M ? zr / dmine : 0.0, ui = r < (uint32_t)M ? zi / dmine : 0.0;
-#pragma unroll
-        for (int k = M - 1; k > 0; --k) {
-            const double kr = group_bcast(ur, k, W), ki = group_bcast(ui, k, W);            // u_k, final in lane k
-            const double2 c = lt[r < (uint32_t)k ? k * S + (int)r : 0];                     // L_kr
-            if (r < (uint32_t)k) {                                                          // conj(L_kr) u_k
-                ur -= c.x * kr + c.y * ki;
-                ui -= c.x * ki - c.y * kr;
-            }
-        }
-        double wr, wi;
-        beam_w_from_u(ur, ui, s, ok && l_in != 0.0f, &wr, &wi);
-        if (rowlane) A.w_out[t * M + r] = make_double2(wr, wi);
-        if (r == e) { ang_mine = a_in; lvl_mine = l_in; }
-    }
-    if (live && r < A.n) {
-        const size_t t = (size_t)item * A.n + r;
-        if (A.ang_out) A.ang_out[t] = ang_mine;
-        if (A.lvl_out) A.lvl_out[t] = lvl_mine;
-    }
-}
+inline constexpr auto beam_weights_kernel = &bazcapon::capon_kernel<M, BeamGeom<M>::THREADS, BeamGeom<M>::IPB, true, BeamWeightsArgs>;
 
 struct BeamApplyArgs {
     const float2* x;           // [batch][K][M] the chunk's input (device memory, or the caller's mapped input on the zero-copy path)

@@ -30,6 +30,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "capon_solve.hip.h"
+
 namespace bazrefine {
 
 // the rule: y[0] = d(b - 1), y[1] = d(b), y[2] = d(b + 1)
@@ -80,10 +82,7 @@ __global__ __launch_bounds__(256) void refine_kernel(const RefineArgs A)
         A.off_out[t] = 0.0;
         return;
     }
-    // the entry's bin: ang = (float)(b 360 / res) is within 2^-24 relative of b 360 / res, so up to 2^20 bins the product is within
-    // 1/16 of b
-    uint32_t b = (uint32_t)__double2ll_rn((double)a_in * (double)A.res / 360.0);
-    b = b < A.res ? b : A.res - 1u;
+    const uint32_t b = bazcapon::staged_bin(a_in, A.res);
     const uint32_t bm = b == 0u ? A.res - 1u : b - 1u, bp = b + 1u == A.res ? 0u : b + 1u;
     // the three steering rows (kept as the table's floats; widened exactly where used, .cc:110-112)
     float2 a[3][M];

@@ -425,7 +425,7 @@ BAZ_MUSIC_API int baz_music_debug_average(baz_music_ctx* ctx, const void* d_R_in
  *   MODE 2      lvl = (float)P.  ang and the spectrum do not change; entry order stays the pickers' order, by MUSIC strength; a missing
  *               entry stays (0, 0); a degenerate item's entries keep ang and report lvl = 0 (lvl[i] == spectrum[b] no longer holds).  With
  *               lvl == NULL mode 2 behaves as mode 1.
- *   WHAT RUNS   one kernel (gr_baz_amd/csrc/power_kernels.hip.h), the last launch of a sequence (after refinement where that is on): one
+ *   WHAT RUNS   one kernel (gr_baz_amd/csrc/power_kernels.hip.h, on the solve of capon_solve.hip.h), the last launch of a sequence (after refinement where that is on): one
  *               item per group of 4 / 8 / 16 lanes, R read and factorised once per item.  While the mode is on the pickers write into the
  *               staging buffer refinement uses (one buffer with both on) and the final kernels write the caller's ang / lvl, every word
  *               once (refinement and mode 2 together: refine_kernel writes ang, power_kernel lvl).  Its time counts under
@@ -471,7 +471,7 @@ BAZ_MUSIC_API int baz_music_power_estimate(uint32_t m, const double* R_ri, const
  *               loading > 0 an item with K < m snapshots is no longer degenerate (that is the point of loading); an all-zero item still
  *               is (its trace is 0).  R -> sR leaves w unchanged, exactly so for s a power of two.  tests/beam_ref.py restates this in
  *               numpy.  ang, lvl and the spectrum never change under this mode; the power mode keeps its own definition on the unloaded R.
- *   WHAT RUNS   two kernels (gr_baz_amd/csrc/beam_kernels.hip.h), the last launches of a sequence (behind refinement and the power mode
+ *   WHAT RUNS   two kernels (gr_baz_amd/csrc/beam_kernels.hip.h, the first on the solve of capon_solve.hip.h), the last launches of a sequence (behind refinement and the power mode
  *               where they are on): beam_weights_kernel, one item per group of 4 / 8 / 16 lanes, R read and factorised once per item; and
  *               beam_apply_kernel, which reads the batch's input a second time and writes n K complex64 per item.  While the mode is on
  *               the pickers write into the staging buffer refinement and the power mode use, and the final kernels write the caller's

@@ -196,3 +196,73 @@ def test_symbols_and_upper_layers_expose_the_mode():
     assert "power_mode" in inspect.signature(helper_mod.music_doa_helper.set_power_mode).parameters
     from gr_baz_amd import baz                              # (imports the pybind module)
     assert hasattr(baz.baz_music_doa_sptr, "set_power_mode") and hasattr(baz.baz_music_doa_sptr, "last_powers")
+
+
+# ---- one degeneracy rule behind the power and the beam entries ---------------------------------------------------------------------
+
+def _dead_sets(R, a):
+    """(entries baz_music_power_estimate declares dead, entries baz_music_beam_weights(loading = 0) declares dead)."""
+    with np.errstate(all="ignore"):
+        P = capi.power_estimate(R, a)
+        w = capi.beam_weights(R, a, 0.0)
+    return P == 0.0, ~(w != 0).any(axis=1)
+
+
+def _floor(diag):
+    """The pivot floor as the library forms it: the trace summed in index order, 2^-40 (trace / m)."""
+    trace = 0.0
+    for v in diag:
+        trace += float(v)
+    return 2.0 ** -40 * (trace / len(diag))
+
+
+def _diag_at_floor(m, step):
+    """diag(1 .. 1, x) with x `step` ulps from the floor the matrix itself gives (step = 0: on it)."""
+    diag = np.ones(m)
+    diag[-1] = 0.0
+    for _ in range(8):                                                   # (the floor moves by 2^-40 / m of what x moves)
+        x = _floor(diag)
+        for _ in range(abs(step)):
+            x = np.nextafter(x, np.inf if step > 0 else -np.inf)
+        if diag[-1] == x:
+            break
+        diag[-1] = x
+    f = _floor(diag)
+    want = f
+    for _ in range(abs(step)):
+        want = np.nextafter(want, np.inf if step > 0 else -np.inf)
+    assert diag[-1] == want
+    return np.diag(diag).astype(np.complex128)
+
+
+@pytest.mark.parametrize("m", list(range(1, 17)) + [64])
+def test_power_and_beam_entries_declare_the_same_entries_dead(m):
+    """For the same R and rows, P == 0 exactly where w (loading 0) is all zero: random positive-definite matrices (none dead, and
+    one all-zero row: that entry alone), the degenerate inputs of test_degenerate_inputs_give_zero, and diagonal matrices whose last
+    pivot sits one ulp above, on and one ulp below the floor 2^-40 trace / m."""
+    rng = np.random.default_rng(6100 + m)
+    for trial in range(3):
+        R = _hpd(rng, m)
+        a = _rows(rng, 5, m)
+        a[3] = 0
+        dead_p, dead_w = _dead_sets(R, a)
+        assert np.array_equal(dead_p, dead_w)
+        assert np.array_equal(dead_p, np.arange(5) == 3)
+    if m == 4:
+        a = _rows(rng, 3, m)
+        cases = {"zero R": np.zeros((m, m), np.complex128), "minus identity": -np.eye(m).astype(np.complex128)}
+        X = rng.standard_normal((m, 2)) + 1j * rng.standard_normal((m, 2))
+        cases["K = 2 snapshots"] = X @ X.conj().T / 2
+        for name, (i, j, v) in {"NaN entry": (2, 1, np.nan), "NaN on the diagonal": (0, 0, np.nan), "Inf on the diagonal": (3, 3, np.inf),
+                                "minus zero on the diagonal": (1, 1, -0.0)}.items():
+            cases[name] = _hpd(rng, m)
+            cases[name][i, j] = v
+        for name, R in cases.items():
+            dead_p, dead_w = _dead_sets(R, a)
+            assert dead_p.all() and dead_w.all(), name
+    if m >= 2:
+        a = _rows(rng, 3, m)
+        for step, alive in ((1, True), (0, False), (-1, False)):
+            dead_p, dead_w = _dead_sets(_diag_at_floor(m, step), a)
+            assert np.array_equal(dead_p, dead_w), "m=%d, last pivot %+d ulp from the floor" % (m, step)
+            assert (not dead_p.any()) if alive else dead_p.all(), "m=%d, last pivot %+d ulp from the floor" % (m, step)
