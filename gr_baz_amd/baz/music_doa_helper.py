@@ -169,6 +169,34 @@ def _set_beam_mode(h, mode, loading):
     h.impl.set_beam_mode(int(mode), float(loading))
 
 
+def _set_calibration(h, gamma):
+    # EXTENSION, no reference counterpart: per-antenna gain / phase calibration, the table in force becomes gamma_r * a_r(bin), see
+    # include/baz_music_hip.h.  Stays in force across set_frequency(): the library keeps gamma and applies it to every later table
+    # (h.array_response stays the uncalibrated one).
+    if gamma is None:
+        h.impl.set_calibration([])
+        return
+    g = [complex(x) for x in numpy.asarray(gamma).reshape(-1)]
+    if len(g) != h.m:
+        raise ValueError("gamma must hold m = %d complex values" % h.m)
+    h.impl.set_calibration(g)
+
+
+def _calibrate_next(h, items, pilot_bin, ref, min_quality):
+    # EXTENSION: estimate gamma from the next `items` items of the stream, which carry a pilot whose ideal response is row
+    # `pilot_bin` of the helper's own uncalibrated table, or `ref` ([1] * m: a noise source injected equally into all channels).
+    if (pilot_bin is None) == (ref is None):
+        raise ValueError("give either pilot_bin or ref")
+    if pilot_bin is not None:
+        if not 0 <= int(pilot_bin) < h.angular_resolution:
+            raise ValueError("pilot_bin must be a bin of the table, not %r" % (pilot_bin,))
+        ref = h.array_response[int(pilot_bin)]
+    p = [complex(x) for x in numpy.asarray(ref).reshape(-1)]
+    if len(p) != h.m:
+        raise ValueError("ref must hold m = %d complex values" % h.m)
+    h.impl.calibrate_next(int(items), p, float(min_quality))
+
+
 def _set_averaging(h, window, forgetting):
     # EXTENSION, no reference counterpart: the covariance of every item averaged over the last `window` items of the stream
     # (weights forgetting ** age), see include/baz_music_hip.h.  Stays in force across set_frequency(): covariances do not
@@ -238,6 +266,26 @@ if _HAVE_GR:
             forgetting ** age (window 1: off).  Raises ValueError unless 1 <= window <= 64 and 0 < forgetting <= 1."""
             _set_averaging(self, window, forgetting)
 
+        def set_calibration(self, gamma):
+            """Opt-in (not reference behaviour): per-antenna complex gains; the table in force becomes gamma_r * a_r(bin), also
+            after set_frequency() (None: off).  Not available with set_smoothing."""
+            _set_calibration(self, gamma)
+
+        def calibration(self):
+            """The complex64 gains in force, or None while off."""
+            g = self.impl.calibration()
+            return numpy.asarray(g, dtype=numpy.complex64) if len(g) else None
+
+        def calibrate_next(self, items, pilot_bin=None, ref=None, min_quality=0.9):
+            """Opt-in (not reference behaviour): estimate the gains from the next `items` items, which carry a pilot from the
+            direction of bin `pilot_bin` of this helper's table (or with the ideal response `ref`; [1] * m: a noise source injected
+            equally into all channels), and apply them when the estimate's quality (principal eigenvalue over trace) reaches
+            `min_quality`.  last_calibration_quality(): -1 while waiting for the items."""
+            _calibrate_next(self, items, pilot_bin, ref, min_quality)
+
+        def last_calibration_quality(self):
+            return float(self.impl.last_calibration_quality())
+
 else:
 
     class music_doa_helper(object):
@@ -293,6 +341,26 @@ else:
             """Opt-in (not reference behaviour): estimate every item from the covariances of the last `window` items, weighted
             forgetting ** age (window 1: off).  Raises ValueError unless 1 <= window <= 64 and 0 < forgetting <= 1."""
             _set_averaging(self, window, forgetting)
+
+        def set_calibration(self, gamma):
+            """Opt-in (not reference behaviour): per-antenna complex gains; the table in force becomes gamma_r * a_r(bin), also
+            after set_frequency() (None: off).  Not available with set_smoothing."""
+            _set_calibration(self, gamma)
+
+        def calibration(self):
+            """The complex64 gains in force, or None while off."""
+            g = self.impl.calibration()
+            return numpy.asarray(g, dtype=numpy.complex64) if len(g) else None
+
+        def calibrate_next(self, items, pilot_bin=None, ref=None, min_quality=0.9):
+            """Opt-in (not reference behaviour): estimate the gains from the next `items` items, which carry a pilot from the
+            direction of bin `pilot_bin` of this helper's table (or with the ideal response `ref`; [1] * m: a noise source injected
+            equally into all channels), and apply them when the estimate's quality (principal eigenvalue over trace) reaches
+            `min_quality`.  last_calibration_quality(): -1 while waiting for the items."""
+            _calibrate_next(self, items, pilot_bin, ref, min_quality)
+
+        def last_calibration_quality(self):
+            return float(self.impl.last_calibration_quality())
 
         def work(self, items):
             """Runs the wrapped block on (k, nsamples) complex64 items: returns (ang, lvl[, spectrum])."""

@@ -42,6 +42,8 @@ SYMBOLS = [
     "baz_music_set_power_mode", "baz_music_get_power_mode", "baz_music_last_powers", "baz_music_power_estimate",
     "baz_music_set_beam_mode", "baz_music_get_beam_mode", "baz_music_last_beams", "baz_music_last_beams_device",
     "baz_music_last_beam_weights", "baz_music_beam_weights",
+    "baz_music_set_calibration", "baz_music_get_calibration", "baz_music_calibration_apply",
+    "baz_music_calibrate", "baz_music_calibrate_device", "baz_music_calibration_estimate",
     "baz_music_set_averaging", "baz_music_get_averaging", "baz_music_reset_averaging", "baz_music_averaging_weights",
     "baz_music_debug_average",
 ]
@@ -232,6 +234,19 @@ def _bind(L):
                                               ctypes.POINTER(ctypes.c_double)]
     L.baz_music_debug_average.restype = ctypes.c_int
     L.baz_music_debug_average.argtypes = [_vp, _vp, _u32, _vp]
+    _f64p = ctypes.POINTER(ctypes.c_double)
+    L.baz_music_set_calibration.restype = ctypes.c_int
+    L.baz_music_set_calibration.argtypes = [_vp, _f32p]
+    L.baz_music_get_calibration.restype = ctypes.c_int
+    L.baz_music_get_calibration.argtypes = [_vp, _f32p, ctypes.POINTER(ctypes.c_int)]
+    L.baz_music_calibration_apply.restype = ctypes.c_int
+    L.baz_music_calibration_apply.argtypes = [_u32, _u32, _f32p, _f32p, _f32p]
+    L.baz_music_calibrate.restype = ctypes.c_int
+    L.baz_music_calibrate.argtypes = [_vp, _f32p, _u32, _f32p, _f64p, _f64p, _f64p]
+    L.baz_music_calibrate_device.restype = ctypes.c_int
+    L.baz_music_calibrate_device.argtypes = [_vp, _vp, _u32, _f32p, _f64p, _f64p, _f64p]
+    L.baz_music_calibration_estimate.restype = ctypes.c_int
+    L.baz_music_calibration_estimate.argtypes = [_u32, _f64p, _f32p, _f64p, _f64p]
     return L
 
 
@@ -538,6 +553,50 @@ class Context:
         self._chk(self._L.baz_music_last_beams_device(self._h, ctypes.byref(p), ctypes.byref(items)), "baz_music_last_beams_device")
         return int(p.value or 0), int(items.value)
 
+    def set_calibration(self, gamma):
+        """Opt-in extension (not reference behaviour): the table in force becomes gamma_r * a_r(bin) for the m complex gains `gamma`
+        (every one finite and nonzero), across later set_table calls too (include/baz_music_hip.h); None (default): off."""
+        if gamma is None:
+            self._chk(self._L.baz_music_set_calibration(self._h, None), "baz_music_set_calibration")
+            return
+        g = np.ascontiguousarray(np.asarray(gamma, dtype=np.complex64).reshape(-1))
+        if g.shape != (self.m,):
+            raise ValueError("gamma must hold m = %d complex values" % self.m)
+        self._chk(self._L.baz_music_set_calibration(self._h, g.view(np.float32).ctypes.data_as(_f32p)), "baz_music_set_calibration")
+
+    def get_calibration(self):
+        """The m complex64 gains in force, or None while the mode is off."""
+        g, on = np.zeros(self.m, np.complex64), ctypes.c_int(0)
+        self._chk(self._L.baz_music_get_calibration(self._h, g.view(np.float32).ctypes.data_as(_f32p), ctypes.byref(on)),
+                  "baz_music_get_calibration")
+        return g if on.value else None
+
+    def _calibrate(self, call, where, inp, batch, ref, want_rbar):
+        p = np.ascontiguousarray(np.asarray(ref, dtype=np.complex64).reshape(-1))
+        if p.shape != (self.m,):
+            raise ValueError("ref must hold m = %d complex values" % self.m)
+        g, q = np.zeros(self.m, np.complex128), ctypes.c_double(0.0)
+        rbar = np.zeros((self.m, self.m), np.complex128) if want_rbar else None
+        f64p = ctypes.POINTER(ctypes.c_double)
+        self._chk(call(self._h, inp, int(batch), p.view(np.float32).ctypes.data_as(_f32p), g.view(np.float64).ctypes.data_as(f64p),
+                       ctypes.byref(q), rbar.view(np.float64).ctypes.data_as(f64p) if want_rbar else None), where)
+        return (g, float(q.value), rbar) if want_rbar else (g, float(q.value))
+
+    def calibrate(self, items, ref, want_rbar=False):
+        """Estimates the gains from pilot items ((batch, nsamples) complex64 host array) and the pilot's ideal response `ref` (m complex):
+        (gamma complex128[m], quality[, Rbar complex128[m, m]]).  Does not apply them: set_calibration(gamma.astype(complex64))."""
+        x = np.ascontiguousarray(np.asarray(items, dtype=np.complex64))
+        if x.ndim == 1:
+            x = x[None, :]
+        if x.shape[1] != self.nsamples:
+            raise ValueError("items must be (batch, %d) complex64" % self.nsamples)
+        return self._calibrate(self._L.baz_music_calibrate, "baz_music_calibrate", x.view(np.float32).ctypes.data_as(_f32p), x.shape[0],
+                               ref, want_rbar)
+
+    def calibrate_device(self, d_in, batch, ref, want_rbar=False):
+        """calibrate() on `batch` items in device memory (d_in: a plain integer pointer); blocks, the results are host arrays."""
+        return self._calibrate(self._L.baz_music_calibrate_device, "baz_music_calibrate_device", _vp(d_in), batch, ref, want_rbar)
+
     def set_stream(self, hip_stream):
         self._chk(self._L.baz_music_set_stream(self._h, _vp(hip_stream) if hip_stream else None),
                   "baz_music_set_stream")
@@ -662,6 +721,41 @@ def beam_weights(R, a, loading=0.0):
     if r != OK:
         raise ValueError("baz_music_beam_weights: %s" % lib().baz_music_strerror(r).decode())
     return out[:a.shape[0]].copy()
+
+
+def calibration_apply(table, gamma):
+    """HOST-ONLY: the calibrated table gamma_r * a_r(bin) the library's definition gives (resolution x m complex64; needs no device)."""
+    t = np.ascontiguousarray(np.asarray(table, dtype=np.complex64))
+    if t.ndim != 2:
+        raise ValueError("calibration_apply: table must be resolution x m")
+    g = np.ascontiguousarray(np.asarray(gamma, dtype=np.complex64).reshape(-1))
+    if t.size and g.shape != (t.shape[1],):
+        raise ValueError("calibration_apply: gamma must hold m = %d complex values" % t.shape[1])
+    out = np.zeros(t.shape if t.size else (1, 1), np.complex64)
+    r = lib().baz_music_calibration_apply(t.shape[1], t.shape[0], t.view(np.float32).ctypes.data_as(_f32p),
+                                          g.view(np.float32).ctypes.data_as(_f32p), out.view(np.float32).ctypes.data_as(_f32p))
+    if r != OK:
+        raise ValueError("baz_music_calibration_apply: %s" % lib().baz_music_strerror(r).decode())
+    return out
+
+
+def calibration_estimate(rbar, ref):
+    """HOST-ONLY: (gamma complex128[m], quality) the library's definition gives for a mean covariance Rbar (m x m complex) and the
+    pilot's ideal response `ref` (m complex64); needs no device."""
+    R = np.ascontiguousarray(rbar, dtype=np.complex128)
+    if R.ndim != 2 or R.shape[0] != R.shape[1]:
+        raise ValueError("calibration_estimate: Rbar must be a square matrix")
+    m = R.shape[0]
+    p = np.ascontiguousarray(np.asarray(ref, dtype=np.complex64).reshape(-1))
+    if p.shape != (m,):
+        raise ValueError("calibration_estimate: ref must hold m = %d complex values" % m)
+    g, q = np.zeros(max(m, 1), np.complex128), ctypes.c_double(0.0)
+    f64p = ctypes.POINTER(ctypes.c_double)
+    r = lib().baz_music_calibration_estimate(m, R.view(np.float64).ctypes.data_as(f64p), p.view(np.float32).ctypes.data_as(_f32p),
+                                             g.view(np.float64).ctypes.data_as(f64p), ctypes.byref(q))
+    if r != OK:
+        raise ValueError("baz_music_calibration_estimate: %s" % lib().baz_music_strerror(r).decode())
+    return g[:m].copy(), float(q.value)
 
 
 def refine_estimate(y3):

@@ -18,12 +18,14 @@
 #include "refine_kernels.hip.h"
 #include "power_kernels.hip.h"
 #include "beam_kernels.hip.h"
+#include "calib_kernels.hip.h"
 #include "average_kernels.hip.h"
 
 #include <algorithm>
 #include <array>
 #include <chrono>
 #include <cmath>
+#include <complex>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -350,6 +352,16 @@ struct baz_music_ctx {
     size_t avg_hist_cap[2] = {0, 0};             // double2 elements
     double2* dRavg = nullptr;       // averaged covariances of the launch in flight (what the EVD reads while the mode is on)
     size_t ravg_cap = 0;            // double2 elements
+    // Opt-in per-antenna gain / phase calibration (baz_music_set_calibration; NOT reference behaviour; calib_kernels.hip.h).
+    // While calib_on is false build_tables_device launches what it launched before the mode existed; hRaw always holds the caller's
+    // table.  calib_on / calib_gamma change under `tab_mtx` (they are read by the table builders only).  The estimator's buffers are
+    // allocated by its first call.
+    bool calib_on = false;
+    bazcalib::CalibGamma calib_gamma = {};   // gamma_r, r < m
+    float* dCalIn = nullptr;        // baz_music_calibrate: the chunk's input on the device
+    size_t cal_in_cap = 0;          // floats
+    double* dCalPart = nullptr;     // the runs' partial sums, [groups][2 m^2], then R-bar, [2 m^2]
+    size_t cal_part_cap = 0;        // doubles
     size_t chunk_bytes = 0;   // host-fed path: traffic per pipelined chunk (BAZ_MUSIC_CHUNK_MIB); 0 = by buffer kind
     // host-fed path: page ranges of the caller's buffers this context has page-locked (baz_music_host_register)
     struct HostPin { uintptr_t lo, hi; uint32_t asked; };   // [lo, hi): the caller's exact bytes
@@ -1899,8 +1911,12 @@ int build_tables_device(baz_music_ctx* c, TableSet& T)
     void *zRaw = nullptr, *zStats = nullptr;
     HIP_TRY(c, hipHostGetDevicePointer(&zRaw, c->hRaw, 0));
     HIP_TRY(c, hipHostGetDevicePointer(&zStats, c->hTabStats, 0));
-    hipLaunchKernelGGL(baztab::copy_words_kernel, dim3((unsigned)std::min<size_t>(512, (raw_bytes / 8 + 255) / 256)), dim3(256), 0, s,
-                       static_cast<const unsigned long long*>(zRaw), reinterpret_cast<unsigned long long*>(c->dRaw), raw_bytes / 8);
+    if (c->calib_on)   // opt-in calibration: the same read over the link, times gamma (calib_kernels.hip.h); every image below follows from dRaw
+        hipLaunchKernelGGL(bazcalib::table_calib_kernel, dim3((unsigned)std::min<size_t>(512, (raw_bytes / 8 + 255) / 256)), dim3(bazcalib::CALIB_THREADS), 0, s,
+                           static_cast<const float2*>(zRaw), reinterpret_cast<float2*>(c->dRaw), raw_bytes / 8, m, c->calib_gamma);
+    else
+        hipLaunchKernelGGL(baztab::copy_words_kernel, dim3((unsigned)std::min<size_t>(512, (raw_bytes / 8 + 255) / 256)), dim3(256), 0, s,
+                           static_cast<const unsigned long long*>(zRaw), reinterpret_cast<unsigned long long*>(c->dRaw), raw_bytes / 8);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemsetAsync(c->dTabStats, 0, sizeof(baztab::TableStats), s));
     hipLaunchKernelGGL(baztab::table_stats_kernel, grid_for(res), dim3(256), 0, s, c->dRaw, m, res, c->wide ? 0 : 1,
@@ -1998,11 +2014,12 @@ int build_tables_device(baz_music_ctx* c, TableSet& T)
 }
 
 // Replaces set_array_response's body (.cc:60-70).  The caller holds c->tab_mtx.  `first`: called from baz_music_create (no
-// batch can be in flight, the images go straight into the active set).
+// batch can be in flight, the images go straight into the active set).  table_ri == nullptr: the table c->hRaw already holds
+// (baz_music_set_calibration: the same table under another gamma).
 int retune(baz_music_ctx* c, const float* table_ri, bool first)
 {
     const auto t0 = std::chrono::steady_clock::now();
-    std::memcpy(c->hRaw, table_ri, (size_t)c->res * c->m * 2 * sizeof(float));
+    if (table_ri) std::memcpy(c->hRaw, table_ri, (size_t)c->res * c->m * 2 * sizeof(float));
     if (first) return build_tables_device(c, c->tab);
     // the shadow set was the active one until the previous swap: batches launched before that swap may still read it
     if (c->swap_recorded) HIP_TRY(c, hipStreamWaitEvent(c->s_tab, c->ev_swap, 0));
@@ -3000,6 +3017,8 @@ void baz_music_destroy(baz_music_ctx* c)
         if (c->dOrdTap) (void)dev_free(c->dOrdTap);
         if (c->dRefAl) (void)dev_free(c->dRefAl);
         if (c->dRavg) (void)dev_free(c->dRavg);
+        if (c->dCalIn) (void)dev_free(c->dCalIn);
+        if (c->dCalPart) (void)dev_free(c->dCalPart);
         if (c->dAvgHist[0]) (void)dev_free(c->dAvgHist[0]);
         if (c->dAvgHist[1]) (void)dev_free(c->dAvgHist[1]);
         if (c->dCand) (void)dev_free(c->dCand);
@@ -3969,6 +3988,7 @@ int baz_music_set_smoothing(baz_music_ctx* c, uint32_t subarray, int forward_bac
         std::lock_guard<std::mutex> lk(c->mtx);
         if (c->beam_mode) return BAZ_MUSIC_E_UNSUPPORTED;
     }
+    if (c->calib_on) return BAZ_MUSIC_E_UNSUPPORTED;   // (raw data under Gamma != c I is not shift invariant; calib_on changes under tab_mtx)
     bazsmooth::Perm perm = {};
     if (smoothing_check(c->m, c->res, c->hRaw, subarray, fb, perm.p) != BAZ_MUSIC_OK) return BAZ_MUSIC_E_INVALID;
     const uint32_t L = c->m - subarray + 1;
@@ -4276,6 +4296,235 @@ int baz_music_beam_weights(uint32_t m, const double* R_ri, const float* a_ri, ui
         for (uint32_t i = 0; i < m; ++i) bazcapon::beam_w_from_u(ur[i], ui[i], s, true, &w[2 * i], &w[2 * i + 1]);
     }
     return BAZ_MUSIC_OK;
+}
+
+namespace {
+bool calib_value_ok(const float re, const float im)   // finite and nonzero
+{
+    return (re - re == 0.0f) && (im - im == 0.0f) && (re != 0.0f || im != 0.0f);
+}
+bool calib_vector_ok(uint32_t m, const float* v_ri)
+{
+    for (uint32_t r = 0; r < m; ++r)
+        if (!calib_value_ok(v_ri[2 * r], v_ri[2 * r + 1])) return false;
+    return true;
+}
+}  // namespace
+
+int baz_music_set_calibration(baz_music_ctx* c, const float* gamma_ri)
+{
+    if (!c || (gamma_ri && !calib_vector_ok(c->m, gamma_ri))) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> tl(c->tab_mtx);   // a retune of the table c->hRaw holds; against set_table and set_smoothing
+    DeviceGuard guard(c->device);
+    if (gamma_ri && c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;   // (sm.inner changes under tab_mtx + mtx: reading it under one is safe)
+    if (!gamma_ri && !c->calib_on) return BAZ_MUSIC_OK;            // off and staying off: the images in force are the ones to keep
+    const bool old_on = c->calib_on;
+    const bazcalib::CalibGamma old_gamma = c->calib_gamma;
+    c->calib_on = gamma_ri != nullptr;
+    for (uint32_t r = 0; r < c->m; ++r)
+        c->calib_gamma.g[r] = gamma_ri ? make_float2(gamma_ri[2 * r], gamma_ri[2 * r + 1]) : make_float2(1.0f, 0.0f);
+    const int r = retune(c, nullptr, false);      // (smoothing is off here: it and a calibration exclude each other)
+    if (r != BAZ_MUSIC_OK) {                    // the old images stay in force (retune exchanges only after a complete build)
+        c->calib_on = old_on;
+        c->calib_gamma = old_gamma;
+    }
+    return r;
+}
+
+int baz_music_get_calibration(const baz_music_ctx* c, float* gamma_ri, int* on)
+{
+    if (!c || !on) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> tl(const_cast<baz_music_ctx*>(c)->tab_mtx);
+    *on = c->calib_on ? 1 : 0;
+    if (gamma_ri)
+        for (uint32_t r = 0; r < c->m; ++r) {
+            gamma_ri[2 * r] = c->calib_on ? c->calib_gamma.g[r].x : 1.0f;
+            gamma_ri[2 * r + 1] = c->calib_on ? c->calib_gamma.g[r].y : 0.0f;
+        }
+    return BAZ_MUSIC_OK;
+}
+
+// The definition of include/baz_music_hip.h on the host: table_calib_kernel's own routine, entry by entry.
+int baz_music_calibration_apply(uint32_t m, uint32_t resolution, const float* table_ri, const float* gamma_ri, float* out_ri)
+{
+    if (m < 1 || m > BAZ_MUSIC_MAX_M || resolution == 0 || !table_ri || !gamma_ri || !out_ri) return BAZ_MUSIC_E_INVALID;
+    if (!calib_vector_ok(m, gamma_ri)) return BAZ_MUSIC_E_INVALID;
+    for (size_t b = 0; b < resolution; ++b)
+        for (uint32_t r = 0; r < m; ++r) {
+            const size_t i = 2 * (b * m + r);
+            bazcalib::calib_mul(gamma_ri[2 * r], gamma_ri[2 * r + 1], table_ri[i], table_ri[i + 1], &out_ri[i], &out_ri[i + 1]);
+        }
+    return BAZ_MUSIC_OK;
+}
+
+// gamma-hat and quality from R-bar (include/baz_music_hip.h): a cyclic Hermitian Jacobi in fp64 on the host.  A rotation of the pair
+// (p, q) with a_pq = g e^{i phi} is J = diag(1, e^{-i phi}) [[c, s], [-s, c]] with the real Jacobi angle of [[a_pp, g], [g, a_qq]];
+// A <- J^H A J, V <- V J.  Pairs at or below 2^-75 of the Frobenius norm are left alone (m^2 of them stay far below the m 2^-52 |A|
+// backward error of the rotations themselves); the sweeps end when one rotates nothing.
+int baz_music_calibration_estimate(uint32_t m, const double* Rbar_ri, const float* ref_ri, double* gamma_ri, double* quality)
+{
+    if (m < 1 || m > BAZ_MUSIC_MAX_M || !Rbar_ri || !ref_ri || !gamma_ri || !quality) return BAZ_MUSIC_E_INVALID;
+    if (!calib_vector_ok(m, ref_ri)) return BAZ_MUSIC_E_INVALID;
+    typedef std::complex<double> cd;
+    auto degenerate = [&]() {
+        for (uint32_t r = 0; r < m; ++r) { gamma_ri[2 * r] = 1.0; gamma_ri[2 * r + 1] = 0.0; }
+        *quality = 0.0;
+        return BAZ_MUSIC_OK;
+    };
+    double trace = 0.0, frob2 = 0.0;
+    for (size_t i = 0; i < (size_t)2 * m * m; ++i) {
+        if (!(Rbar_ri[i] - Rbar_ri[i] == 0.0)) return degenerate();
+    }
+    for (uint32_t i = 0; i < m; ++i) trace = trace + Rbar_ri[2 * ((size_t)i * m + i)];
+    if (!(trace > 0.0) || !(trace - trace == 0.0)) return degenerate();
+    // (scaled by a power of two so that squares neither overflow nor vanish: exact, and the eigenvectors do not change)
+    int ex = 0;
+    (void)frexp(trace, &ex);
+    std::vector<cd> A((size_t)m * m), V((size_t)m * m, cd(0.0, 0.0));
+    for (uint32_t p = 0; p < m; ++p) {
+        V[(size_t)p * m + p] = cd(1.0, 0.0);
+        A[(size_t)p * m + p] = cd(ldexp(Rbar_ri[2 * ((size_t)p * m + p)], -ex), 0.0);
+        for (uint32_t q = p + 1; q < m; ++q) {
+            const cd a(ldexp(Rbar_ri[2 * ((size_t)p * m + q)], -ex), ldexp(Rbar_ri[2 * ((size_t)p * m + q) + 1], -ex));
+            A[(size_t)p * m + q] = a;
+            A[(size_t)q * m + p] = std::conj(a);
+        }
+    }
+    for (const cd& a : A) frob2 += std::norm(a);
+    const double small = ldexp(std::sqrt(frob2), -75);
+    for (int sweep = 0; sweep < 64; ++sweep) {
+        bool rotated = false;
+        for (uint32_t p = 0; p + 1 < m; ++p)
+            for (uint32_t q = p + 1; q < m; ++q) {
+                const cd apq = A[(size_t)p * m + q];
+                const double g = std::abs(apq);
+                if (!(g > small)) continue;
+                rotated = true;
+                const cd ph = apq / g;                            // e^{i phi}
+                const double app = A[(size_t)p * m + p].real(), aqq = A[(size_t)q * m + q].real();
+                const double tau = (aqq - app) / (2.0 * g);
+                const double t = (tau >= 0.0 ? 1.0 : -1.0) / (std::fabs(tau) + std::sqrt(1.0 + tau * tau));
+                const double cs = 1.0 / std::sqrt(1.0 + t * t), sn = t * cs;
+                const cd jqp = -sn * std::conj(ph), jqq = cs * std::conj(ph);   // J = [[cs, sn], [jqp, jqq]]
+                for (uint32_t k = 0; k < m; ++k) {                 // A <- A J, V <- V J (columns p, q)
+                    const cd akp = A[(size_t)k * m + p], akq = A[(size_t)k * m + q];
+                    A[(size_t)k * m + p] = akp * cs + akq * jqp;
+                    A[(size_t)k * m + q] = akp * sn + akq * jqq;
+                    const cd vkp = V[(size_t)k * m + p], vkq = V[(size_t)k * m + q];
+                    V[(size_t)k * m + p] = vkp * cs + vkq * jqp;
+                    V[(size_t)k * m + q] = vkp * sn + vkq * jqq;
+                }
+                for (uint32_t k = 0; k < m; ++k) {                 // A <- J^H A (rows p, q)
+                    const cd apk = A[(size_t)p * m + k], aqk = A[(size_t)q * m + k];
+                    A[(size_t)p * m + k] = cs * apk + std::conj(jqp) * aqk;
+                    A[(size_t)q * m + k] = sn * apk + std::conj(jqq) * aqk;
+                }
+                A[(size_t)p * m + q] = cd(0.0, 0.0);
+                A[(size_t)q * m + p] = cd(0.0, 0.0);
+                A[(size_t)p * m + p] = cd(A[(size_t)p * m + p].real(), 0.0);
+                A[(size_t)q * m + q] = cd(A[(size_t)q * m + q].real(), 0.0);
+            }
+        if (!rotated) break;
+    }
+    uint32_t top = 0;
+    for (uint32_t p = 1; p < m; ++p)
+        if (A[(size_t)p * m + p].real() > A[(size_t)top * m + top].real()) top = p;
+    const double l1 = ldexp(A[(size_t)top * m + top].real(), ex);
+    double vn = 0.0;
+    for (uint32_t r = 0; r < m; ++r) vn = vn + std::norm(V[(size_t)r * m + top]);
+    vn = std::sqrt(vn);
+    const cd v0 = V[(size_t)0 * m + top];
+    if (v0 == cd(0.0, 0.0) || !(vn > 0.0)) return degenerate();
+    std::vector<cd> gh(m);
+    for (uint32_t r = 0; r < m; ++r) gh[r] = (V[(size_t)r * m + top] / vn) / cd((double)ref_ri[2 * r], (double)ref_ri[2 * r + 1]);
+    const double a0 = std::abs(gh[0]);
+    if (!(a0 > 0.0) || !(a0 - a0 == 0.0)) return degenerate();
+    const cd rot = std::conj(gh[0]) / a0;
+    double s2 = 0.0;
+    for (uint32_t r = 0; r < m; ++r) {
+        gh[r] = r == 0 ? cd(a0, 0.0) : gh[r] * rot;
+        s2 = s2 + std::norm(gh[r]);
+    }
+    const double scale = 1.0 / std::sqrt(s2 / (double)m);
+    for (uint32_t r = 0; r < m; ++r) {
+        gamma_ri[2 * r] = gh[r].real() * scale;
+        gamma_ri[2 * r + 1] = r == 0 ? 0.0 : gh[r].imag() * scale;
+    }
+    *quality = l1 / trace;
+    return BAZ_MUSIC_OK;
+}
+
+namespace {
+// R-bar of `batch` items (device memory, or host memory staged chunk by chunk through dCalIn) into Rbar (host, 2 m^2 doubles): the
+// covariance stage debug_cov runs, chunk by chunk through the context's R workspace, cov_mean_kernel over each chunk's runs, one fold.
+// The caller holds c->mtx.
+int calib_mean_locked(baz_music_ctx* c, const void* in, bool in_on_host, uint32_t batch, double* Rbar)
+{
+    const uint32_t ncomp = 2u * c->m * c->m;
+    const bazcalib::MeanGeometry G = bazcalib::mean_geometry(batch, c->m);
+    const uint32_t chunk = std::min(G.chunk, batch);
+    int r = c->wide ? ensure_wide_workspace(c, chunk) : ensure_workspace(c, chunk);
+    if (r == BAZ_MUSIC_OK) r = grow(c, c->dCalPart, c->cal_part_cap, (size_t)(G.groups + 1) * ncomp);
+    if (r == BAZ_MUSIC_OK && in_on_host) r = grow(c, c->dCalIn, c->cal_in_cap, (size_t)chunk * c->nsamples * 2);
+    if (r) return r;
+    BAZ_REQUIRE(c, dR); BAZ_REQUIRE(c, dCalPart);
+    const dim3 gx((ncomp + bazcalib::MEAN_THREADS - 1) / bazcalib::MEAN_THREADS);
+    for (uint32_t off = 0; off < batch; off += G.chunk) {
+        const uint32_t nb = std::min(G.chunk, batch - off);
+        const float* d_in = static_cast<const float*>(in) + (size_t)off * c->nsamples * 2;
+        if (in_on_host) {
+            HIP_TRY(c, hipMemcpyAsync(c->dCalIn, d_in, (size_t)nb * c->nsamples * 8, hipMemcpyHostToDevice, c->stream));
+            d_in = c->dCalIn;
+        }
+        r = c->wide ? launch_cov_wide(c, d_in, nb, c->dR) : launch_cov(c, d_in, nb, c->dR);
+        if (r) return r;
+        ProfScope ps(c, BAZ_MUSIC_STAGE_MERGE);             // (the covariance counts under COV, the two levels of the mean under MERGE)
+        const uint32_t runs = (nb + G.run - 1) / G.run;
+        hipLaunchKernelGGL(bazcalib::cov_mean_kernel, dim3(gx.x, runs), dim3(bazcalib::MEAN_THREADS), 0, c->stream,
+                           reinterpret_cast<const double*>(c->dR), c->dCalPart + (size_t)(off / G.run) * ncomp, nb, G.run, ncomp, 1.0);
+        HIP_TRY(c, hipGetLastError());
+    }
+    double* const dMean = c->dCalPart + (size_t)G.groups * ncomp;
+    {
+        ProfScope ps(c, BAZ_MUSIC_STAGE_MERGE);
+        hipLaunchKernelGGL(bazcalib::cov_mean_kernel, dim3(gx.x, 1), dim3(bazcalib::MEAN_THREADS), 0, c->stream, c->dCalPart, dMean, G.groups,
+                           G.groups, ncomp, 1.0 / (double)batch);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(Rbar, dMean, (size_t)ncomp * sizeof(double), hipMemcpyDeviceToHost));
+    return BAZ_MUSIC_OK;
+}
+
+int calibrate_any(baz_music_ctx* c, const void* in, bool in_on_host, uint32_t batch, const float* ref_ri, double* gamma_ri, double* quality,
+                  double* Rbar_ri)
+{
+    if (!c || !in || batch == 0 || !ref_ri || !gamma_ri || !quality) return BAZ_MUSIC_E_INVALID;
+    if (!calib_vector_ok(c->m, ref_ri)) return BAZ_MUSIC_E_INVALID;
+    std::vector<double> mean((size_t)2 * c->m * c->m);
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);
+        DeviceGuard guard(c->device);
+        if (c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;
+        (void)hipGetLastError();
+        const int r = calib_mean_locked(c, in, in_on_host, batch, mean.data());
+        if (r) return r;
+    }
+    if (Rbar_ri) std::memcpy(Rbar_ri, mean.data(), mean.size() * sizeof(double));
+    return baz_music_calibration_estimate(c->m, mean.data(), ref_ri, gamma_ri, quality);
+}
+}  // namespace
+
+int baz_music_calibrate(baz_music_ctx* c, const float* in_ri, uint32_t batch, const float* ref_ri, double* gamma_ri, double* quality,
+                        double* Rbar_ri)
+{
+    return calibrate_any(c, in_ri, true, batch, ref_ri, gamma_ri, quality, Rbar_ri);
+}
+
+int baz_music_calibrate_device(baz_music_ctx* c, const void* d_in, uint32_t batch, const float* ref_ri, double* gamma_ri, double* quality,
+                               double* Rbar_ri)
+{
+    return calibrate_any(c, d_in, false, batch, ref_ri, gamma_ri, quality, Rbar_ri);
 }
 
 int baz_music_get_smoothing(const baz_music_ctx* c, uint32_t* subarray, int* forward_backward)

@@ -12,6 +12,7 @@
 
 #include <gnuradio/io_signature.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -87,7 +88,8 @@ baz_music_doa::baz_music_doa(unsigned int m, unsigned int n, unsigned int nsampl
                      gr::io_signature::make3(1, 3, n * sizeof(float), n * sizeof(float),
                                              resolution * sizeof(float))),
       d_m(m), d_n(n), d_nsamples(nsamples), d_resolution(resolution),
-      d_array_response(array_response), d_ctx(NULL), d_pin_buffers(false)
+      d_array_response(array_response), d_ctx(NULL), d_pin_buffers(false),
+      d_cal_want(0), d_cal_min_quality(0.0), d_cal_quality(-1.0)
 {
     const std::vector<float> flat = flatten_response(array_response, m, resolution);
     const int rc = baz_music_create(&d_ctx, m, n, nsamples, resolution, flat.data(), next_device());
@@ -239,6 +241,48 @@ void baz_music_doa::reset_averaging()
     if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: reset_averaging: ") + baz_music_strerror(rc));
 }
 
+void baz_music_doa::set_calibration(const std::vector<gr_complex>& gamma)
+{
+    if (!gamma.empty() && gamma.size() != d_m) throw std::invalid_argument("music_doa: set_calibration: gamma must hold m values (or none: off)");
+    const int rc = baz_music_set_calibration(d_ctx, gamma.empty() ? NULL : reinterpret_cast<const float*>(gamma.data()));
+    if (rc == BAZ_MUSIC_E_INVALID) throw std::invalid_argument("music_doa: set_calibration: every gain must be finite and nonzero");
+    if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: set_calibration: ") + baz_music_strerror(rc));
+}
+
+std::vector<gr_complex> baz_music_doa::calibration()
+{
+    std::vector<gr_complex> gamma(d_m);
+    int on = 0;
+    const int rc = baz_music_get_calibration(d_ctx, reinterpret_cast<float*>(gamma.data()), &on);
+    if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: calibration: ") + baz_music_strerror(rc));
+    if (!on) gamma.clear();
+    return gamma;
+}
+
+void baz_music_doa::calibrate_next(unsigned int items, const std::vector<gr_complex>& ref, double min_quality)
+{
+    if (items == 0 || ref.size() != d_m || !(min_quality >= 0.0 && min_quality <= 1.0))
+        throw std::invalid_argument("music_doa: calibrate_next: items > 0, m reference values and 0 <= min_quality <= 1 are required");
+    for (unsigned int r = 0; r < d_m; ++r) {
+        const float re = ref[r].real(), im = ref[r].imag();
+        if (!(re - re == 0.0f) || !(im - im == 0.0f) || (re == 0.0f && im == 0.0f))
+            throw std::invalid_argument("music_doa: calibrate_next: every reference value must be finite and nonzero");
+    }
+    gr::thread::scoped_lock guard(d_cal_mutex);
+    d_cal_items.clear();
+    d_cal_items.reserve((size_t)items * d_nsamples);
+    d_cal_ref = ref;
+    d_cal_min_quality = min_quality;
+    d_cal_quality = -1.0;
+    d_cal_want = items;
+}
+
+double baz_music_doa::last_calibration_quality()
+{
+    gr::thread::scoped_lock guard(d_cal_mutex);
+    return d_cal_quality;
+}
+
 std::vector<unsigned char> baz_music_doa::last_orders(unsigned int count)
 {
     std::vector<unsigned char> out(count);
@@ -283,6 +327,33 @@ int baz_music_doa::work(int noutput_items, gr_vector_const_void_star& input_item
         fprintf(stderr, "[%s<%li>] MUSIC DOA: device error: %s (%s)\n", name().c_str(), unique_id(),
                 baz_music_strerror(rc), baz_music_last_hip_error(d_ctx));
         return -1;   /* WORK_DONE */
+    }
+
+    /* calibrate_next: this call's items join the capture; once it is complete, one estimate, applied (to the calls after this one)
+     * when its quality allows.  A failing estimate disarms and reports quality 0; the stream goes on. */
+    gr::thread::scoped_lock guard(d_cal_mutex);
+    if (d_cal_want) {
+        const size_t have = d_cal_items.size() / d_nsamples;
+        const size_t take = std::min<size_t>((size_t)noutput_items, d_cal_want - have);
+        const gr_complex* items = reinterpret_cast<const gr_complex*>(in);
+        d_cal_items.insert(d_cal_items.end(), items, items + take * d_nsamples);
+        if (have + take == d_cal_want) {
+            std::vector<double> gamma(2 * (size_t)d_m);
+            double quality = 0.0;
+            int rc2 = baz_music_calibrate(d_ctx, reinterpret_cast<const float*>(d_cal_items.data()), d_cal_want,
+                                          reinterpret_cast<const float*>(d_cal_ref.data()), gamma.data(), &quality, NULL);
+            if (rc2 == BAZ_MUSIC_OK && quality > 0.0 && quality >= d_cal_min_quality) {
+                std::vector<float> g32(gamma.begin(), gamma.end());      /* complex128 -> complex64, round to nearest */
+                rc2 = baz_music_set_calibration(d_ctx, g32.data());
+            }
+            if (rc2 != BAZ_MUSIC_OK) {
+                fprintf(stderr, "[%s<%li>] MUSIC DOA: calibrate_next: %s\n", name().c_str(), unique_id(), baz_music_strerror(rc2));
+                quality = 0.0;
+            }
+            d_cal_quality = quality;
+            d_cal_want = 0;
+            std::vector<gr_complex>().swap(d_cal_items);
+        }
     }
     return noutput_items;
 }

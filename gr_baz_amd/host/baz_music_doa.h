@@ -91,6 +91,18 @@ public:
      * 1 <= window <= 64 and 0 < forgetting <= 1. */
     void set_averaging(unsigned int window, double forgetting);
     void reset_averaging();
+    /* Extension, off by default (not in the reference): per-antenna gain / phase calibration -- the table in force becomes
+     * gamma_r a_r(bin), across set_array_response too (baz_music_set_calibration, include/baz_music_hip.h).  An empty vector is off.
+     * calibration(): the gains in force (empty while off).  calibrate_next arms an estimate from a pilot: the block copies the next
+     * `items` items that pass through work() (across as many calls as it takes; their outputs are untouched), calls
+     * baz_music_calibrate once with the pilot's ideal response `ref` and applies the result, rounded to complex64, only when its
+     * quality is >= min_quality.  last_calibration_quality(): -1 while armed (and before the first estimate), else the quality of
+     * the last estimate.  Not available while smoothing is on.  Throws std::invalid_argument for a vector that does not hold m
+     * finite nonzero values, items == 0 or a min_quality outside [0, 1]. */
+    void set_calibration(const std::vector<gr_complex>& gamma);
+    std::vector<gr_complex> calibration();
+    void calibrate_next(unsigned int items, const std::vector<gr_complex>& ref, double min_quality);
+    double last_calibration_quality();
 
     /* Page-locking of the scheduler's stream buffers (baz_music_set_host_pinning, include/baz_music_hip.h): work()
      * registers the ranges it is handed the first time it sees them, stop() and the destructor release them.  On by
@@ -119,6 +131,13 @@ private:
     gr::thread::mutex d_mutex;
     baz_music_ctx* d_ctx;                /* device-side state (table, workspace, stream) */
     bool d_pin_buffers;
+    /* calibrate_next: guarded by d_cal_mutex (its own: work() must never wait for a retune that holds d_mutex) */
+    gr::thread::mutex d_cal_mutex;
+    unsigned int d_cal_want;            /* items to capture; 0: not armed */
+    std::vector<gr_complex> d_cal_items; /* the items captured so far */
+    std::vector<gr_complex> d_cal_ref;
+    double d_cal_min_quality;
+    double d_cal_quality;
 };
 
 /* Placement rule of independent block instances (BASELINE config 4: 64 streams in one flowgraph; SURVEY.md 8e,

@@ -259,6 +259,13 @@ PYBIND11_MODULE(_baz_music, mod)
         .def("set_averaging", [](music_doa_handle& h, unsigned int window, double forgetting) { h.blk->set_averaging(window, forgetting); },
              py::arg("window"), py::arg("forgetting") = 1.0)
         .def("reset_averaging", [](music_doa_handle& h) { h.blk->reset_averaging(); })
+        .def("set_calibration", [](music_doa_handle& h, const std::vector<gr_complex>& gamma) { h.blk->set_calibration(gamma); },
+             py::arg("gamma"))
+        .def("calibration", [](music_doa_handle& h) { return h.blk->calibration(); })
+        .def("calibrate_next", [](music_doa_handle& h, unsigned int items, const std::vector<gr_complex>& ref, double min_quality) {
+                 h.blk->calibrate_next(items, ref, min_quality);
+             }, py::arg("items"), py::arg("ref"), py::arg("min_quality") = 0.9)
+        .def("last_calibration_quality", [](music_doa_handle& h) { return h.blk->last_calibration_quality(); })
         .def("last_orders",
              [](music_doa_handle& h, unsigned int count) {
                  const std::vector<unsigned char> v = h.blk->last_orders(count);

@@ -504,6 +504,70 @@ BAZ_MUSIC_API int baz_music_last_beams(baz_music_ctx* ctx, float* out_ri, uint32
 BAZ_MUSIC_API int baz_music_last_beams_device(baz_music_ctx* ctx, const void** d_beams, uint32_t* items);
 BAZ_MUSIC_API int baz_music_last_beam_weights(baz_music_ctx* ctx, double* out_ri, uint32_t items);
 BAZ_MUSIC_API int baz_music_beam_weights(uint32_t m, const double* R_ri, const float* a_ri, uint32_t count, double loading, double* w_ri);
+/* OPT-IN extension, NOT reference behaviour: per-antenna gain / phase calibration.  On a real receiver every channel has
+ * its own complex gain gamma_r: the snapshots are x = Gamma a(theta) s + noise with Gamma = diag(gamma).  The correction lives in the
+ * TABLE, not in the data: MUSIC on the raw covariance with the rows gamma (.) a(theta) is exact under that model, while dividing the data
+ * by gamma would colour the noise wherever the |gamma_r| differ.
+ * set_calibration: gamma_ri = m complex64 (re / im interleaved), every one finite and nonzero, else BAZ_MUSIC_E_INVALID and the setting in
+ * force stays; NULL = off (the default, the reference).
+ *   DEFINITION  the table in force is a'_r(bin) = gamma_r a_r(bin), a = the table last given to create / set_table.  Both operands are
+ *               widened exactly to fp64; each of the four products is exact (two 24-bit significands);
+ *               re = g.re a.re - g.im a.im and im = g.re a.im + g.im a.re take one fp64 rounding each (the same with or without FMA
+ *               contraction), then one round-to-nearest-even conversion to fp32.  Every numeric statement of this header then holds for
+ *               the table a': parity with the reference, the per-path error bounds, the steering rows refinement, power and beam read.
+ *               For the table a' the reference itself is the oracle.  gamma = all (1, 0) gives the bytes of a (1 a is exact; a component
+ *               -0 may come back as +0).  calibration_apply is the host form, the kernel's own routine: table_ri = resolution x m
+ *               complex64 -> out_ri likewise; needs no device; BAZ_MUSIC_E_INVALID for m == 0, m > BAZ_MUSIC_MAX_M, resolution == 0, a
+ *               NULL array or a gamma entry that is zero or not finite.  tests/calib_ref.py restates it in numpy.
+ *   WHAT RUNS   every device image of the table follows from the raw table on the device, which the first launch of a retune fills from
+ *               the page-locked copy of the caller's table.  While a calibration is on that launch is table_calib_kernel
+ *               (gr_baz_amd/csrc/calib_kernels.hip.h) instead of copy_words_kernel: the same zero-copy read over the link, times gamma
+ *               (handed to the kernel by value), unit-stride 8-byte stores.  Nothing else in the builders changes, so the correction
+ *               reaches every scan path and every mode at once, the 17 .. BAZ_MUSIC_MAX_M path included.  Off -- a context never set,
+ *               one set to NULL, one switched on and off again -- launches exactly what it launched before the mode existed and every
+ *               image and output is the reference's bit for bit.
+ *   PERSISTENCE gamma stays in force across baz_music_set_table: the page-locked copy keeps holding the caller's table, and
+ *               set_calibration is a retune of that table -- built into the shadow set, exchanged under the batch mutex, so a batch
+ *               sees the old table image or the new one, never a mixture; it updates baz_music_last_retune_ms like set_table.
+ *   SCOPE       every antenna count.  Composes with peak mode, the emitter-count mode, refinement, averaging, power and beam.  It does
+ *               NOT compose with baz_music_set_smoothing (the re-stacked inner context presumes a shift-invariant array, which raw data
+ *               under Gamma != c I does not give): set_calibration(non-NULL) while smoothing is on and set_smoothing(on) while a
+ *               calibration is on return BAZ_MUSIC_E_UNSUPPORTED, the setting already in force stays.  baz_music_debug_table_image
+ *               describes the calibrated table.
+ * get_calibration: *on = 0 / 1; gamma_ri (may be NULL) receives the m values in force, (1, 0) each while off.
+ *
+ * Estimating gamma from a pilot -- one emitter at a known direction (ref = its row of the uncalibrated table), or a noise source
+ * injected equally into all channels (ref = all (1, 0)).
+ *   MODEL       a single pilot, noise white AT THE CHANNEL OUTPUTS: the covariance is P (Gamma p)(Gamma p)^H + sigma^2 I, whose
+ *               principal eigenvector is exactly proportional to Gamma p whatever sigma^2 is.
+ *   DEFINITION  R_t = the plain covariance of item t, exactly what baz_music_debug_cov returns (never the averaged one);
+ *               Rbar = (1 / B) sum_t R_t in fp64, in the fixed two-level order of calib_kernels.hip.h (runs of consecutive items summed in
+ *               ascending order, the runs' sums folded in ascending order, one multiplication by 1.0 / B; the cut is a function of
+ *               (B, m) alone and nothing is accumulated atomically: the bits of Rbar depend on the input and (B, m) alone, and the
+ *               host-fed and the device form give the same bits).  v = the unit eigenvector of the largest eigenvalue l1 of Rbar, by a
+ *               cyclic Hermitian Jacobi in fp64 ON THE HOST (one m x m matrix is no work for the device; the batch's covariances and
+ *               their mean are) from the upper triangle and the real diagonal as stored.  g_r = v_r / p_r, p = ref widened exactly; g
+ *               times conj(g_0) / |g_0| with Im g_0 stored as exactly 0 (g_0 > 0); g scaled so that (1 / m) sum |g_r|^2 = 1.
+ *               quality = l1 / Re tr(Rbar) (the trace summed in index order), in [1 / m, 1]: 1 for a pure pilot, about 1 / m for noise;
+ *               the caller gates on it.  DEGENERATE -- Rbar holds a NaN or an Inf, its trace is not > 0, or v_0 == 0 --: BAZ_MUSIC_OK
+ *               with quality = 0 and g = all (1, 0).  tests/calib_ref.py restates this on numpy.linalg.eigh.
+ *   CALLS       calibrate: `batch` items from host memory, staged through a device buffer of the context chunk by chunk;
+ *               calibrate_device: from device memory.  Both block, write gamma_ri (m complex128), *quality and, where Rbar_ri is not
+ *               NULL, Rbar (m*m complex128, row-major), all host memory, and do NOT apply the result: round it to complex64 and hand it
+ *               to set_calibration.  They consume no averaging history, touch none of the last_* taps and do not change the table; the
+ *               covariance stage is the one debug_cov runs (at the fused shape the two-kernel form, as under averaging), in chunks of
+ *               the context's covariance workspace (profiled under BAZ_MUSIC_STAGE_COV; cov_mean_kernel's launches under
+ *               BAZ_MUSIC_STAGE_MERGE).  calibration_estimate is the routine they call on their Rbar; it needs no device.
+ *   ERRORS      BAZ_MUSIC_E_INVALID for a ref entry that is zero or not finite, batch == 0, m out of range or a NULL pointer where one
+ *               is required (Rbar_ri of calibrate* may be NULL); BAZ_MUSIC_E_UNSUPPORTED while smoothing is on. */
+BAZ_MUSIC_API int baz_music_set_calibration(baz_music_ctx* ctx, const float* gamma_ri);
+BAZ_MUSIC_API int baz_music_get_calibration(const baz_music_ctx* ctx, float* gamma_ri, int* on);
+BAZ_MUSIC_API int baz_music_calibration_apply(uint32_t m, uint32_t resolution, const float* table_ri, const float* gamma_ri, float* out_ri);
+BAZ_MUSIC_API int baz_music_calibrate(baz_music_ctx* ctx, const float* in_ri, uint32_t batch, const float* ref_ri, double* gamma_ri,
+                                      double* quality, double* Rbar_ri);
+BAZ_MUSIC_API int baz_music_calibrate_device(baz_music_ctx* ctx, const void* d_in, uint32_t batch, const float* ref_ri, double* gamma_ri,
+                                             double* quality, double* Rbar_ri);
+BAZ_MUSIC_API int baz_music_calibration_estimate(uint32_t m, const double* Rbar_ri, const float* ref_ri, double* gamma_ri, double* quality);
 /* Statistic: how many (item, bin) values of the LAST process call were recomputed in the reference's literal form
  * ||G^H a||^2 because the projector form a^H Q a put them at or below ~m 1e-8 max||a||^2 (near-nulls of the noise
  * subspace, SNR >~ 55 dB); blocks until that call is done (a host-fed call cut into chunks reports their sum).
