@@ -159,6 +159,26 @@ def _set_power_mode(h, mode):
     h.impl.set_power_mode(int(mode))
 
 
+ESTIMATORS = {"music": 0, "capon": 1, "bartlett": 2}
+
+
+def estimator_kind(kind):
+    """0 / 1 / 2 for 0 / 1 / 2 or "music" / "capon" / "bartlett" (any letter case); ValueError otherwise."""
+    if isinstance(kind, str):
+        if kind.lower() not in ESTIMATORS:
+            raise ValueError("estimator must be 0, 1, 2 or one of %s, not %r" % (sorted(ESTIMATORS), kind))
+        return ESTIMATORS[kind.lower()]
+    if isinstance(kind, bool) or kind not in (0, 1, 2):
+        raise ValueError("estimator must be 0, 1, 2 or one of %s, not %r" % (sorted(ESTIMATORS), kind))
+    return int(kind)
+
+
+def _set_estimator(h, kind):
+    # EXTENSION, no reference counterpart: the Capon (1) or Bartlett (2) spectrum in place of MUSIC (0, the reference), see
+    # include/baz_music_hip.h.  Stays in force across set_frequency().
+    h.impl.set_estimator(estimator_kind(kind))
+
+
 def _set_beam_mode(h, mode, loading):
     # EXTENSION, no reference counterpart: the MVDR beamformer output y = w^H X per reported entry over the item's own snapshots
     # (behind last_beams()), see include/baz_music_hip.h.  Stays in force across set_frequency().
@@ -247,6 +267,12 @@ if _HAVE_GR:
             (1: behind last_powers(); 2: also on the lvl port; 0: off).  The constructor keeps the reference's signature."""
             _set_power_mode(self, power_mode)
 
+        def set_estimator(self, kind):
+            """Opt-in (not reference behaviour): the spectrum estimator, 0 / "music" (the reference), 1 / "capon" or
+            2 / "bartlett": powers in the units of the covariance for every bin, no emitter count needed.  The constructor keeps
+            the reference's signature."""
+            _set_estimator(self, kind)
+
         def last_powers(self, count):
             """The float64 power estimates of the first `count` (item, slot) entries of the last work() call."""
             return numpy.asarray(self.impl.last_powers(int(count)), dtype=numpy.float64)
@@ -322,6 +348,12 @@ else:
             """Opt-in (not reference behaviour): a Capon power estimate per reported entry, in the units of the covariance
             (1: behind last_powers(); 2: also on the lvl port; 0: off).  The constructor keeps the reference's signature."""
             _set_power_mode(self, power_mode)
+
+        def set_estimator(self, kind):
+            """Opt-in (not reference behaviour): the spectrum estimator, 0 / "music" (the reference), 1 / "capon" or
+            2 / "bartlett": powers in the units of the covariance for every bin, no emitter count needed.  The constructor keeps
+            the reference's signature."""
+            _set_estimator(self, kind)
 
         def last_powers(self, count):
             """The float64 power estimates of the first `count` (item, slot) entries of the last work() call."""

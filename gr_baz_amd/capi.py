@@ -46,7 +46,9 @@ SYMBOLS = [
     "baz_music_calibrate", "baz_music_calibrate_device", "baz_music_calibration_estimate",
     "baz_music_set_averaging", "baz_music_get_averaging", "baz_music_reset_averaging", "baz_music_averaging_weights",
     "baz_music_debug_average",
+    "baz_music_set_estimator", "baz_music_get_estimator", "baz_music_spectrum_estimate",
 ]
+ESTIMATOR_MUSIC, ESTIMATOR_CAPON, ESTIMATOR_BARTLETT = 0, 1, 2   # BAZ_MUSIC_ESTIMATOR_*
 MAX_AVG_WINDOW = 64                 # BAZ_MUSIC_MAX_AVG_WINDOW
 ORDER_MODES = {None: 0, "mdl": 1, "aic": 2}   # baz_music_set_order_mode: criterion by name
 SMOOTH_WORKSPACE_BYTES = 128 << 20  # BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES: re-stacked items per chunk while smoothing is on
@@ -206,6 +208,13 @@ def _bind(L):
                                            ctypes.POINTER(ctypes.c_double)]
     L.baz_music_set_beam_mode.restype = ctypes.c_int
     L.baz_music_set_beam_mode.argtypes = [_vp, ctypes.c_int, ctypes.c_double]
+    L.baz_music_set_estimator.restype = ctypes.c_int
+    L.baz_music_set_estimator.argtypes = [_vp, ctypes.c_int]
+    L.baz_music_get_estimator.restype = ctypes.c_int
+    L.baz_music_get_estimator.argtypes = [_vp, ctypes.POINTER(ctypes.c_int)]
+    L.baz_music_spectrum_estimate.restype = ctypes.c_int
+    L.baz_music_spectrum_estimate.argtypes = [ctypes.c_int, _u32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), _u32,
+                                              ctypes.POINTER(ctypes.c_double)]
     L.baz_music_get_beam_mode.restype = ctypes.c_int
     L.baz_music_get_beam_mode.argtypes = [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double)]
     L.baz_music_last_beams.restype = ctypes.c_int
@@ -515,6 +524,17 @@ class Context:
             self._chk(r, "baz_music_last_powers")
         return out[:r].copy()
 
+    def set_estimator(self, kind):
+        """Opt-in extension (not reference behaviour): the spectrum estimator -- ESTIMATOR_MUSIC (0, the default: the reference),
+        ESTIMATOR_CAPON (1) or ESTIMATOR_BARTLETT (2): powers in the units of R for every bin, ang / lvl picked from the float32
+        spectrum (include/baz_music_hip.h)."""
+        self._chk(self._L.baz_music_set_estimator(self._h, int(kind)), "baz_music_set_estimator")
+
+    def get_estimator(self):
+        kind = ctypes.c_int(0)
+        self._chk(self._L.baz_music_get_estimator(self._h, ctypes.byref(kind)), "baz_music_get_estimator")
+        return int(kind.value)
+
     def set_beam_mode(self, mode, loading=0.0):
         """Opt-in extension (not reference behaviour): 1 computes the MVDR weights w = R^-1 a / (a^H R^-1 a) of every reported entry
         and the beam y = w^H X over the item's snapshots (last_beams, last_beam_weights; every port unchanged); `loading` adds
@@ -703,6 +723,23 @@ def power_estimate(R, a):
                                        out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
     if r != OK:
         raise ValueError("baz_music_power_estimate: %s" % lib().baz_music_strerror(r).decode())
+    return out[:a.shape[0]].copy()
+
+
+def spectrum_estimate(kind, R, rows):
+    """HOST-ONLY: the Capon (kind 1) or Bartlett (kind 2) spectrum values the library's definition gives for one covariance R
+    (m x m complex) and the steering rows (count x m complex64) (needs no device).  Returns a float64 array, one value per row."""
+    R = np.ascontiguousarray(R, dtype=np.complex128)
+    if R.ndim != 2 or R.shape[0] != R.shape[1]:
+        raise ValueError("spectrum_estimate: R must be a square matrix")
+    m = R.shape[0]
+    a = np.ascontiguousarray(rows, dtype=np.complex64).reshape(-1, m) if m else np.zeros((0, 0), np.complex64)
+    out = np.zeros(max(a.shape[0], 1), np.float64)
+    r = lib().baz_music_spectrum_estimate(int(kind), m, R.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                          a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), a.shape[0],
+                                          out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    if r != OK:
+        raise ValueError("baz_music_spectrum_estimate: %s" % lib().baz_music_strerror(r).decode())
     return out[:a.shape[0]].copy()
 
 

@@ -20,6 +20,7 @@
 #include "beam_kernels.hip.h"
 #include "calib_kernels.hip.h"
 #include "average_kernels.hip.h"
+#include "spectrum_kernels.hip.h"
 
 #include <algorithm>
 #include <array>
@@ -362,6 +363,10 @@ struct baz_music_ctx {
     size_t cal_in_cap = 0;          // floats
     double* dCalPart = nullptr;     // the runs' partial sums, [groups][2 m^2], then R-bar, [2 m^2]
     size_t cal_part_cap = 0;        // doubles
+    // Opt-in choice of estimator (baz_music_set_estimator; NOT reference behaviour; spectrum_kernels.hip.h).  While
+    // estimator is 0 none of the mode's kernels is launched and nothing is allocated for it.  With it on the spectrum is written to
+    // port 2 or, where that is not wired, to the private spectrum peak mode keeps (dPeakSpec).
+    int estimator = 0;              // 0: MUSIC (the reference); 1: Capon; 2: Bartlett
     size_t chunk_bytes = 0;   // host-fed path: traffic per pipelined chunk (BAZ_MUSIC_CHUNK_MIB); 0 = by buffer kind
     // host-fed path: page ranges of the caller's buffers this context has page-locked (baz_music_host_register)
     struct HostPin { uintptr_t lo, hi; uint32_t asked; };   // [lo, hi): the caller's exact bytes
@@ -2446,7 +2451,78 @@ int launch_beam_apply(baz_music_ctx* c, const void* d_in, uint32_t batch)
 #undef BAZ_CALL
 }
 
+// ---- opt-in Capon / Bartlett spectrum estimators (spectrum_kernels.hip.h) ----------------------------------------------------------
+// Launch geometry of spectrum_scan_kernel: groups of IG items times ranges of whole 256-bin passes.  A workgroup factorises its
+// items once per range (m^3 / 3 against m^2 / 2 per bin), so a row is cut only while the launch has fewer than ~8 workgroups per CU.
+struct SpecGeom { uint32_t groups, nranges, range_bins; };
+SpecGeom spectrum_geometry(const baz_music_ctx* c, uint32_t batch, uint32_t ig)
+{
+    SpecGeom g;
+    g.groups = (batch + ig - 1) / ig;
+    const uint32_t passes = (c->res + 255u) / 256u;
+    const uint32_t want = std::max<uint32_t>(1u, (8u * c->num_cus + g.groups - 1) / g.groups);
+    const uint32_t per = (passes + std::min(want, passes) - 1) / std::min(want, passes);     // passes per range
+    g.range_bins = per * 256u;
+    g.nranges = (passes + per - 1) / per;
+    return g;
+}
+
+template <int M>
+int launch_spectrum_t(baz_music_ctx* c, bazspectrum::SpectrumArgs& A)
+{
+    const SpecGeom g = spectrum_geometry(c, A.batch, (uint32_t)bazspectrum::ScanGeom<M>::IG);
+    if ((uint64_t)g.groups * g.nranges > 0x7fffffffull) return BAZ_MUSIC_E_UNSUPPORTED;   // (the grid's x extent)
+    A.nranges = g.nranges;
+    A.range_bins = g.range_bins;
+    if (c->estimator == BAZ_MUSIC_ESTIMATOR_CAPON)
+        hipLaunchKernelGGL((bazspectrum::spectrum_scan_kernel<M, bazspectrum::KIND_CAPON>), dim3(g.groups * g.nranges), dim3(256), 0, c->stream, A);
+    else
+        hipLaunchKernelGGL((bazspectrum::spectrum_scan_kernel<M, bazspectrum::KIND_BARTLETT>), dim3(g.groups * g.nranges), dim3(256), 0, c->stream, A);
+    HIP_TRY(c, hipGetLastError());
+    return BAZ_MUSIC_OK;
+}
+
+// The scan of `batch` items: reads the covariances this sequence's frontend left (averaged where that mode is on) and the raw image
+// of the table in force, writes every word of d_spec.
+int launch_spectrum(baz_music_ctx* c, uint32_t batch, float* d_spec)
+{
+    ProfScope ps(c, BAZ_MUSIC_STAGE_SCAN);
+    BAZ_REQUIRE_TAB(c, dRW);
+    if (c->avg_window > 1) BAZ_REQUIRE(c, dRavg); else BAZ_REQUIRE(c, dR);
+    if (const int rn = refuse_null(c, d_spec, "d_spec (estimator)")) return rn;
+    if (c->res > 0x7fffff00u) return BAZ_MUSIC_E_UNSUPPORTED;                             // (bin + 256 in 32 bits)
+    bazspectrum::SpectrumArgs A;
+    A.R = c->avg_window > 1 ? c->dRavg : c->dR;
+    A.raw = c->tab.dRW;
+    A.spec = d_spec;
+    A.rel_floor = BAZ_MUSIC_POWER_PIVOT_FLOOR;
+    A.batch = batch; A.res = c->res;
+    A.nranges = 1; A.range_bins = 256;
+#define BAZ_CALL(MV) launch_spectrum_t<MV>(c, A)
+    switch (c->m) {
+        BAZ_M_CASES(BAZ_CALL)
+        default: return BAZ_MUSIC_E_UNSUPPORTED;
+    }
+#undef BAZ_CALL
+}
+
+// the reference's top-n rule on the float32 spectrum the scan just wrote (peak mode 0 under an estimator)
+int launch_topn_spec(baz_music_ctx* c, uint32_t batch, float* d_ang, float* d_lvl, const float* d_spec)
+{
+    ProfScope ps(c, BAZ_MUSIC_STAGE_MERGE);
+    auto* kernel = &bazspectrum::topn_spec_kernel<16>;
+    switch (topn_list_len(c->n)) {
+        case 2: kernel = &bazspectrum::topn_spec_kernel<2>; break;
+        case 4: kernel = &bazspectrum::topn_spec_kernel<4>; break;
+        case 8: kernel = &bazspectrum::topn_spec_kernel<8>; break;
+        default: break;
+    }
+    hipLaunchKernelGGL(kernel, dim3((batch + 3) / 4), dim3(256), 0, c->stream, d_spec, d_ang, d_lvl, batch, c->res, c->n);
+    return launch_rc(c);
+}
+
 int process_device_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void* d_ang, void* d_lvl, void* d_spec);
+int process_estimator_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void* d_ang, void* d_lvl, void* d_spec);
 
 // One launch sequence over `batch` items.  Averaging on: a sequence that fails forgets the history (the stream position the host
 // keeps no longer describes what the device holds); the next item is t = 0.
@@ -2465,6 +2541,7 @@ int process_device_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void
         if (rw == BAZ_MUSIC_OK) c->stat_next_clean = true;    // (no scan statistic on this path: the counters stay 0)
         return rw;
     }
+    if (c->estimator) return process_estimator_body(c, d_in, batch, d_ang, d_lvl, d_spec);
     int r = ensure_workspace(c, batch);
     if (r) return r;
     r = reserve_candidates(c, batch);
@@ -2533,6 +2610,61 @@ int process_device_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void
     }
     if (c->beam_mode) {            // the last two launches: ang / lvl where neither refine_kernel nor power_kernel has written them
         const bool earlier = c->refine_mode || c->power_mode;
+        r = launch_beam_weights(c, batch, earlier ? nullptr : static_cast<float*>(d_ang), earlier ? nullptr : static_cast<float*>(d_lvl));
+        if (r == BAZ_MUSIC_OK) r = launch_beam_apply(c, d_in, batch);
+        if (r) return r;
+        c->out_beam.count += batch;
+    }
+    return BAZ_MUSIC_OK;
+}
+
+// The sequence of a context whose estimator is Capon or Bartlett (up to BAZ_MUSIC_FAST_M antennas; the emitter-count mode, refinement
+// and smoothing are refused while it is on): the covariance kernels of the two-kernel frontend (also at the fused shape), the averaging
+// stage where it is on, spectrum_scan_kernel, a picker on the float32 spectrum, then the power / beam kernels where they are on.  No
+// EVD, no MUSIC scan, no merge: nothing clears the next call's statistic counter, so stat_next_clean stays false and
+// begin_statistic's memset takes over; nothing adds to this call's counter (baz_music_refined_values reports 0).  Of the workspace
+// only dR is touched: the projector / noise-vector / candidate buffers are neither demanded nor sized here.
+int process_estimator_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void* d_ang, void* d_lvl, void* d_spec)
+{
+    int r = ensure_workspace(c, batch);
+    if (r) return r;
+    if (c->avg_window > 1) {
+        r = ensure_average(c, c->avg_window, batch);
+        if (r) return r;
+        BAZ_REQUIRE(c, dRavg); BAZ_REQUIRE(c, dAvgHist[0]); BAZ_REQUIRE(c, dAvgHist[1]);
+    }
+    BAZ_REQUIRE(c, dRefined); BAZ_REQUIRE(c, dR); BAZ_REQUIRE_TAB(c, dRW);
+    for (const SideMode& md : side_modes(c))
+        if (const int rs = side_refuse(c, md, batch)) return rs;
+    r = launch_cov(c, static_cast<const float*>(d_in), batch, c->dR);
+    if (r == BAZ_MUSIC_OK && c->avg_window > 1) r = launch_average(c, c->dR, batch, c->dRavg);
+    if (r) return r;
+    float* spec = static_cast<float*>(d_spec);
+    if (!spec) {                   // the pickers read the spectrum: the private one when port 2 is not wired
+        r = grow(c, c->dPeakSpec, c->peak_spec_cap, (size_t)batch * c->res);
+        if (r) return r;
+        spec = c->dPeakSpec;
+    }
+    float* ang = static_cast<float*>(d_ang);
+    float* lvl = static_cast<float*>(d_lvl);
+    const size_t entries = (size_t)batch * c->n;
+    if (c->power_mode || c->beam_mode) {   // the pickers' staging, as on the MUSIC sequence
+        r = grow(c, c->dRefAl, c->ref_al_cap, entries * 2);
+        if (r) return r;
+        ang = c->dRefAl;
+        lvl = c->dRefAl + entries;
+    }
+    r = launch_spectrum(c, batch, spec);
+    if (r) return r;
+    r = c->peak_mode ? launch_peaks(c, batch, ang, lvl, spec) : launch_topn_spec(c, batch, ang, lvl, spec);
+    if (r) return r;
+    if (c->power_mode) {
+        r = launch_power(c, batch, static_cast<float*>(d_ang), static_cast<float*>(d_lvl));
+        if (r) return r;
+        c->out_pow.count += batch;
+    }
+    if (c->beam_mode) {
+        const bool earlier = c->power_mode != 0;
         r = launch_beam_weights(c, batch, earlier ? nullptr : static_cast<float*>(d_ang), earlier ? nullptr : static_cast<float*>(d_lvl));
         if (r == BAZ_MUSIC_OK) r = launch_beam_apply(c, d_in, batch);
         if (r) return r;
@@ -3118,6 +3250,7 @@ int baz_music_reserve(baz_music_ctx* c, uint32_t max_batch)
     }
     int r = ensure_workspace(c, max_batch);
     if (r == BAZ_MUSIC_OK && (c->refine_mode || c->power_mode || c->beam_mode)) r = grow(c, c->dRefAl, c->ref_al_cap, (size_t)max_batch * c->n * 2);   // (the pickers' staging)
+    if (r == BAZ_MUSIC_OK && c->estimator) r = grow(c, c->dPeakSpec, c->peak_spec_cap, (size_t)max_batch * c->res);   // (the private spectrum of calls without port 2)
 #ifdef BAZ_MUSIC_LAB
     if (r == BAZ_MUSIC_OK && c->sort_mode != 0) r = ensure_sort_workspace(c, max_batch);
 #endif
@@ -3415,9 +3548,13 @@ const char* baz_music_stage_name(baz_music_ctx* c, int stage)
         std::lock_guard<std::mutex> lk(c->mtx);
         if (c->sm.inner) return "";   // smoothing on: no stage of this context runs (baz_music_set_smoothing)
         // averaging on: the fused shape runs its two-kernel form (launch_frontend)
-        if (stage == BAZ_MUSIC_STAGE_COV && c->fused_covevd && c->avg_window > 1) return "bazmusic::cov4_x4_kernel";
+        if (stage == BAZ_MUSIC_STAGE_COV && c->fused_covevd && (c->avg_window > 1 || c->estimator)) return "bazmusic::cov4_x4_kernel";
     }
     if (stage == BAZ_MUSIC_STAGE_SCAN && !c->wide) {
+        {
+            std::lock_guard<std::mutex> lk(c->mtx);
+            if (c->estimator) return "bazspectrum::spectrum_scan_kernel";
+        }
         // the kernel the LAST scan launch took (it depends on the wiring of the call and on the table in force: ADVICE r4);
         // before the first launch: what a call with the spectrum port would take
         // (the four names are formatted once, in baz_music_create: the pointer handed out stays valid for the context's life)
@@ -3986,7 +4123,7 @@ int baz_music_set_smoothing(baz_music_ctx* c, uint32_t subarray, int forward_bac
     }
     {   // (the beam mode has no m-antenna weight vector for the inner context's re-stacked items)
         std::lock_guard<std::mutex> lk(c->mtx);
-        if (c->beam_mode) return BAZ_MUSIC_E_UNSUPPORTED;
+        if (c->beam_mode || c->estimator) return BAZ_MUSIC_E_UNSUPPORTED;   // (nor does the estimator choice reach the inner context)
     }
     if (c->calib_on) return BAZ_MUSIC_E_UNSUPPORTED;   // (raw data under Gamma != c I is not shift invariant; calib_on changes under tab_mtx)
     bazsmooth::Perm perm = {};
@@ -4000,7 +4137,7 @@ int baz_music_set_smoothing(baz_music_ctx* c, uint32_t subarray, int forward_bac
     if (r != BAZ_MUSIC_OK) return r;
     {
         std::lock_guard<std::mutex> lk(c->mtx);   // a batch sees the old mode or the new one
-        r = c->beam_mode ? BAZ_MUSIC_E_UNSUPPORTED : baz_music_set_stream(inner, c->stream);   // (set_beam_mode may have come in between)
+        r = (c->beam_mode || c->estimator) ? BAZ_MUSIC_E_UNSUPPORTED : baz_music_set_stream(inner, c->stream);   // (set_beam_mode / set_estimator may have come in between)
         if (r == BAZ_MUSIC_OK) r = baz_music_set_peak_mode(inner, c->peak_mode);
         if (r == BAZ_MUSIC_OK) r = baz_music_set_order_mode(inner, c->order_mode);
         if (r == BAZ_MUSIC_OK) r = baz_music_set_refine_mode(inner, c->refine_mode);
@@ -4028,6 +4165,7 @@ int baz_music_set_order_mode(baz_music_ctx* c, int criterion)
     if (!c || criterion < 0 || criterion > 2) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
     if (criterion && c->wide) return BAZ_MUSIC_E_UNSUPPORTED;   // the ORDER epilogues exist for the specialised kernels only
+    if (criterion && c->estimator) return BAZ_MUSIC_E_UNSUPPORTED;   // (Capon / Bartlett compute no eigenvalues)
     if (c->sm.inner) {   // (the inner context is never wider than this one)
         const int r = baz_music_set_order_mode(c->sm.inner, criterion);
         if (r != BAZ_MUSIC_OK) return r;
@@ -4085,6 +4223,7 @@ int baz_music_set_refine_mode(baz_music_ctx* c, int mode)
     if (!c || (mode != 0 && mode != 1)) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
     if (mode && c->wide) return BAZ_MUSIC_E_UNSUPPORTED;   // no peak picker on the run-time-m path: only first entries would move
+    if (mode && c->estimator) return BAZ_MUSIC_E_UNSUPPORTED;   // (the fit is on the MUSIC denominator)
     if (c->sm.inner) {   // (the inner context is never wider than this one)
         const int r = baz_music_set_refine_mode(c->sm.inner, mode);
         if (r != BAZ_MUSIC_OK) return r;
@@ -4214,6 +4353,38 @@ int baz_music_power_estimate(uint32_t m, const double* R_ri, const float* a_ri, 
     if (!R_ri || !a_ri || !out) return BAZ_MUSIC_E_INVALID;
     bazcapon::HostSolve S(m, R_ri, nullptr, BAZ_MUSIC_POWER_PIVOT_FLOOR);
     for (uint32_t e = 0; e < count; ++e) out[e] = S.ok ? bazcapon::power_from_s(S.solve(a_ri + 2 * (size_t)e * m)) : 0.0;
+    return BAZ_MUSIC_OK;
+}
+
+int baz_music_set_estimator(baz_music_ctx* c, int kind)
+{
+    if (!c || kind < BAZ_MUSIC_ESTIMATOR_MUSIC || kind > BAZ_MUSIC_ESTIMATOR_BARTLETT) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    if (kind && c->wide) return BAZ_MUSIC_E_UNSUPPORTED;   // (spectrum_scan_kernel is specialised per m, like the other modes' kernels)
+    // the emitter-count mode needs eigenvalues, refinement fits the MUSIC denominator, smoothing runs an inner MUSIC context
+    if (kind && (c->order_mode || c->refine_mode || c->sm.inner)) return BAZ_MUSIC_E_UNSUPPORTED;
+    c->estimator = kind;
+    return BAZ_MUSIC_OK;
+}
+
+int baz_music_get_estimator(const baz_music_ctx* c, int* kind)
+{
+    if (!c || !kind) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(const_cast<baz_music_ctx*>(c)->mtx);
+    *kind = c->estimator;
+    return BAZ_MUSIC_OK;
+}
+
+// The definitions of include/baz_music_hip.h on the host: Capon through bazcapon::HostSolve exactly as baz_music_power_estimate (the
+// same bits), Bartlett through bazspectrum::bartlett_host.
+int baz_music_spectrum_estimate(int kind, uint32_t m, const double* R_ri, const float* a_ri, uint32_t count, double* out)
+{
+    if (kind != BAZ_MUSIC_ESTIMATOR_CAPON && kind != BAZ_MUSIC_ESTIMATOR_BARTLETT) return BAZ_MUSIC_E_INVALID;
+    if (kind == BAZ_MUSIC_ESTIMATOR_CAPON) return baz_music_power_estimate(m, R_ri, a_ri, count, out);
+    if (m < 1 || m > BAZ_MUSIC_MAX_M) return BAZ_MUSIC_E_INVALID;
+    if (count == 0) return BAZ_MUSIC_OK;
+    if (!R_ri || !a_ri || !out) return BAZ_MUSIC_E_INVALID;
+    for (uint32_t e = 0; e < count; ++e) out[e] = bazspectrum::bartlett_host(m, R_ri, a_ri + 2 * (size_t)e * m);
     return BAZ_MUSIC_OK;
 }
 

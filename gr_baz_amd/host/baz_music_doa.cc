@@ -201,6 +201,13 @@ void baz_music_doa::set_power_mode(int mode)
     if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: set_power_mode: ") + baz_music_strerror(rc));
 }
 
+void baz_music_doa::set_estimator(int kind)
+{
+    const int rc = baz_music_set_estimator(d_ctx, kind);
+    if (rc == BAZ_MUSIC_E_INVALID) throw std::invalid_argument("music_doa: set_estimator: kind must be 0 (MUSIC), 1 (Capon) or 2 (Bartlett)");
+    if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: set_estimator: ") + baz_music_strerror(rc));
+}
+
 std::vector<double> baz_music_doa::last_powers(unsigned int count)
 {
     std::vector<double> out(count);

@@ -79,6 +79,10 @@ public:
      * last work() call in fp64. */
     void set_power_mode(int mode);
     std::vector<double> last_powers(unsigned int count);
+    /* Extension, off by default (not in the reference): the spectrum estimator (baz_music_set_estimator, include/baz_music_hip.h).
+     * kind 0 is MUSIC (the reference), 1 the Capon and 2 the Bartlett spectrum: powers in the units of the covariance for every bin,
+     * no emitter count needed; ang / lvl are picked from the float32 spectrum. */
+    void set_estimator(int kind);
     /* Extension, off by default (not in the reference): the MVDR beamformer output y = w^H X of every reported entry over the item's
      * own snapshots, w = R^-1 a / (a^H R^-1 a) (baz_music_set_beam_mode, include/baz_music_hip.h).  mode 1 computes them and leaves
      * every port as it is; loading >= 0 adds loading * mean diagonal to R's diagonal.  last_beams: the beams of the first `items`

@@ -247,6 +247,7 @@ PYBIND11_MODULE(_baz_music, mod)
         .def("set_refine_mode", [](music_doa_handle& h, bool on) { h.blk->set_refine_mode(on); }, py::arg("parabolic"))
         .def("set_power_mode", [](music_doa_handle& h, int mode) { h.blk->set_power_mode(mode); }, py::arg("mode"))
         .def("last_powers", [](music_doa_handle& h, unsigned int count) { return h.blk->last_powers(count); }, py::arg("count"))
+        .def("set_estimator", [](music_doa_handle& h, int kind) { h.blk->set_estimator(kind); }, py::arg("kind"))
         .def("set_beam_mode", [](music_doa_handle& h, int mode, double loading) { h.blk->set_beam_mode(mode, loading); },
              py::arg("mode"), py::arg("loading") = 0.0)
         .def("last_beams", [](music_doa_handle& h, unsigned int items) {

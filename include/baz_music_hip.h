@@ -568,6 +568,53 @@ BAZ_MUSIC_API int baz_music_calibrate(baz_music_ctx* ctx, const float* in_ri, ui
 BAZ_MUSIC_API int baz_music_calibrate_device(baz_music_ctx* ctx, const void* d_in, uint32_t batch, const float* ref_ri, double* gamma_ri,
                                              double* quality, double* Rbar_ri);
 BAZ_MUSIC_API int baz_music_calibration_estimate(uint32_t m, const double* Rbar_ri, const float* ref_ri, double* gamma_ri, double* quality);
+/* OPT-IN extension, NOT reference behaviour: a choice of spectrum ESTIMATOR.  MUSIC needs the emitter count n to split the
+ * signal subspace from the noise subspace (with n too small the spectrum is wrong, not merely wider) and its 1 / ||G^H a||^2 has no unit.
+ * The Capon (minimum-variance) and Bartlett (conventional beamformer) spectra need no count and no eigendecomposition and are powers in the
+ * units of R over the whole circle.  kind: BAZ_MUSIC_ESTIMATOR_MUSIC (0, the default: the reference), _CAPON (1), _BARTLETT (2); anything
+ * else BAZ_MUSIC_E_INVALID and the previous kind stays in force.
+ *   DEFINITION  for kind 1 and 2 the item's R is taken exactly as the power mode takes it: the covariance baz_music_debug_cov returns,
+ *               Rbar_t with averaging on, read from the lower triangle as stored, the imaginary part of the diagonal ignored.  a = row b
+ *               of the table in force, widened exactly from complex64.  For every bin b:
+ *                 Capon     P_C(b) = the power mode's P for row b: the same unpivoted LDL^H, the same BAZ_MUSIC_POWER_PIVOT_FLOOR degeneracy
+ *                           rule, the same s -> P step.  A degenerate item's whole row is 0; a bin whose s is 0 or not finite is 0.
+ *                 Bartlett  P_B(b) = q / (w w),  w = sum_i |a_i|^2,
+ *                           y_i = sum_{j<i} R_ij a_j + Re(R_ii) a_i + sum_{j>i} conj(R_ji) a_j,  q = sum_i Re(conj(a_i) y_i),
+ *                           all sums in index order; 0 when w == 0 or when q or w is not finite.  For unit-modulus rows this is
+ *                           a^H R a / m^2: an emitter's power plus sigma^2 / m, the unit of P_C.
+ *               Both are linear in R: R -> sR gives sP, exactly so for s a power of two.  The spectrum port carries (float)P(b) for
+ *               every bin.  ang / lvl are taken FROM THOSE float32 VALUES AS STORED: with peak mode 0 by the reference's rule (the n
+ *               largest values in descending order, the earlier bin first on ties, a value reported only if it is > 0, NaN never,
+ *               missing entries (0, 0): lib/baz_music_doa.cc:95,129-141), with peak mode 1 the n strongest local maxima;
+ *               lvl[i] == spectrum[bin_i] holds bit for bit.  n keeps its meaning as the number of reported entries (create's n < m
+ *               rule stays).  The device evaluates P in fp64 in its own operation order (1 / d_i multiplied in; q over the lower
+ *               triangle): a stored float32 is within one ulp_f32 of (float) of the host definition, zeros are exact.
+ *               tests/spectrum_ref.py restates this in numpy.
+ *   WHAT RUNS   the covariance kernels of the two-kernel frontend (also at 4 antennas with K % 256 == 0, as under averaging), the
+ *               averaging stage where it is on, spectrum_scan_kernel (gr_baz_amd/csrc/spectrum_kernels.hip.h; its time counts under
+ *               BAZ_MUSIC_STAGE_SCAN): a 256-thread workgroup factorises 64 / 32 / 16 items into LDS, then every lane takes one bin and
+ *               walks the group's items; then a picker on the float32 spectrum (topn_spec_kernel, or peak_pick_kernel under peak mode
+ *               1), then the power and beam kernels where those modes are on.  No EVD kernel, no MUSIC scan and no merge kernel is
+ *               launched; baz_music_refined_values reports 0.  Without the spectrum port the scan writes a private spectrum of the
+ *               context (baz_music_reserve sizes it while a kind is set).  Kind 0 launches exactly the kernels it launched before the
+ *               mode existed, allocates nothing new and is the reference bit for bit: a context never set, one set to 0, one switched
+ *               on and off again.
+ *   SCOPE       up to BAZ_MUSIC_FAST_M antennas (BAZ_MUSIC_E_UNSUPPORTED beyond), like the other modes.  Composes with peak mode,
+ *               averaging, calibration and retune (the table image in force for the batch), the power and beam modes (they read R and
+ *               the staged entries) and the host-fed baz_music_process.  It does NOT compose with the emitter-count mode (no
+ *               eigenvalues), refinement (the fit is on the MUSIC denominator) or smoothing: whichever of the two is set second returns
+ *               BAZ_MUSIC_E_UNSUPPORTED and the setting already in force stays.
+ *   WHEN        set_estimator takes effect for items submitted after it returns and is serialised against process*() like
+ *               set_peak_mode: a batch sees the old kind or the new one.  The previous kind stays in force after any error.
+ * spectrum_estimate needs no device: one R (m*m complex128, row-major, re / im interleaved) and `count` steering rows (m complex64 each)
+ * give `count` values by the definition above -- kind 1 the bits of baz_music_power_estimate (the same routine), kind 2 the loop above;
+ * 1 <= m <= BAZ_MUSIC_MAX_M; BAZ_MUSIC_E_INVALID for kind 0 or an unknown kind, m out of range or a NULL array with count > 0. */
+#define BAZ_MUSIC_ESTIMATOR_MUSIC    0   /* the default: the reference */
+#define BAZ_MUSIC_ESTIMATOR_CAPON    1
+#define BAZ_MUSIC_ESTIMATOR_BARTLETT 2
+BAZ_MUSIC_API int baz_music_set_estimator(baz_music_ctx* ctx, int kind);
+BAZ_MUSIC_API int baz_music_get_estimator(const baz_music_ctx* ctx, int* kind);
+BAZ_MUSIC_API int baz_music_spectrum_estimate(int kind, uint32_t m, const double* R_ri, const float* a_ri, uint32_t count, double* out);
 /* Statistic: how many (item, bin) values of the LAST process call were recomputed in the reference's literal form
  * ||G^H a||^2 because the projector form a^H Q a put them at or below ~m 1e-8 max||a||^2 (near-nulls of the noise
  * subspace, SNR >~ 55 dB); blocks until that call is done (a host-fed call cut into chunks reports their sum).
