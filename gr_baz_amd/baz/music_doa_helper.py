@@ -217,6 +217,32 @@ def _calibrate_next(h, items, pilot_bin, ref, min_quality):
     h.impl.calibrate_next(int(items), p, float(min_quality))
 
 
+def _set_noise_covariance(h, rn):
+    # EXTENSION, no reference counterpart: noise pre-whitening with the m x m noise covariance rn = L L^H: the EVD decomposes
+    # W R W^H and the table in force becomes W a, W = L^-1, see include/baz_music_hip.h.  Stays in force across set_frequency()
+    # and set_calibration() (h.array_response stays the caller's table).
+    if rn is None:
+        h.impl.set_noise_covariance([])
+        return
+    R = numpy.asarray(rn, dtype=numpy.complex128)
+    if R.shape != (h.m, h.m):
+        raise ValueError("rn must be an m x m = %d x %d complex matrix" % (h.m, h.m))
+    h.impl.set_noise_covariance([complex(x) for x in R.reshape(-1)])
+
+
+def _noise_covariance(h):
+    rn = h.impl.noise_covariance()
+    return numpy.asarray(rn, dtype=numpy.complex128).reshape(h.m, h.m) if len(rn) else None
+
+
+def _whiten_next(h, items):
+    # EXTENSION: measure the noise covariance from the next `items` items of the stream (a noise-only capture: emitters off,
+    # or the antennas terminated) and switch the whitening on with it.
+    if int(items) <= 0:
+        raise ValueError("items must be > 0, not %r" % (items,))
+    h.impl.whiten_next(int(items))
+
+
 def _set_averaging(h, window, forgetting):
     # EXTENSION, no reference counterpart: the covariance of every item averaged over the last `window` items of the stream
     # (weights forgetting ** age), see include/baz_music_hip.h.  Stays in force across set_frequency(): covariances do not
@@ -312,6 +338,24 @@ if _HAVE_GR:
         def last_calibration_quality(self):
             return float(self.impl.last_calibration_quality())
 
+        def set_noise_covariance(self, rn):
+            """Opt-in (not reference behaviour): noise pre-whitening with the m x m noise covariance `rn` (Hermitian positive
+            definite), also after set_frequency() and set_calibration() (None: off).  Not available with set_smoothing, the beam
+            mode or the Capon / Bartlett estimators."""
+            _set_noise_covariance(self, rn)
+
+        def noise_covariance(self):
+            """The m x m complex128 noise covariance in force, or None while off."""
+            return _noise_covariance(self)
+
+        def whiten_next(self, items):
+            """Opt-in (not reference behaviour): measure the noise covariance from the next `items` items (a noise-only capture)
+            and apply it.  last_whitening_status(): -1 while waiting for the items, 0 once applied, else the error code."""
+            _whiten_next(self, items)
+
+        def last_whitening_status(self):
+            return int(self.impl.last_whitening_status())
+
 else:
 
     class music_doa_helper(object):
@@ -393,6 +437,24 @@ else:
 
         def last_calibration_quality(self):
             return float(self.impl.last_calibration_quality())
+
+        def set_noise_covariance(self, rn):
+            """Opt-in (not reference behaviour): noise pre-whitening with the m x m noise covariance `rn` (Hermitian positive
+            definite), also after set_frequency() and set_calibration() (None: off).  Not available with set_smoothing, the beam
+            mode or the Capon / Bartlett estimators."""
+            _set_noise_covariance(self, rn)
+
+        def noise_covariance(self):
+            """The m x m complex128 noise covariance in force, or None while off."""
+            return _noise_covariance(self)
+
+        def whiten_next(self, items):
+            """Opt-in (not reference behaviour): measure the noise covariance from the next `items` items (a noise-only capture)
+            and apply it.  last_whitening_status(): -1 while waiting for the items, 0 once applied, else the error code."""
+            _whiten_next(self, items)
+
+        def last_whitening_status(self):
+            return int(self.impl.last_whitening_status())
 
         def work(self, items):
             """Runs the wrapped block on (k, nsamples) complex64 items: returns (ang, lvl[, spectrum])."""

@@ -47,6 +47,8 @@ SYMBOLS = [
     "baz_music_set_averaging", "baz_music_get_averaging", "baz_music_reset_averaging", "baz_music_averaging_weights",
     "baz_music_debug_average",
     "baz_music_set_estimator", "baz_music_get_estimator", "baz_music_spectrum_estimate",
+    "baz_music_set_noise_covariance", "baz_music_get_noise_covariance", "baz_music_whitening_factor", "baz_music_whiten_table",
+    "baz_music_debug_whiten", "baz_music_mean_covariance", "baz_music_mean_covariance_device",
 ]
 ESTIMATOR_MUSIC, ESTIMATOR_CAPON, ESTIMATOR_BARTLETT = 0, 1, 2   # BAZ_MUSIC_ESTIMATOR_*
 MAX_AVG_WINDOW = 64                 # BAZ_MUSIC_MAX_AVG_WINDOW
@@ -256,6 +258,20 @@ def _bind(L):
     L.baz_music_calibrate_device.argtypes = [_vp, _vp, _u32, _f32p, _f64p, _f64p, _f64p]
     L.baz_music_calibration_estimate.restype = ctypes.c_int
     L.baz_music_calibration_estimate.argtypes = [_u32, _f64p, _f32p, _f64p, _f64p]
+    L.baz_music_set_noise_covariance.restype = ctypes.c_int
+    L.baz_music_set_noise_covariance.argtypes = [_vp, _f64p]
+    L.baz_music_get_noise_covariance.restype = ctypes.c_int
+    L.baz_music_get_noise_covariance.argtypes = [_vp, _f64p, ctypes.POINTER(ctypes.c_int)]
+    L.baz_music_whitening_factor.restype = ctypes.c_int
+    L.baz_music_whitening_factor.argtypes = [_u32, _f64p, _f64p]
+    L.baz_music_whiten_table.restype = ctypes.c_int
+    L.baz_music_whiten_table.argtypes = [_u32, _u32, _f32p, _f64p, _f32p]
+    L.baz_music_debug_whiten.restype = ctypes.c_int
+    L.baz_music_debug_whiten.argtypes = [_vp, _vp, _u32, _vp]
+    L.baz_music_mean_covariance.restype = ctypes.c_int
+    L.baz_music_mean_covariance.argtypes = [_vp, _f32p, _u32, _f64p]
+    L.baz_music_mean_covariance_device.restype = ctypes.c_int
+    L.baz_music_mean_covariance_device.argtypes = [_vp, _vp, _u32, _f64p]
     return L
 
 
@@ -617,6 +633,52 @@ class Context:
         """calibrate() on `batch` items in device memory (d_in: a plain integer pointer); blocks, the results are host arrays."""
         return self._calibrate(self._L.baz_music_calibrate_device, "baz_music_calibrate_device", _vp(d_in), batch, ref, want_rbar)
 
+    def set_noise_covariance(self, rn):
+        """Opt-in extension (not reference behaviour): noise pre-whitening with the m x m noise covariance `rn` (Hermitian positive
+        definite; its lower triangle is read).  The EVD decomposes W R W^H and the table in force becomes W a, W the inverse of rn's
+        Cholesky factor, across later set_table / set_calibration calls too (include/baz_music_hip.h); None (default): off."""
+        if rn is None:
+            self._chk(self._L.baz_music_set_noise_covariance(self._h, None), "baz_music_set_noise_covariance")
+            return
+        R = np.ascontiguousarray(np.asarray(rn, dtype=np.complex128))
+        if R.shape != (self.m, self.m):
+            raise ValueError("rn must be an m x m = %d x %d complex matrix" % (self.m, self.m))
+        self._chk(self._L.baz_music_set_noise_covariance(self._h, R.view(np.float64).ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
+                  "baz_music_set_noise_covariance")
+
+    def get_noise_covariance(self):
+        """The noise covariance in force (m x m complex128, as given), or None while the mode is off."""
+        R, on = np.zeros((self.m, self.m), np.complex128), ctypes.c_int(0)
+        self._chk(self._L.baz_music_get_noise_covariance(self._h, R.view(np.float64).ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                         ctypes.byref(on)), "baz_music_get_noise_covariance")
+        return R if on.value else None
+
+    def debug_whiten(self, d_R_in, batch, d_R_out):
+        """The whitening stage alone on `batch` caller-supplied covariances (device pointers, m*m complex128 each, not overlapping)."""
+        self._chk(self._L.baz_music_debug_whiten(self._h, _vp(d_R_in), int(batch), _vp(d_R_out)), "baz_music_debug_whiten")
+
+    def mean_covariance(self, items):
+        """The mean covariance Rbar (m x m complex128) of items ((batch, nsamples) complex64 host array): calibrate()'s Rbar without
+        a pilot -- of a noise-only capture, an estimate of the noise covariance for set_noise_covariance.  Blocks; changes nothing."""
+        x = np.ascontiguousarray(np.asarray(items, dtype=np.complex64))
+        if x.ndim == 1:
+            x = x[None, :]
+        if x.shape[1] != self.nsamples:
+            raise ValueError("items must be (batch, %d) complex64" % self.nsamples)
+        R = np.zeros((self.m, self.m), np.complex128)
+        self._chk(self._L.baz_music_mean_covariance(self._h, x.view(np.float32).ctypes.data_as(_f32p), x.shape[0],
+                                                    R.view(np.float64).ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
+                  "baz_music_mean_covariance")
+        return R
+
+    def mean_covariance_device(self, d_in, batch):
+        """mean_covariance() on `batch` items in device memory (d_in: a plain integer pointer); blocks, the result is a host array."""
+        R = np.zeros((self.m, self.m), np.complex128)
+        self._chk(self._L.baz_music_mean_covariance_device(self._h, _vp(d_in), int(batch),
+                                                           R.view(np.float64).ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
+                  "baz_music_mean_covariance_device")
+        return R
+
     def set_stream(self, hip_stream):
         self._chk(self._L.baz_music_set_stream(self._h, _vp(hip_stream) if hip_stream else None),
                   "baz_music_set_stream")
@@ -773,6 +835,38 @@ def calibration_apply(table, gamma):
                                           g.view(np.float32).ctypes.data_as(_f32p), out.view(np.float32).ctypes.data_as(_f32p))
     if r != OK:
         raise ValueError("baz_music_calibration_apply: %s" % lib().baz_music_strerror(r).decode())
+    return out
+
+
+def whitening_factor(rn):
+    """HOST-ONLY: W = L^-1 (m x m complex128, lower triangular, real positive diagonal) of the Cholesky factor rn = L L^H, by the
+    routine set_noise_covariance runs; ValueError where the setter would refuse (a non-finite entry, a pivot at or below the floor)."""
+    R = np.ascontiguousarray(rn, dtype=np.complex128)
+    if R.ndim != 2 or R.shape[0] != R.shape[1] or R.shape[0] < 1:
+        raise ValueError("whitening_factor: rn must be a square matrix")
+    W = np.zeros_like(R)
+    f64p = ctypes.POINTER(ctypes.c_double)
+    r = lib().baz_music_whitening_factor(R.shape[0], R.view(np.float64).ctypes.data_as(f64p), W.view(np.float64).ctypes.data_as(f64p))
+    if r != OK:
+        raise ValueError("baz_music_whitening_factor: %s" % lib().baz_music_strerror(r).decode())
+    return W
+
+
+def whiten_table(table, w):
+    """HOST-ONLY: the whitened table a'_r(bin) = fl32(sum_{k<=r} W_rk a_k(bin)) the library's definition gives (resolution x m
+    complex64; the device kernel's own routine, bit for bit; needs no device)."""
+    t = np.ascontiguousarray(np.asarray(table, dtype=np.complex64))
+    if t.ndim != 2 or not t.size:
+        raise ValueError("whiten_table: table must be resolution x m")
+    W = np.ascontiguousarray(w, dtype=np.complex128)
+    if W.shape != (t.shape[1], t.shape[1]):
+        raise ValueError("whiten_table: w must be m x m = %d x %d" % (t.shape[1], t.shape[1]))
+    out = np.zeros(t.shape, np.complex64)
+    r = lib().baz_music_whiten_table(t.shape[1], t.shape[0], t.view(np.float32).ctypes.data_as(_f32p),
+                                     W.view(np.float64).ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                     out.view(np.float32).ctypes.data_as(_f32p))
+    if r != OK:
+        raise ValueError("baz_music_whiten_table: %s" % lib().baz_music_strerror(r).decode())
     return out
 
 

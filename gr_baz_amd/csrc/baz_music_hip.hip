@@ -19,6 +19,7 @@
 #include "power_kernels.hip.h"
 #include "beam_kernels.hip.h"
 #include "calib_kernels.hip.h"
+#include "whiten_kernels.hip.h"
 #include "average_kernels.hip.h"
 #include "spectrum_kernels.hip.h"
 
@@ -225,6 +226,10 @@ struct baz_music_ctx {
         bool cs_ok = false;              // coarse image built and its scales representable
         bool i8_ok = false;              // digit image built (finite table, scale representable, size within I8_IMAGE_LIMIT)
         double refine_below = 0.0;       // literal-form refinement: threshold on d = a^H Q a
+        // opt-in noise pre-whitening (whiten_kernels.hip.h): the W this set's images were built under, m x m row-major.  It lives here so
+        // that the swap of a retune exchanges (images, W) together: a batch whitens with the W its table was whitened with.
+        double2* dWh = nullptr;          // allocated by the first build with the mode on
+        bool wh_on = false;              // the whiten stage runs for batches that read this set
     } tab, shadow;
     std::mutex tab_mtx;              // retunes among themselves (held for a whole baz_music_set_table; never while `mtx` is wanted by work())
     hipStream_t s_tab = nullptr;     // side stream of the table builders (highest priority: they are tiny)
@@ -363,6 +368,18 @@ struct baz_music_ctx {
     size_t cal_in_cap = 0;          // floats
     double* dCalPart = nullptr;     // the runs' partial sums, [groups][2 m^2], then R-bar, [2 m^2]
     size_t cal_part_cap = 0;        // doubles
+    // Opt-in noise pre-whitening (baz_music_set_noise_covariance; NOT reference behaviour; whiten_kernels.hip.h).  While it
+    // is off build_tables_device and the launch sequences launch what they launched before the mode existed and nothing below is
+    // allocated.  wh_on / wh_Rn / hWh change under `tab_mtx` (the table builders read them); wh_want -- the mode is on or being switched
+    // on -- changes under `mtx` (what set_beam_mode / set_estimator refuse on); the stage's buffers belong to the launch sequences (`mtx`).
+    bool wh_on = false;
+    bool wh_want = false;
+    std::vector<double> wh_Rn;      // Rn as given (m*m complex128), for get_noise_covariance
+    double2* hWh = nullptr;         // W, m x m row-major, page-locked: the builders copy it into the set they build
+    double2* dRwh = nullptr;        // R' of the launch in flight (what the EVD reads while the mode is on)
+    size_t rwh_cap = 0;             // double2 elements
+    double2* dWhT = nullptr;        // 17 .. 64 antennas: (W R)^H between the two passes
+    size_t wht_cap = 0;             // double2 elements
     // Opt-in choice of estimator (baz_music_set_estimator; NOT reference behaviour; spectrum_kernels.hip.h).  While
     // estimator is 0 none of the mode's kernels is launched and nothing is allocated for it.  With it on the spectrum is written to
     // port 2 or, where that is not wired, to the private spectrum peak mode keeps (dPeakSpec).
@@ -1058,15 +1075,73 @@ int launch_average(baz_music_ctx* c, const double2* dRin, uint32_t batch, double
     return BAZ_MUSIC_OK;
 }
 
+// ---- opt-in noise pre-whitening (whiten_kernels.hip.h) ------------------------------------------------------------------------------
+// The covariance in force: what this launch sequence's EVD decomposes and what refinement's vectors, the power / beam kernels and the
+// estimators' scan follow from -- R' where whitening is on, else the averaged covariances where averaging is on, else the plain ones.
+double2* cov_in_force(const baz_music_ctx* c)
+{
+    if (c->tab.wh_on) return c->dRwh;
+    return c->avg_window > 1 ? c->dRavg : c->dR;
+}
+
+// The stage's buffers for a launch of `items` items: R' and, on the 17 .. 64 antenna path, the pass between the two products.
+int ensure_whiten(baz_music_ctx* c, uint32_t items, bool want_out)
+{
+    const size_t need = (size_t)round_up(items, 64) * c->m * c->m;
+    int r = want_out ? grow(c, c->dRwh, c->rwh_cap, need) : BAZ_MUSIC_OK;
+    if (r == BAZ_MUSIC_OK && c->wide) r = grow(c, c->dWhT, c->wht_cap, need);
+    return r;
+}
+
+template <int M>
+int launch_whiten_t(baz_music_ctx* c, const double2* dRin, uint32_t batch, double2* dRout)
+{
+    constexpr uint32_t IPB = bazwhiten::WhitenGeom<M>::IPB;
+    hipLaunchKernelGGL((bazwhiten::whiten_kernel<M>), dim3((batch + IPB - 1) / IPB), dim3(bazwhiten::WhitenGeom<M>::THREADS), 0, c->stream,
+                       dRin, dRout, c->tab.dWh, batch);
+    HIP_TRY(c, hipGetLastError());
+    return BAZ_MUSIC_OK;
+}
+
+// The whitening stage of one launch sequence: dRout[i] = W dRin[i] W^H with the W of the table set in force, between the covariance
+// (or the averaging stage) and the EVD.  ensure_whiten() came first.
+int launch_whiten(baz_music_ctx* c, const double2* dRin, uint32_t batch, double2* dRout)
+{
+    ProfScope ps(c, BAZ_MUSIC_STAGE_COV);
+    if (const int rn = refuse_null(c, c->tab.dWh, "dWh")) return rn;
+    if (!dRin || !dRout) return refuse_null(c, nullptr, "dRwh (ensure_whiten)");
+    if (c->wide) {
+        if (c->wht_cap < (size_t)batch * c->m * c->m) return refuse_null(c, nullptr, "dWhT (ensure_whiten)");
+        const size_t lds = (size_t)c->m * (c->m + 1) / 2 * sizeof(double2);
+        hipLaunchKernelGGL((bazwhiten::whiten_wide_kernel<true>), dim3(batch), dim3(bazwhiten::WHITEN_THREADS), lds, c->stream, dRin, c->dWhT,
+                           c->tab.dWh, c->m);
+        HIP_TRY(c, hipGetLastError());
+        hipLaunchKernelGGL((bazwhiten::whiten_wide_kernel<false>), dim3(batch), dim3(bazwhiten::WHITEN_THREADS), lds, c->stream, c->dWhT, dRout,
+                           c->tab.dWh, c->m);
+        HIP_TRY(c, hipGetLastError());
+        return BAZ_MUSIC_OK;
+    }
+#define BAZ_CALL(MV) launch_whiten_t<MV>(c, dRin, batch, dRout)
+    switch (c->m) {
+        BAZ_M_CASES(BAZ_CALL)
+        default: return BAZ_MUSIC_E_UNSUPPORTED;
+    }
+#undef BAZ_CALL
+}
+
 // Covariance + EVD of `batch` items: the projector coefficients into `dQ` (the workspace's c->dQ, or a debug tap's own buffer), the
 // noise eigenvectors into c->dG.  The fused kernel where it applies, else two kernels through c->dR.  ensure_workspace() came first.
 int launch_frontend(baz_music_ctx* c, const void* d_in, uint32_t batch, double* dQ, uint32_t qstride)
 {
     const float* in = static_cast<const float*>(d_in);
-    if (c->avg_window > 1) {   // opt-in averaging: always two kernels through c->dR, the averaging stage between them (ensure_average() came first)
-        int ra = launch_cov(c, in, batch, c->dR);
-        if (ra == BAZ_MUSIC_OK) ra = launch_average(c, c->dR, batch, c->dRavg);
-        return ra ? ra : launch_evd(c, c->dRavg, batch, dQ, qstride, c->dG);
+    if (c->avg_window > 1 || c->tab.wh_on) {   // opt-in averaging / whitening: always two kernels through c->dR, the stages between them
+        int ra = launch_cov(c, in, batch, c->dR);       // (ensure_average() came first; average first, whiten second)
+        if (ra == BAZ_MUSIC_OK && c->avg_window > 1) ra = launch_average(c, c->dR, batch, c->dRavg);
+        if (ra == BAZ_MUSIC_OK && c->tab.wh_on) {
+            ra = ensure_whiten(c, batch, true);
+            if (ra == BAZ_MUSIC_OK) ra = launch_whiten(c, c->avg_window > 1 ? c->dRavg : c->dR, batch, c->dRwh);
+        }
+        return ra ? ra : launch_evd(c, cov_in_force(c), batch, dQ, qstride, c->dG);
     }
     // (power / beam mode on: the fused kernel also stores its R, the tap baz_music_debug_cov uses -- same kernel, same Q and G bits)
     if (c->fused_covevd) return launch_covevd(c, in, batch, dQ, qstride, c->dG, (c->power_mode || c->beam_mode) ? c->dR : nullptr);
@@ -1713,6 +1788,10 @@ int process_wide_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, void
         r = ensure_average(c, c->avg_window, pass);
         if (r) return r;
     }
+    if (c->tab.wh_on) {
+        r = ensure_whiten(c, pass, true);
+        if (r) return r;
+    }
     r = check_launch_pointers(c);
     if (r) return r;
     const float* in = static_cast<const float*>(d_in);
@@ -1724,12 +1803,16 @@ int process_wide_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, void
         const uint32_t nb = std::min(pass, batch - off);
         r = launch_cov_wide(c, in + (size_t)off * c->nsamples * 2, nb, c->dR);
         if (r) return r;
-        const double2* Rw = c->dR;             // what the EVD reads: the pass's plain covariances, or their averages (the history runs from pass to pass)
+        // what the EVD reads: the pass's plain covariances, or their averages (the history runs from pass to pass), or either whitened
         if (c->avg_window > 1) {
             r = launch_average(c, c->dR, nb, c->dRavg);
             if (r) return r;
-            Rw = c->dRavg;
         }
+        if (c->tab.wh_on) {
+            r = launch_whiten(c, c->avg_window > 1 ? c->dRavg : c->dR, nb, c->dRwh);
+            if (r) return r;
+        }
+        const double2* const Rw = cov_in_force(c);
         {
             ProfScope ps(c, BAZ_MUSIC_STAGE_EVD);
             const uint8_t* only = nullptr;
@@ -1883,6 +1966,7 @@ void free_table_set(TableSet& T)
     if (T.dTA) (void)dev_free(T.dTA);
     if (T.dA2) (void)dev_free(T.dA2);
     if (T.dRW) (void)dev_free(T.dRW);
+    if (T.dWh) (void)dev_free(T.dWh);
     T = TableSet();
 }
 
@@ -1916,7 +2000,19 @@ int build_tables_device(baz_music_ctx* c, TableSet& T)
     void *zRaw = nullptr, *zStats = nullptr;
     HIP_TRY(c, hipHostGetDevicePointer(&zRaw, c->hRaw, 0));
     HIP_TRY(c, hipHostGetDevicePointer(&zStats, c->hTabStats, 0));
-    if (c->calib_on)   // opt-in calibration: the same read over the link, times gamma (calib_kernels.hip.h); every image below follows from dRaw
+    T.wh_on = c->wh_on;
+    if (c->wh_on) {    // opt-in whitening: this set's W first (the stage reads it), then the same read over the link, times gamma where on, times W
+        if (!T.dWh && dev_malloc((void**)&T.dWh, (size_t)m * m * sizeof(double2)) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
+        void* zW = nullptr;
+        HIP_TRY(c, hipHostGetDevicePointer(&zW, c->hWh, 0));
+        hipLaunchKernelGGL(baztab::copy_words_kernel, dim3((m * m * 2 + 255) / 256), dim3(256), 0, s, static_cast<const unsigned long long*>(zW),
+                           reinterpret_cast<unsigned long long*>(T.dWh), (size_t)m * m * 2);
+        HIP_TRY(c, hipGetLastError());
+        const uint32_t bps = bazwhiten::WHITEN_THREADS / m;
+        hipLaunchKernelGGL(bazwhiten::table_whiten_kernel, dim3(std::min<uint32_t>(512, (res + bps - 1) / bps)), dim3(bazwhiten::WHITEN_THREADS),
+                           (size_t)m * (m + 1) / 2 * sizeof(double2), s, static_cast<const float2*>(zRaw), reinterpret_cast<float2*>(c->dRaw), res, m,
+                           T.dWh, c->calib_on ? 1 : 0, c->calib_gamma);
+    } else if (c->calib_on)   // opt-in calibration: the same read over the link, times gamma (calib_kernels.hip.h); every image below follows from dRaw
         hipLaunchKernelGGL(bazcalib::table_calib_kernel, dim3((unsigned)std::min<size_t>(512, (raw_bytes / 8 + 255) / 256)), dim3(bazcalib::CALIB_THREADS), 0, s,
                            static_cast<const float2*>(zRaw), reinterpret_cast<float2*>(c->dRaw), raw_bytes / 8, m, c->calib_gamma);
     else
@@ -2293,6 +2389,7 @@ int check_launch_pointers(baz_music_ctx* c)
     BAZ_REQUIRE(c, dR);
     BAZ_REQUIRE(c, dRedo);
     if (c->avg_window > 1) { BAZ_REQUIRE(c, dRavg); BAZ_REQUIRE(c, dAvgHist[0]); BAZ_REQUIRE(c, dAvgHist[1]); }
+    if (c->tab.wh_on) { BAZ_REQUIRE(c, dRwh); BAZ_REQUIRE_TAB(c, dWh); }
     if (c->wide) {
         BAZ_REQUIRE(c, dGw); BAZ_REQUIRE(c, dWS); BAZ_REQUIRE(c, dSw); BAZ_REQUIRE_TAB(c, dTA); BAZ_REQUIRE_TAB(c, dA2);
         if (c->wide_mfma) { BAZ_REQUIRE_TAB(c, dTB); BAZ_REQUIRE_TAB(c, dA2p); }
@@ -2348,12 +2445,12 @@ template <class Args>
 int capon_args(baz_music_ctx* c, uint32_t batch, float* d_ang, float* d_lvl, Args& A)
 {
     BAZ_REQUIRE(c, dRefAl); BAZ_REQUIRE_TAB(c, dRW);
-    if (c->avg_window > 1) BAZ_REQUIRE(c, dRavg); else BAZ_REQUIRE(c, dR);
+    A.R = cov_in_force(c);                           // what launch_frontend handed to the EVD
+    if (const int rn = refuse_null(c, A.R, "the covariance in force")) return rn;
     A.ang_in = c->dRefAl;
     A.lvl_in = c->dRefAl + (size_t)batch * c->n;
     A.ang_out = d_ang;
     A.lvl_out = d_lvl;
-    A.R = c->avg_window > 1 ? c->dRavg : c->dR;      // what launch_frontend handed to the EVD
     A.raw = c->tab.dRW;
     A.rel_floor = BAZ_MUSIC_POWER_PIVOT_FLOOR;
     A.batch = batch; A.n = c->n; A.res = c->res;
@@ -2488,11 +2585,11 @@ int launch_spectrum(baz_music_ctx* c, uint32_t batch, float* d_spec)
 {
     ProfScope ps(c, BAZ_MUSIC_STAGE_SCAN);
     BAZ_REQUIRE_TAB(c, dRW);
-    if (c->avg_window > 1) BAZ_REQUIRE(c, dRavg); else BAZ_REQUIRE(c, dR);
+    if (const int rn = refuse_null(c, cov_in_force(c), "the covariance in force")) return rn;
     if (const int rn = refuse_null(c, d_spec, "d_spec (estimator)")) return rn;
     if (c->res > 0x7fffff00u) return BAZ_MUSIC_E_UNSUPPORTED;                             // (bin + 256 in 32 bits)
     bazspectrum::SpectrumArgs A;
-    A.R = c->avg_window > 1 ? c->dRavg : c->dR;
+    A.R = cov_in_force(c);
     A.raw = c->tab.dRW;
     A.spec = d_spec;
     A.rel_floor = BAZ_MUSIC_POWER_PIVOT_FLOOR;
@@ -2548,6 +2645,10 @@ int process_device_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void
     if (r) return r;
     if (c->avg_window > 1) {
         r = ensure_average(c, c->avg_window, batch);
+        if (r) return r;
+    }
+    if (c->tab.wh_on) {
+        r = ensure_whiten(c, batch, true);
         if (r) return r;
     }
     r = check_launch_pointers(c);
@@ -3150,6 +3251,9 @@ void baz_music_destroy(baz_music_ctx* c)
         if (c->dRefAl) (void)dev_free(c->dRefAl);
         if (c->dRavg) (void)dev_free(c->dRavg);
         if (c->dCalIn) (void)dev_free(c->dCalIn);
+        if (c->dRwh) (void)dev_free(c->dRwh);
+        if (c->dWhT) (void)dev_free(c->dWhT);
+        if (c->hWh) (void)hipHostFree(c->hWh);
         if (c->dCalPart) (void)dev_free(c->dCalPart);
         if (c->dAvgHist[0]) (void)dev_free(c->dAvgHist[0]);
         if (c->dAvgHist[1]) (void)dev_free(c->dAvgHist[1]);
@@ -3241,6 +3345,10 @@ int baz_music_reserve(baz_music_ctx* c, uint32_t max_batch)
     if (c->avg_window > 1) {     // averaging: both history buffers and the averaged covariances of the largest launch
         const int ra = ensure_average(c, c->avg_window, c->wide ? std::min(max_batch, wide_pass_items(c)) : max_batch);
         if (ra) return ra;
+    }
+    if (c->tab.wh_on) {          // whitening: R' of the largest launch (and the pass between the two products at 17 .. 64 antennas)
+        const int rh = ensure_whiten(c, c->wide ? std::min(max_batch, wide_pass_items(c)) : max_batch, true);
+        if (rh) return rh;
     }
     if (c->wide) {
         const uint32_t pass = std::min(max_batch, wide_pass_items(c));
@@ -3547,8 +3655,8 @@ const char* baz_music_stage_name(baz_music_ctx* c, int stage)
     {
         std::lock_guard<std::mutex> lk(c->mtx);
         if (c->sm.inner) return "";   // smoothing on: no stage of this context runs (baz_music_set_smoothing)
-        // averaging on: the fused shape runs its two-kernel form (launch_frontend)
-        if (stage == BAZ_MUSIC_STAGE_COV && c->fused_covevd && (c->avg_window > 1 || c->estimator)) return "bazmusic::cov4_x4_kernel";
+        // averaging / whitening on: the fused shape runs its two-kernel form (launch_frontend)
+        if (stage == BAZ_MUSIC_STAGE_COV && c->fused_covevd && (c->avg_window > 1 || c->estimator || c->tab.wh_on)) return "bazmusic::cov4_x4_kernel";
     }
     if (stage == BAZ_MUSIC_STAGE_SCAN && !c->wide) {
         {
@@ -4126,6 +4234,7 @@ int baz_music_set_smoothing(baz_music_ctx* c, uint32_t subarray, int forward_bac
         if (c->beam_mode || c->estimator) return BAZ_MUSIC_E_UNSUPPORTED;   // (nor does the estimator choice reach the inner context)
     }
     if (c->calib_on) return BAZ_MUSIC_E_UNSUPPORTED;   // (raw data under Gamma != c I is not shift invariant; calib_on changes under tab_mtx)
+    if (c->wh_on) return BAZ_MUSIC_E_UNSUPPORTED;      // (nor is the whitened table W a; wh_on changes under tab_mtx)
     bazsmooth::Perm perm = {};
     if (smoothing_check(c->m, c->res, c->hRaw, subarray, fb, perm.p) != BAZ_MUSIC_OK) return BAZ_MUSIC_E_INVALID;
     const uint32_t L = c->m - subarray + 1;
@@ -4363,6 +4472,7 @@ int baz_music_set_estimator(baz_music_ctx* c, int kind)
     if (kind && c->wide) return BAZ_MUSIC_E_UNSUPPORTED;   // (spectrum_scan_kernel is specialised per m, like the other modes' kernels)
     // the emitter-count mode needs eigenvalues, refinement fits the MUSIC denominator, smoothing runs an inner MUSIC context
     if (kind && (c->order_mode || c->refine_mode || c->sm.inner)) return BAZ_MUSIC_E_UNSUPPORTED;
+    if (kind && c->wh_want) return BAZ_MUSIC_E_UNSUPPORTED;   // (whitening on: Capon is invariant under the transform, nothing is gained)
     c->estimator = kind;
     return BAZ_MUSIC_OK;
 }
@@ -4394,6 +4504,7 @@ int baz_music_set_beam_mode(baz_music_ctx* c, int mode, double loading)
     std::lock_guard<std::mutex> lk(c->mtx);
     if (mode && c->wide) return BAZ_MUSIC_E_UNSUPPORTED;   // (the kernels are specialised per m, like the pickers they follow)
     if (mode && c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;   // (smoothing: no m-antenna weight vector for the re-stacked items)
+    if (mode && c->wh_want) return BAZ_MUSIC_E_UNSUPPORTED;    // (whitening on: the weights would apply to unwhitened snapshots)
     c->beam_mode = mode;
     c->beam_loading = loading;
     return BAZ_MUSIC_OK;
@@ -4696,6 +4807,156 @@ int baz_music_calibrate_device(baz_music_ctx* c, const void* d_in, uint32_t batc
                                double* Rbar_ri)
 {
     return calibrate_any(c, d_in, false, batch, ref_ri, gamma_ri, quality, Rbar_ri);
+}
+
+// ---- opt-in noise pre-whitening: the host side (include/baz_music_hip.h; whiten_kernels.hip.h) -------------------------------------
+// W = L^-1 of the unpivoted Cholesky factor Rn = L L^H, in fp64 from the lower triangle and the real diagonal as stored.
+int baz_music_whitening_factor(uint32_t m, const double* Rn_ri, double* W_ri)
+{
+    if (m < 1 || m > BAZ_MUSIC_MAX_M || !Rn_ri || !W_ri) return BAZ_MUSIC_E_INVALID;
+    typedef std::complex<double> cd;
+    for (size_t i = 0; i < (size_t)2 * m * m; ++i)
+        if (!(Rn_ri[i] - Rn_ri[i] == 0.0)) return BAZ_MUSIC_E_INVALID;
+    double mean = 0.0;
+    for (uint32_t i = 0; i < m; ++i) mean = mean + Rn_ri[2 * ((size_t)i * m + i)];
+    mean = mean / (double)m;
+    const double floor_d = BAZ_MUSIC_POWER_PIVOT_FLOOR * mean;
+    std::vector<cd> L((size_t)m * m, cd(0.0, 0.0)), W((size_t)m * m, cd(0.0, 0.0));
+    for (uint32_t j = 0; j < m; ++j) {
+        double d = Rn_ri[2 * ((size_t)j * m + j)];
+        for (uint32_t k = 0; k < j; ++k) d = d - std::norm(L[(size_t)j * m + k]);
+        if (!(d - d == 0.0) || !(d > floor_d)) return BAZ_MUSIC_E_INVALID;       // (a pivot: not finite, or at / below the floor)
+        const double ljj = std::sqrt(d);
+        L[(size_t)j * m + j] = cd(ljj, 0.0);
+        for (uint32_t i = j + 1; i < m; ++i) {
+            cd s(Rn_ri[2 * ((size_t)i * m + j)], Rn_ri[2 * ((size_t)i * m + j) + 1]);
+            for (uint32_t k = 0; k < j; ++k) s = s - L[(size_t)i * m + k] * std::conj(L[(size_t)j * m + k]);
+            L[(size_t)i * m + j] = s / ljj;
+        }
+    }
+    // W L = I by substitution, row by row of W (w_i L = e_i, from the diagonal leftwards): the form whose rounding errors are a
+    // small relative perturbation of L per row, so that |W L - I| <= gamma |W| |L| componentwise
+    for (uint32_t i = 0; i < m; ++i) {
+        W[(size_t)i * m + i] = cd(1.0 / L[(size_t)i * m + i].real(), 0.0);
+        for (uint32_t j = i; j-- > 0;) {
+            cd s(0.0, 0.0);
+            for (uint32_t k = j + 1; k <= i; ++k) s = s + W[(size_t)i * m + k] * L[(size_t)k * m + j];
+            W[(size_t)i * m + j] = -s / L[(size_t)j * m + j].real();
+        }
+    }
+    for (size_t i = 0; i < (size_t)m * m; ++i) {
+        if (!(W[i].real() - W[i].real() == 0.0) || !(W[i].imag() - W[i].imag() == 0.0)) return BAZ_MUSIC_E_INVALID;
+        W_ri[2 * i] = W[i].real();
+        W_ri[2 * i + 1] = W[i].imag();
+    }
+    return BAZ_MUSIC_OK;
+}
+
+// The definition of include/baz_music_hip.h on the host: table_whiten_kernel's own routine, entry by entry.
+int baz_music_whiten_table(uint32_t m, uint32_t resolution, const float* table_ri, const double* W_ri, float* out_ri)
+{
+    if (m < 1 || m > BAZ_MUSIC_MAX_M || resolution == 0 || !table_ri || !W_ri || !out_ri) return BAZ_MUSIC_E_INVALID;
+    const double2* const W = reinterpret_cast<const double2*>(W_ri);
+    std::vector<float2> row(m);
+    for (size_t b = 0; b < resolution; ++b) {
+        for (uint32_t k = 0; k < m; ++k) row[k] = make_float2(table_ri[2 * (b * m + k)], table_ri[2 * (b * m + k) + 1]);   // (out may be table)
+        for (uint32_t r = 0; r < m; ++r)
+            bazwhiten::whiten_entry(W + (size_t)r * m, row.data(), r, &out_ri[2 * (b * m + r)], &out_ri[2 * (b * m + r) + 1]);
+    }
+    return BAZ_MUSIC_OK;
+}
+
+int baz_music_set_noise_covariance(baz_music_ctx* c, const double* Rn_ri)
+{
+    if (!c) return BAZ_MUSIC_E_INVALID;
+    const size_t mm = (size_t)c->m * c->m;
+    std::vector<double> W;
+    if (Rn_ri) {
+        W.resize(2 * mm);
+        if (const int rf = baz_music_whitening_factor(c->m, Rn_ri, W.data())) return rf;
+    }
+    std::lock_guard<std::mutex> tl(c->tab_mtx);   // a retune of the table c->hRaw holds; against set_table, set_calibration and set_smoothing
+    DeviceGuard guard(c->device);
+    if (Rn_ri && c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;   // (the whitened table is not shift invariant)
+    if (!Rn_ri && !c->wh_on) return BAZ_MUSIC_OK;               // off and staying off: the images in force are the ones to keep
+    bool old_want = false;
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);
+        // (the beam mode's weights would apply to unwhitened snapshots; Capon is invariant under the transform)
+        if (Rn_ri && (c->beam_mode || c->estimator)) return BAZ_MUSIC_E_UNSUPPORTED;
+        old_want = c->wh_want;
+        if (Rn_ri) c->wh_want = true;             // (from here set_beam_mode / set_estimator refuse)
+    }
+    if (Rn_ri && !c->hWh && hipHostMalloc((void**)&c->hWh, mm * sizeof(double2), hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        std::lock_guard<std::mutex> lk(c->mtx);
+        c->wh_want = old_want;
+        return BAZ_MUSIC_E_NOMEM;
+    }
+    const bool old_on = c->wh_on;
+    std::vector<double> old_W;
+    if (old_on) old_W.assign(reinterpret_cast<const double*>(c->hWh), reinterpret_cast<const double*>(c->hWh) + 2 * mm);
+    c->wh_on = Rn_ri != nullptr;
+    if (Rn_ri) std::memcpy(c->hWh, W.data(), 2 * mm * sizeof(double));     // (no builder runs: they hold tab_mtx and wait for their stream)
+    const int r = retune(c, nullptr, false);
+    std::lock_guard<std::mutex> lk(c->mtx);
+    if (r != BAZ_MUSIC_OK) {                      // the old pair (images, W) stays in force: retune exchanges only after a complete build
+        c->wh_on = old_on;
+        if (old_on) std::memcpy(c->hWh, old_W.data(), 2 * mm * sizeof(double));
+        c->wh_want = old_want;
+        return r;
+    }
+    if (Rn_ri) c->wh_Rn.assign(Rn_ri, Rn_ri + 2 * mm); else c->wh_Rn.clear();
+    c->wh_want = c->wh_on;
+    return BAZ_MUSIC_OK;
+}
+
+int baz_music_get_noise_covariance(const baz_music_ctx* c, double* Rn_ri, int* on)
+{
+    if (!c || !on) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> tl(const_cast<baz_music_ctx*>(c)->tab_mtx);
+    *on = c->wh_on ? 1 : 0;
+    if (Rn_ri)
+        for (uint32_t i = 0; i < c->m; ++i)
+            for (uint32_t j = 0; j < c->m; ++j) {
+                const size_t e = 2 * ((size_t)i * c->m + j);
+                Rn_ri[e] = c->wh_on ? c->wh_Rn[e] : (i == j ? 1.0 : 0.0);
+                Rn_ri[e + 1] = c->wh_on ? c->wh_Rn[e + 1] : 0.0;
+            }
+    return BAZ_MUSIC_OK;
+}
+
+int baz_music_debug_whiten(baz_music_ctx* c, const void* d_R_in, uint32_t batch, void* d_R_out)
+{
+    if (!c || !d_R_in || !d_R_out || d_R_in == d_R_out || batch == 0) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    DeviceGuard guard(c->device);
+    if (c->sm.inner || !c->tab.wh_on) return BAZ_MUSIC_E_UNSUPPORTED;
+    (void)hipGetLastError();
+    const int r = ensure_whiten(c, batch, false);
+    return r ? r : launch_whiten(c, static_cast<const double2*>(d_R_in), batch, static_cast<double2*>(d_R_out));
+}
+
+namespace {
+int mean_covariance_any(baz_music_ctx* c, const void* in, bool in_on_host, uint32_t batch, double* Rbar_ri)
+{
+    if (!c || !in || batch == 0 || !Rbar_ri) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    DeviceGuard guard(c->device);
+    if (c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;
+    (void)hipGetLastError();
+    return calib_mean_locked(c, in, in_on_host, batch, Rbar_ri);
+}
+}  // namespace
+
+int baz_music_mean_covariance(baz_music_ctx* c, const float* in_ri, uint32_t batch, double* Rbar_ri)
+{
+    return mean_covariance_any(c, in_ri, true, batch, Rbar_ri);
+}
+
+int baz_music_mean_covariance_device(baz_music_ctx* c, const void* d_in, uint32_t batch, double* Rbar_ri)
+{
+    return mean_covariance_any(c, d_in, false, batch, Rbar_ri);
 }
 
 int baz_music_get_smoothing(const baz_music_ctx* c, uint32_t* subarray, int* forward_backward)

@@ -89,7 +89,8 @@ baz_music_doa::baz_music_doa(unsigned int m, unsigned int n, unsigned int nsampl
                                              resolution * sizeof(float))),
       d_m(m), d_n(n), d_nsamples(nsamples), d_resolution(resolution),
       d_array_response(array_response), d_ctx(NULL), d_pin_buffers(false),
-      d_cal_want(0), d_cal_min_quality(0.0), d_cal_quality(-1.0)
+      d_cal_want(0), d_cal_min_quality(0.0), d_cal_quality(-1.0),
+      d_wh_want(0), d_wh_status(0)
 {
     const std::vector<float> flat = flatten_response(array_response, m, resolution);
     const int rc = baz_music_create(&d_ctx, m, n, nsamples, resolution, flat.data(), next_device());
@@ -290,6 +291,42 @@ double baz_music_doa::last_calibration_quality()
     return d_cal_quality;
 }
 
+void baz_music_doa::set_noise_covariance(const std::vector<std::complex<double> >& rn)
+{
+    if (!rn.empty() && rn.size() != (size_t)d_m * d_m)
+        throw std::invalid_argument("music_doa: set_noise_covariance: rn must hold m*m values, row-major (or none: off)");
+    const int rc = baz_music_set_noise_covariance(d_ctx, rn.empty() ? NULL : reinterpret_cast<const double*>(rn.data()));
+    if (rc == BAZ_MUSIC_E_INVALID)
+        throw std::invalid_argument("music_doa: set_noise_covariance: rn must be finite, Hermitian positive definite and well above rank deficiency");
+    if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: set_noise_covariance: ") + baz_music_strerror(rc));
+}
+
+std::vector<std::complex<double> > baz_music_doa::noise_covariance()
+{
+    std::vector<std::complex<double> > rn((size_t)d_m * d_m);
+    int on = 0;
+    const int rc = baz_music_get_noise_covariance(d_ctx, reinterpret_cast<double*>(rn.data()), &on);
+    if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: noise_covariance: ") + baz_music_strerror(rc));
+    if (!on) rn.clear();
+    return rn;
+}
+
+void baz_music_doa::whiten_next(unsigned int items)
+{
+    if (items == 0) throw std::invalid_argument("music_doa: whiten_next: items > 0 is required");
+    gr::thread::scoped_lock guard(d_wh_mutex);
+    d_wh_items.clear();
+    d_wh_items.reserve((size_t)items * d_nsamples);
+    d_wh_status = -1;
+    d_wh_want = items;
+}
+
+int baz_music_doa::last_whitening_status()
+{
+    gr::thread::scoped_lock guard(d_wh_mutex);
+    return d_wh_status;
+}
+
 std::vector<unsigned char> baz_music_doa::last_orders(unsigned int count)
 {
     std::vector<unsigned char> out(count);
@@ -360,6 +397,27 @@ int baz_music_doa::work(int noutput_items, gr_vector_const_void_star& input_item
             d_cal_quality = quality;
             d_cal_want = 0;
             std::vector<gr_complex>().swap(d_cal_items);
+        }
+    }
+
+    /* whiten_next: this call's items join the noise-only capture; once it is complete, their mean covariance becomes the noise
+     * covariance in force (for the calls after this one).  A failure disarms and is reported by last_whitening_status(); the
+     * setting in force stays and the stream goes on. */
+    gr::thread::scoped_lock wguard(d_wh_mutex);
+    if (d_wh_want) {
+        const size_t have = d_wh_items.size() / d_nsamples;
+        const size_t take = std::min<size_t>((size_t)noutput_items, d_wh_want - have);
+        const gr_complex* items = reinterpret_cast<const gr_complex*>(in);
+        d_wh_items.insert(d_wh_items.end(), items, items + take * d_nsamples);
+        if (have + take == d_wh_want) {
+            std::vector<double> rbar(2 * (size_t)d_m * d_m);
+            int rc2 = baz_music_mean_covariance(d_ctx, reinterpret_cast<const float*>(d_wh_items.data()), d_wh_want, rbar.data());
+            if (rc2 == BAZ_MUSIC_OK) rc2 = baz_music_set_noise_covariance(d_ctx, rbar.data());
+            if (rc2 != BAZ_MUSIC_OK)
+                fprintf(stderr, "[%s<%li>] MUSIC DOA: whiten_next: %s\n", name().c_str(), unique_id(), baz_music_strerror(rc2));
+            d_wh_status = rc2;
+            d_wh_want = 0;
+            std::vector<gr_complex>().swap(d_wh_items);
         }
     }
     return noutput_items;

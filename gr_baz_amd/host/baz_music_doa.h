@@ -16,6 +16,7 @@
 #include <gnuradio/sync_block.h>
 #include <gnuradio/thread/thread.h>
 
+#include <complex>
 #include <utility>
 #include <vector>
 
@@ -107,6 +108,19 @@ public:
     std::vector<gr_complex> calibration();
     void calibrate_next(unsigned int items, const std::vector<gr_complex>& ref, double min_quality);
     double last_calibration_quality();
+    /* Extension, off by default (not in the reference): noise pre-whitening -- with the noise covariance rn = L L^H (m*m values,
+     * row-major; its lower triangle is read) the EVD decomposes W R W^H and the table in force becomes W a, W = L^-1, across
+     * set_array_response and set_calibration too (baz_music_set_noise_covariance, include/baz_music_hip.h).  An empty vector is off.
+     * noise_covariance(): the matrix in force (empty while off).  whiten_next arms a measurement: the block copies the next `items`
+     * items that pass through work() (a noise-only capture; across as many calls as it takes; their outputs are untouched), calls
+     * baz_music_mean_covariance once and hands the result to the setter.  last_whitening_status(): -1 while armed, 0 once applied
+     * (and before the first measurement), else the error code of the step that failed (the setting in force stays).  Not available
+     * while smoothing, the beam mode or an estimator other than MUSIC is on.  Throws std::invalid_argument for a vector that does
+     * not hold m*m finite values of a positive definite matrix, or items == 0. */
+    void set_noise_covariance(const std::vector<std::complex<double> >& rn);
+    std::vector<std::complex<double> > noise_covariance();
+    void whiten_next(unsigned int items);
+    int last_whitening_status();
 
     /* Page-locking of the scheduler's stream buffers (baz_music_set_host_pinning, include/baz_music_hip.h): work()
      * registers the ranges it is handed the first time it sees them, stop() and the destructor release them.  On by
@@ -142,6 +156,11 @@ private:
     std::vector<gr_complex> d_cal_ref;
     double d_cal_min_quality;
     double d_cal_quality;
+    /* whiten_next: guarded by d_wh_mutex (its own, as d_cal_mutex is) */
+    gr::thread::mutex d_wh_mutex;
+    unsigned int d_wh_want;             /* items to capture; 0: not armed */
+    std::vector<gr_complex> d_wh_items;  /* the items captured so far */
+    int d_wh_status;
 };
 
 /* Placement rule of independent block instances (BASELINE config 4: 64 streams in one flowgraph; SURVEY.md 8e,

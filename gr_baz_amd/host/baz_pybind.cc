@@ -267,6 +267,11 @@ PYBIND11_MODULE(_baz_music, mod)
                  h.blk->calibrate_next(items, ref, min_quality);
              }, py::arg("items"), py::arg("ref"), py::arg("min_quality") = 0.9)
         .def("last_calibration_quality", [](music_doa_handle& h) { return h.blk->last_calibration_quality(); })
+        .def("set_noise_covariance", [](music_doa_handle& h, const std::vector<std::complex<double> >& rn) { h.blk->set_noise_covariance(rn); },
+             py::arg("rn"))
+        .def("noise_covariance", [](music_doa_handle& h) { return h.blk->noise_covariance(); })
+        .def("whiten_next", [](music_doa_handle& h, unsigned int items) { h.blk->whiten_next(items); }, py::arg("items"))
+        .def("last_whitening_status", [](music_doa_handle& h) { return h.blk->last_whitening_status(); })
         .def("last_orders",
              [](music_doa_handle& h, unsigned int count) {
                  const std::vector<unsigned char> v = h.blk->last_orders(count);

@@ -615,6 +615,61 @@ BAZ_MUSIC_API int baz_music_calibration_estimate(uint32_t m, const double* Rbar_
 BAZ_MUSIC_API int baz_music_set_estimator(baz_music_ctx* ctx, int kind);
 BAZ_MUSIC_API int baz_music_get_estimator(const baz_music_ctx* ctx, int* kind);
 BAZ_MUSIC_API int baz_music_spectrum_estimate(int kind, uint32_t m, const double* R_ri, const float* a_ri, uint32_t count, double* out);
+/* OPT-IN extension, NOT reference behaviour: noise PRE-WHITENING with a known or measured noise covariance.  MUSIC and the
+ * MDL / AIC emitter count assume a noise covariance sigma^2 I; channels of a real receiver differ in noise figure and gain setting and
+ * neighbouring front ends share noise.  The calibration above corrects the signal model, this mode the noise model: with Rn = L L^H and
+ * W = L^-1 the whitened snapshots W x have noise covariance I and steering vectors W a, so every stage runs in the whitened space.
+ * set_noise_covariance: Rn_ri = m*m complex128, row-major, re / im interleaved; NULL = off (the default, the reference).  Rn is read as R
+ * is read elsewhere: the lower triangle as stored, the imaginary part of the diagonal ignored.
+ *   FACTOR      on the host in fp64: the unpivoted Cholesky factor Rn = L L^H (column by column, sums in index order), then W = L^-1 by
+ *               substitution, row by row of W L = I.  W is lower triangular with a real positive diagonal (imaginary part exactly 0, the
+ *               upper triangle exactly 0).  No normalisation is applied: R' is in units of the noise, and the caller may scale Rn.
+ *               whitening_factor is the setter's own routine: Rn_ri -> W_ri (m*m complex128 each), needs no device.
+ *   ERRORS      BAZ_MUSIC_E_INVALID for a non-finite entry of Rn_ri (any of the 2 m^2 numbers) and for a pivot d_j = Re Rn_jj -
+ *               sum_{k<j} |L_jk|^2 that is not finite or is <= BAZ_MUSIC_POWER_PIVOT_FLOOR times the mean of the real diagonal (a
+ *               rank-deficient or indefinite Rn).  After any error the previous setting stays in force.
+ *   TABLE       the table in force is a'_r(b) = fl32(sum_{k <= r} W_rk a~_k(b)), a~ the entry of the table last given to create /
+ *               set_table after the calibration where that is on (gamma first, then W), widened exactly.  The sum is fp64 from
+ *               (+0, +0) with k ascending; each term is four fused multiply-adds, re = fma(W.re, a.re, re), re = fma(-W.im, a.im, re),
+ *               im = fma(W.re, a.im, im), im = fma(W.im, a.re, im); one round-to-nearest conversion to fp32 per component.
+ *               whiten_table is the host form, the kernel's own routine, bit for bit: table_ri = resolution x m complex64, W_ri = m*m
+ *               complex128 (the upper triangle is not read) -> out_ri; needs no device; W = I returns the bytes of the table (a component
+ *               -0 may come back as +0).  The mode persists across baz_music_set_table and baz_music_set_calibration; every numeric
+ *               statement of this header then holds for the table a' and the covariance R'.
+ *   COVARIANCE  the EVD decomposes R' = W R W^H per item in fp64, R = the plain covariance, or Rbar_t where averaging is on (average
+ *               first, whiten second; the averaging history keeps plain covariances, so switching this mode does not touch it).  R is read
+ *               as the Hermitian matrix its lower triangle describes; T_rj = sum_{k<=r} W_rk R_kj, then for r >= j
+ *               R'_rj = sum_{k<=r} W_rk conj(T_jk), both from (+0, +0) with k ascending by the four fused multiply-adds above.  The full
+ *               m x m matrix is written: upper triangle = conj(lower), the diagonal's imaginary part exactly +0.  An item touches no other
+ *               item's data.  The emitter count reads the eigenvalues of R', refinement and the power mode read R' and a', the scans read
+ *               the images of the whitened table.  baz_music_debug_cov keeps returning the plain R; debug_whiten runs the stage alone
+ *               (d_R_in -> d_R_out, `batch` matrices of m*m complex128 in device memory, not overlapping) with the W in force and is
+ *               BAZ_MUSIC_E_UNSUPPORTED while the mode is off.  tests/whiten_ref.py restates all of this in numpy.
+ *   WHAT RUNS   table_whiten_kernel (gr_baz_amd/csrc/whiten_kernels.hip.h) takes the place of copy_words_kernel / table_calib_kernel as
+ *               the first launch of a retune; every other image follows unchanged.  Between the covariance (or the averaging stage)
+ *               and the EVD runs whiten_kernel<M> (2 .. 16 antennas) or whiten_wide_kernel twice (17 .. 64); their time counts under
+ *               BAZ_MUSIC_STAGE_COV.  At 4 antennas with K % 256 == 0 the two-kernel frontend runs, as under averaging.  W travels with
+ *               the table set: set_noise_covariance is a retune of the table in force into the shadow set, exchanged under the batch
+ *               mutex, so a batch sees the old (table, W) or the new pair, never a mixture.  Off -- a context never set, one set to NULL,
+ *               one switched on and off again -- launches exactly what it launched before the mode existed and every output is the
+ *               reference's bit for bit.
+ *   SCOPE       every antenna count 2 .. BAZ_MUSIC_MAX_M.  Composes with peak mode, the emitter-count mode, refinement, the power mode (by
+ *               its own definition on R' and a'), averaging, calibration, retune and the host-fed baz_music_process.  It does NOT compose
+ *               with smoothing (the whitened table is not shift invariant), the beam mode (its weights would apply to unwhitened
+ *               snapshots) or estimator kinds 1 / 2 (Capon is invariant under the transform: nothing is gained): whichever of the two is
+ *               set second returns BAZ_MUSIC_E_UNSUPPORTED and the setting already in force stays.
+ * get_noise_covariance: *on = 0 / 1; Rn_ri (may be NULL) receives the Rn in force as given, the identity while off.
+ * mean_covariance / _device: Rbar of `batch` items from host / device memory into Rbar_ri (m*m complex128, host memory): exactly the Rbar of
+ * baz_music_calibrate's definition (the same routine, the same bits), without a pilot -- a noise-only capture becomes an Rn.  They block,
+ * consume no averaging history and change nothing; BAZ_MUSIC_E_INVALID for batch == 0 or a NULL pointer, BAZ_MUSIC_E_UNSUPPORTED while
+ * smoothing is on. */
+BAZ_MUSIC_API int baz_music_set_noise_covariance(baz_music_ctx* ctx, const double* Rn_ri);
+BAZ_MUSIC_API int baz_music_get_noise_covariance(const baz_music_ctx* ctx, double* Rn_ri, int* on);
+BAZ_MUSIC_API int baz_music_whitening_factor(uint32_t m, const double* Rn_ri, double* W_ri);
+BAZ_MUSIC_API int baz_music_whiten_table(uint32_t m, uint32_t resolution, const float* table_ri, const double* W_ri, float* out_ri);
+BAZ_MUSIC_API int baz_music_debug_whiten(baz_music_ctx* ctx, const void* d_R_in, uint32_t batch, void* d_R_out);
+BAZ_MUSIC_API int baz_music_mean_covariance(baz_music_ctx* ctx, const float* in_ri, uint32_t batch, double* Rbar_ri);
+BAZ_MUSIC_API int baz_music_mean_covariance_device(baz_music_ctx* ctx, const void* d_in, uint32_t batch, double* Rbar_ri);
 /* Statistic: how many (item, bin) values of the LAST process call were recomputed in the reference's literal form
  * ||G^H a||^2 because the projector form a^H Q a put them at or below ~m 1e-8 max||a||^2 (near-nulls of the noise
  * subspace, SNR >~ 55 dB); blocks until that call is done (a host-fed call cut into chunks reports their sum).
