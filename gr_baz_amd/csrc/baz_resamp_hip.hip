@@ -76,6 +76,33 @@ u128 to_fixed(long double v, bool* exact)
 i128 to_fixed_signed(long double v, bool* exact) { return v < 0 ? -(i128)to_fixed(-v, exact) : (i128)to_fixed(v, exact); }
 long double from_fixed(u128 f) { return (long double)(uint64_t)(f >> 64) + (long double)(uint64_t)f / TWO64; }
 
+// The reference forms s = d_mu + d_mu_inc (+ d_mu_adj) in x87 arithmetic: a sum whose integer part has k bits keeps 64 - k
+// fraction bits, the closed form keeps all 64.  True when no sum of one call can round: the phase in force, the increment and
+// the adjustment are all multiples of 2^(k-64), k the integer bit count of the largest sum the call can form -- first + inc,
+// that plus adj, or (1 - 2^-64) + inc on a later step (mu < 1 from the second output on).  Every later phase of the call is
+// then a multiple of 2^(k-64) below 2^k as well.  Conservative: judged by the lowest set bits, not by the sums that occur.
+int low_bit(u128 v)
+{
+    if (v == 0) return 128;
+    const uint64_t lo = (uint64_t)v;
+    return lo ? __builtin_ctzll(lo) : 64 + __builtin_ctzll((uint64_t)(v >> 64));
+}
+bool sums_stay_exact(u128 first, u128 inc, i128 adj)
+{
+    u128 top = first + inc;
+    if (adj > 0) top += (u128)adj;
+    const u128 later = (((u128)1 << 64) - 1) + inc;
+    if (later > top) top = later;
+    const uint64_t hi = (uint64_t)(top >> 64);
+    const int k = hi ? 64 - __builtin_clzll(hi) : 0;
+    int low = low_bit(first);
+    if (low_bit(inc) < low) low = low_bit(inc);
+    if (low_bit((u128)(adj < 0 ? -adj : adj)) < low) low = low_bit((u128)(adj < 0 ? -adj : adj));
+    return low >= k;
+}
+// A ratio that is not a double value (a quotient rounded to 64 bits, the ppb pair) is off the grid of its own sums but for luck
+bool is_double(long double r) { return (long double)(double)r == r; }
+
 bool ratio_ok(long double r) { return r >= 1.0L / 2048.0L && r <= 2147483648.0L; }
 
 long double sincl_(long double x)
@@ -156,6 +183,7 @@ int64_t process_device_locked(baz_resamp_ctx* c, const void* d_in, uint64_t in_s
     }
     const u128 pend = step1 + (u128)(n - 1) * inc;               // phase after the n-th step
     if ((uint64_t)(pend >> 64) > 0xFFFFFFFFull * 2048ull) return BAZ_RESAMP_E_INVALID;
+    if (!sums_stay_exact(first, inc, adj)) c->exact = false;    // an x87 sum of this call may have rounded (see above)
     PhaseParams p;
     p.first_lo = (uint64_t)first; p.first_hi = (uint64_t)(first >> 64);
     p.base_lo = (uint64_t)step1;  p.base_hi = (uint64_t)(step1 >> 64);
@@ -266,6 +294,7 @@ int baz_resamp_create(baz_resamp_ctx** out, uint32_t nstreams, double phase_shif
     c->device = dev;
     c->mu = to_fixed((long double)phase_shift, &c->exact);
     c->mu_inc = to_fixed(ratio, &c->exact);
+    if (!is_double(ratio) || !sums_stay_exact(c->mu, c->mu_inc, 0)) c->exact = false;
     build_taps(c->taps);
     DeviceGuard guard(dev);
     if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess ||
@@ -391,6 +420,7 @@ static int set_ratio_ld(baz_resamp_ctx* c, long double r)
     if (!ratio_ok(r)) return BAZ_RESAMP_E_UNSUPPORTED;
     std::lock_guard<std::mutex> lk(c->mtx);
     c->mu_inc_update = to_fixed(r, &c->exact);
+    if (!is_double(r)) c->exact = false;
     c->update = true;
     c->stopped_at_bad = false;
     return BAZ_RESAMP_OK;

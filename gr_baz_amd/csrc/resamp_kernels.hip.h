@@ -5,8 +5,12 @@
 //     out[oo++] = d_resamp->interpolate(&in[ii], d_mu);            (.cc:172; gnuradio-filter MMSE interpolator)
 //     s = d_mu + d_mu_inc (+ d_mu_adj once); f = floor(s); ii += (int)f; d_mu = s - f;        (.cc:183-193)
 // The phase recurrence is a sum, so output o is evaluated independently: P_o = base + o * inc in 64.64-bit fixed
-// point (ii_o = integer part, mu_o = fraction), exactly the reference's x87 sequence whenever that one is exact
-// (include/baz_resamp_hip.h).  One thread per (output, stream); a block's input window is contiguous
+// point (ii_o = integer part, mu_o = fraction).  That is the reference's x87 sequence only while none of its sums rounds:
+// a sum with k integer bits keeps 64 - k fraction bits there, all 64 here -- double parameters included (phase 0.001 with
+// ratio 17.3 differs by 2^-60 in mu from the second output on).  The bound on the distance, and the host-side flag that
+// says when the two are the same walk, are in include/baz_resamp_hip.h; the x87 roundings are NOT reproduced here (the
+// two-input walk below does reproduce them).  A phase of exactly 1.0 reads row 0 at ii + 1, the reference row 128 at ii:
+// equal for tables whose row 128 is row 0 delayed by one sample.  One thread per (output, stream); a block's input window is contiguous
 // (256 outputs span <= 256*ratio + 8 samples) and is read through L1/L2 -- 8 overlapping float2 loads per output,
 // HBM sees every input once.  The 129 x 8 tap table (4 KiB) sits in LDS.
 #pragma once

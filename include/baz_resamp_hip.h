@@ -19,10 +19,25 @@
  * and baz_resamp_set_taps() installs the host's own table, which the host block does wherever it is compiled against
  * a real gnuradio-filter: bit-exact with whatever gnuradio-filter the host has.  The reference's x87 `long double` phase recurrence mu <- frac(mu + mu_inc),
  * ii <- ii + floor(mu + mu_inc) is evaluated in closed form, P_o = mu_0 + o * mu_inc in 64.64-bit fixed point
- * (128-bit integers), one output per thread.  This is EXACTLY the reference's sequence whenever its sums are exact
- * in the 64-bit x87 mantissa -- always for ratios and phases given as `double` (make()'s signature) with
- * ratio >= 2^-11; for num/denom ratios (64-bit quotient) the two differ by < o * 2^-64 in mu, which moves imu only
- * when mu*128 sits within that distance of a rounding boundary.
+ * (128-bit integers, every quantity truncated to 2^-64 on conversion), one output per thread.  This is the reference's
+ * sequence whenever every x87 sum of the reference is exact, and ONLY then: the x87 significand has 64 bits, so a sum
+ * s = mu + mu_inc (+ adjustment) whose integer part has k bits keeps 64 - k fraction bits and rounds the rest away
+ * (to nearest, ties to even), while the closed form keeps all 64.  `double` parameters do NOT guarantee exact sums: a
+ * double phase in [2^-e-1, 2^-e) carries bits down to 2^-(53+e) -- phase 0.001 (last bit 2^-60) with ratio 17.3 (k = 5,
+ * 59 bits kept) is off by 2^-60 from the second output on; phase 81/256 + 2^-26 + 2^-54 with ratio 1024 reads the
+ * neighbouring tap row on every output but the first.  The distance in total phase T = (samples consumed) + mu after o
+ * steps is bounded by
+ *     |T_ref - T_lib| <= d_mu + sum over the o steps of [ d_inc + 2^(k-65)  (+ d_adj + 2^(k'-65) on the adjusted step) ]
+ * with d_mu, d_inc < 2^-64 and d_adj what the 64.64 conversion of each quantity dropped (0 for doubles >= 2^-11),
+ * k = bit length of floor(mu_inc) + 1 and k' = bit length of floor(mu_inc) + 2 + floor(|adjustment|).  With a constant
+ * double ratio the grid of mu only coarsens, at most two sums of the whole stream round, and the distance stays below
+ * d_mu + 2^(k-64) for ever -- a constant offset in mu; with a quotient ratio (num/denom, the ppb pair: 64 significant
+ * bits of their own) every sum may round and the distance grows like o * 2^(k-65).  Either moves imu only where mu*128
+ * sits within that distance of a rounding boundary.  baz_resamp_phase_exact() tells the two situations apart.
+ * (tests/resamp_phase_ref.py derives the bound and models both walks in integers.)
+ * A phase of exactly 1.0 (the constructor allows it) reads tap row 0 at ii + 1 here, row 128 at ii in the reference:
+ * the same filter for every table whose row 128 is row 0 delayed by one sample (the MMSE table: both are pure
+ * delays), not for an arbitrary table installed with baz_resamp_set_taps().
  *
  * The two-input branch (.cc:205-217, per-sample ratio input) is served by baz_resamp_process2*: ii_{o+1} depends on
  * the ratio sample read at ii_o, a data-dependent serial chain that one lane walks (see resamp_walk_kernel) -- offered
@@ -98,7 +113,13 @@ BAZ_RESAMP_API int baz_resamp_set_ratio_ppb(baz_resamp_ctx* ctx, long whole, dou
 BAZ_RESAMP_API int baz_resamp_adjust(baz_resamp_ctx* ctx, double d);                                    /* msg double, .cc:127-134 */
 BAZ_RESAMP_API double baz_resamp_mu(const baz_resamp_ctx* ctx);                                         /* .cc:220-224 */
 BAZ_RESAMP_API double baz_resamp_ratio(const baz_resamp_ctx* ctx);                                      /* .cc:226-230 */
-/* 1 when every phase quantity so far was exactly representable in 64.64 fixed point (see the header comment). */
+/* 1 while the walk so far is provably the reference's, bit for bit (see the header comment): every phase quantity was
+ * exactly representable in 64.64 fixed point, every ratio was a `double` value, and in every process call so far (and
+ * for the constructor's pair) the phase in force, the ratio and the adjustment were all multiples of 2^(k-64), k the
+ * integer bit count of the largest sum the call can form -- so no x87 sum of the reference could have rounded.
+ * Conservative: it may be 0 where no sum happened to round (always for quotient ratios), never 1 where one did.  A
+ * setter's conversion shows at once, its effect on the sums with the process call that applies it.  Once 0 it stays 0.
+ * The one-input outputs are those of the documented 64.64 walk whatever this returns. */
 BAZ_RESAMP_API int baz_resamp_phase_exact(const baz_resamp_ctx* ctx);
 /* The 129 x 8 tap table in use (float, host copy). */
 BAZ_RESAMP_API const float* baz_resamp_taps(const baz_resamp_ctx* ctx);

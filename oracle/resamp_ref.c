@@ -116,6 +116,11 @@ void resamp_ref_set_ratio_rational(resamp_ref_t* s, unsigned long long num, unsi
 {
     if (denom != 0) { s->mu_inc_update = (long double)num / (long double)denom; s->update = 1; }
 }
+void resamp_ref_set_ratio_ppb(resamp_ref_t* s, long whole, double frac)                                                /* msg pair, .cc:116-124 */
+{
+    s->mu_inc_update = ((long double)whole + (long double)frac) / (long double)1e9;
+    s->update = 1;
+}
 void resamp_ref_adjust(resamp_ref_t* s, double d) { s->mu_adj = (long double)d * s->mu_inc; s->update_mu_adj = 1; }   /* .cc:130-134 */
 double resamp_ref_mu(const resamp_ref_t* s) { return (double)s->mu; }
 double resamp_ref_ratio(const resamp_ref_t* s) { return (double)s->mu_inc; }

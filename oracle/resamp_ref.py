@@ -40,6 +40,7 @@ def lib():
         for nm in ("set_mu", "set_ratio", "adjust"):
             getattr(L, "resamp_ref_" + nm).argtypes = [ctypes.c_void_p, ctypes.c_double]
         L.resamp_ref_set_ratio_rational.argtypes = [ctypes.c_void_p, ctypes.c_ulonglong, ctypes.c_ulonglong]
+        L.resamp_ref_set_ratio_ppb.argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_double]
         L.resamp_ref_mu.restype = ctypes.c_double
         L.resamp_ref_mu.argtypes = [ctypes.c_void_p]
         L.resamp_ref_ratio.restype = ctypes.c_double
@@ -130,6 +131,7 @@ class Resampler(_Base):
     def set_mu(self, mu): lib().resamp_ref_set_mu(self._s, mu)
     def set_resamp_ratio(self, r): lib().resamp_ref_set_ratio(self._s, r)
     def set_resamp_ratio_rational(self, n, d): lib().resamp_ref_set_ratio_rational(self._s, n, d)
+    def set_resamp_ratio_ppb(self, whole, frac): lib().resamp_ref_set_ratio_ppb(self._s, whole, frac)
     def adjust(self, d): lib().resamp_ref_adjust(self._s, d)
     def mu(self): return lib().resamp_ref_mu(self._s)
     def resamp_ratio(self): return lib().resamp_ref_ratio(self._s)
@@ -162,5 +164,6 @@ class RefResampler(_Base):
     def set_resamp_ratio_rational(self, n, d): ref().baz_ref_resamp_set_ratio_rational(self._h, n, d)
     def adjust(self, d): ref().baz_ref_resamp_post_double(self._h, d)
     def post_ppb(self, i, frac): ref().baz_ref_resamp_post_ppb(self._h, i, frac)
+    set_resamp_ratio_ppb = post_ppb
     def mu(self): return ref().baz_ref_resamp_mu(self._h)
     def resamp_ratio(self): return ref().baz_ref_resamp_ratio(self._h)

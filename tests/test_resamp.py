@@ -12,6 +12,7 @@ import re
 import numpy as np
 import pytest
 
+import resamp_phase_ref as pr
 from conftest import GOLDEN_DIR, ROOT
 from oracle import resamp_ref as rr
 
@@ -143,6 +144,25 @@ def scale_close(a, b, scale, rtol=1e-5):
     return bool(np.all(np.abs(a.real - b.real) <= rtol * scale) and np.all(np.abs(a.imag - b.imag) <= rtol * scale))
 
 
+def model_walks(g):
+    """FixedWalk and X87Walk (tests/resamp_phase_ref.py) through a fixture's calls and events.
+    -> (ii absolute, imu) of the library's model over all outputs, and whether the reference's walk is the same walk."""
+    fixed, x87 = make(pr.FixedWalk, g), make(pr.X87Walk, g)
+    iis, imus, same, pos = [], [], True, 0
+    for i, c in enumerate(g["calls"]):
+        for (ci, kind, a, b) in g["events"]:
+            if int(ci) == i:
+                apply_event(fixed, kind, a, b)
+                apply_event(x87, kind, a, b)
+        ii, imu, k = fixed.work(g["x"].shape[0] - pos, int(c))
+        ix, mx, kx = x87.work(int(c))
+        (ca, cb), (xa, xb) = pr.canonical(ii, imu), pr.canonical(ix, mx)
+        same = same and k == kx and np.array_equal(ca, xa) and np.array_equal(cb, xb)
+        iis.append(ii + pos); imus.append(imu)
+        pos += k
+    return np.concatenate(iis), np.concatenate(imus), same
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", resamp_golden())
 def test_hip_matches_golden(name, gpu_device):
@@ -154,7 +174,11 @@ def test_hip_matches_golden(name, gpu_device):
     assert np.array_equal(cons, g["consumed"])
     assert np.allclose(mus, g["mu_after"], rtol=0, atol=1e-15)
     assert scale_close(out, g["out"], float(np.abs(g["x"]).max()))
-    if exact:   # double-typed ratios: the closed-form phase IS the x87 sequence; same float accumulation order
+    # whatever the flag says: the float32 interpolation at the (ii, imu) of the library's documented 64.64 walk, bit for bit
+    ii, imu, same_walk = model_walks(g)
+    assert np.array_equal(out.view(np.uint32), pr.interp_f32(g["x"], ii, imu, rr.taps()).view(np.uint32))
+    assert same_walk or not exact                # the flag is sound
+    if exact or same_walk:   # the closed-form phase IS the x87 sequence; same float accumulation order
         assert np.array_equal(out.view(np.uint32), g["out"].view(np.uint32))
 
 
@@ -238,16 +262,25 @@ def test_hip_multistream_chunked_equals_oracle(phase, ratio, num, denom, gpu_dev
     calls = [int(c) for c in (1, 255, 256, 257, 5000, 3, 12000) if c * eff + 16 < L / 3]
     with resamp.Resampler(phase, ratio, num, denom, nstreams=S) as blk:
         oracles = [rr.Resampler(phase, ratio, num, denom) for _ in range(S)]
+        fixed, x87 = pr.FixedWalk(phase, ratio, num, denom), pr.X87Walk(phase, ratio, num, denom)
+        taps, same_walk = rr.taps(), True
         pos = 0
         for c in calls:
             out, k = blk.work(x[:, pos:], c)
             assert out.shape == (S, c)
+            ii, imu, kf = fixed.work(L - pos, c)
+            ix, mx, kx = x87.work(c)
+            (ca, cb), (xa, xb) = pr.canonical(ii, imu), pr.canonical(ix, mx)
+            same_walk = same_walk and kf == kx and np.array_equal(ca, xa) and np.array_equal(cb, xb)
+            assert k == kf and blk.phase_exact() == fixed.exact and (same_walk or not fixed.exact)
             for s in range(S):
                 o, ks = oracles[s].work(x[s, pos:], c)
                 assert ks == k
-                if blk.phase_exact():
+                # whatever the flag says: the float32 interpolation at the library's documented 64.64 walk, bit for bit
+                assert np.array_equal(out[s].view(np.uint32), pr.interp_f32(x[s, pos:], ii, imu, taps).view(np.uint32))
+                if blk.phase_exact() or same_walk:
                     assert np.array_equal(out[s].view(np.uint32), o.view(np.uint32))
-                else:   # 64-bit quotient ratio: imu may differ where mu*128 sits on a rounding boundary (none expected here)
+                else:   # a sum of the reference rounded: imu may differ where mu*128 sits on a rounding boundary
                     assert scale_close(out[s], o, float(np.abs(x).max()))
             pos += k
             assert abs(blk.mu() - oracles[0].mu()) < 1e-15
