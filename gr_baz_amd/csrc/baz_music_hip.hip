@@ -719,6 +719,11 @@ bool build_i8p_image(const std::vector<double>& F, uint32_t m, uint32_t res, uin
 
 // the scan's short form (scan_mfma_kernel, SIG) needs fewer MFMAs than the projector GEMM
 bool short_form_applies(uint32_t m, uint32_t n) { return (n == 2 && m >= 9 && m <= 16) || (n == 1 && m >= 6 && m <= 16); }
+// the shapes that get a digit image of the table (alloc_table_set)
+bool wants_i8_image(const baz_music_ctx* c)
+{
+    return !c->wide && c->m >= 6 && c->n <= 4 && i8_image_bytes(c->m, c->fb_steps) <= I8_IMAGE_LIMIT;
+}
 // The int8-matrix-core scan applies: 6 .. 16 antennas (row classes below, run-time-m kernels above), lists of <= 4 keys.
 // (launch_scan_i8 / _i8p / _coarse hold `if constexpr` bounds equal to what i8_active / i8p_active / coarse_applies admit: widen both or get E_UNSUPPORTED)
 bool i8_active(const baz_music_ctx* c)
@@ -740,27 +745,50 @@ bool short_form_in_use(const baz_music_ctx* c)
     return short_form_applies(c->m, c->n) && c->sig_scan && c->dSs && c->tab.dA2p && !c->lab_variant && !i8_active(c);
 }
 
+// The buffers of one workspace grow together, to `items` items (contents are not kept; bytes == 0: the shape has no such buffer).
+// Batches launched earlier may still use the buffers freed here: where one exists the stream is drained first (hipFree happens to
+// synchronise the device today; nothing here relies on it).
+struct WorkBuf { void** p; size_t bytes; };
+int regrow_workspace(baz_music_ctx* c, uint32_t& cap, uint32_t items, std::initializer_list<WorkBuf> bufs)
+{
+    bool any = false;
+    for (const WorkBuf& b : bufs) any = any || *b.p;
+    if (any) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (const WorkBuf& b : bufs)
+        if (*b.p) { (void)dev_free(*b.p); *b.p = nullptr; }
+    cap = 0;
+    for (const WorkBuf& b : bufs)
+        if (b.bytes) HIP_TRY(c, dev_malloc(b.p, b.bytes));
+    cap = items;
+    return BAZ_MUSIC_OK;
+}
+
+// 17 .. 64 antennas (the run-time-m kernels): room for a pass of `items` items
+int ensure_wide_workspace(baz_music_ctx* c, uint32_t items)
+{
+    if (items <= c->wide_cap) return BAZ_MUSIC_OK;
+    const size_t mm = (size_t)c->m * c->m;
+    return regrow_workspace(c, c->wide_cap, items,
+                            {{(void**)&c->dR, (size_t)items * mm * sizeof(double2)},
+                             {(void**)&c->dGw, (size_t)items * (c->m - c->n) * c->m * sizeof(double2)},
+                             {(void**)&c->dWS, (size_t)items * c->res * sizeof(double)},
+                             {(void**)&c->dSw, (size_t)items * c->n * c->m * sizeof(double2)},
+                             {(void**)&c->dRedo, (size_t)items}});
+}
+
+// The workspace of the context's shape, for launches of up to `batch` items
 int ensure_workspace(baz_music_ctx* c, uint32_t batch)
 {
+    if (c->wide) return ensure_wide_workspace(c, batch);
     if (batch <= c->cap) return BAZ_MUSIC_OK;
     const uint32_t cap = round_up(batch, 64);
     const size_t mm = (size_t)c->m * c->m;
-    // batches launched earlier may still use the buffers freed below: drain them first (hipFree happens to synchronise the device
-    // today; nothing here relies on it)
-    if (c->cap) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->dR) { (void)dev_free(c->dR); c->dR = nullptr; }
-    if (c->dQ) { (void)dev_free(c->dQ); c->dQ = nullptr; }
-    if (c->dG) { (void)dev_free(c->dG); c->dG = nullptr; }
-    if (c->dRedo) { (void)dev_free(c->dRedo); c->dRedo = nullptr; }
-    if (c->dSs) { (void)dev_free(c->dSs); c->dSs = nullptr; }
-    c->cap = 0;
-    HIP_TRY(c, dev_malloc((void**)&c->dR, (size_t)cap * mm * sizeof(double2)));
-    HIP_TRY(c, dev_malloc((void**)&c->dQ, (size_t)cap * mm * sizeof(double)));
-    HIP_TRY(c, dev_malloc((void**)&c->dG, (size_t)cap * mm * 2 * sizeof(double)));
-    HIP_TRY(c, dev_malloc((void**)&c->dRedo, (size_t)cap));
-    if (short_form_applies(c->m, c->n)) HIP_TRY(c, dev_malloc((void**)&c->dSs, (size_t)cap * 4 * c->n * c->m * sizeof(double)));
-    c->cap = cap;
-    return BAZ_MUSIC_OK;
+    return regrow_workspace(c, c->cap, cap,
+                            {{(void**)&c->dR, (size_t)cap * mm * sizeof(double2)},
+                             {(void**)&c->dQ, (size_t)cap * mm * sizeof(double)},
+                             {(void**)&c->dG, (size_t)cap * mm * 2 * sizeof(double)},
+                             {(void**)&c->dRedo, (size_t)cap},
+                             {(void**)&c->dSs, short_form_applies(c->m, c->n) ? (size_t)cap * 4 * c->n * c->m * sizeof(double) : 0}});
 }
 
 struct ProfScope {
@@ -852,7 +880,17 @@ int order_begin(baz_music_ctx* c, uint32_t items)
     return BAZ_MUSIC_OK;
 }
 
-int refuse_null(baz_music_ctx* c, const void* p, const char* name);     // (below, next to process_device_locked)
+// A launch sequence is REFUSED (BAZ_MUSIC_E_HIP, message in baz_music_last_hip_error) when a device pointer it is about to hand to a
+// kernel -- or to offset -- is null: a bug of that kind must come back as an error code, never as a GPU memory fault that takes the
+// process down (BENCH_r05: "Memory access fault ... on address 0x10000").  Host-side, a dozen compares per call.
+int refuse_null(baz_music_ctx* c, const void* p, const char* name)
+{
+    if (p) return BAZ_MUSIC_OK;
+    snprintf(c->hip_err, sizeof(c->hip_err), "internal: device pointer %s is null at launch (m=%u n=%u res=%u): launch refused", name, c->m, c->n, c->res);
+    return BAZ_MUSIC_E_HIP;
+}
+#define BAZ_REQUIRE(c, ptr) do { if (const int rn__ = refuse_null((c), (c)->ptr, #ptr)) return rn__; } while (0)
+#define BAZ_REQUIRE_TAB(c, ptr) do { if (const int rn__ = refuse_null((c), (c)->tab.ptr, #ptr)) return rn__; } while (0)
 
 // A chunk of `batch` items under a mode that is on: refused unless the call was opened with the mode on (order_begin) and the chunk
 // ends inside what the call was sized for.
@@ -937,8 +975,32 @@ int launch_cov_t(baz_music_ctx* c, const float* d_in, uint32_t batch, double2* d
     case 14: return CALL(14); case 15: return CALL(15); case 16: return CALL(16);
 #endif
 
+// 17 .. 64 antennas: the run-time-m covariance kernels of music_wide_kernels.hip.h
+int launch_cov_wide(baz_music_ctx* c, const float* d_in, uint32_t nb, double2* dR)
+{
+    ProfScope ps(c, BAZ_MUSIC_STAGE_COV);
+    if (c->wide_cov_mfma && c->m > 32) {   // 33 <= m <= 64: one wave per (item, pair of 16-antenna blocks)
+        const uint32_t nblk = (c->m + 15u) / 16u, npairs = nblk * (nblk + 1u) / 2u;
+        const uint64_t tasks = (uint64_t)nb * npairs;
+        const uint32_t blocks = (uint32_t)std::min<uint64_t>((tasks + 3) / 4, 8u * (uint64_t)c->wide_cov_blocks);
+        hipLaunchKernelGGL(bazwide::cov_wide_pairs_kernel, dim3(blocks), dim3(256), 0, c->stream,
+                           reinterpret_cast<const float2*>(d_in), dR, nb, c->m, c->K, npairs);
+    } else if (c->wide_cov_mfma) {  // 17 <= m <= 32: one wave per item on the fp64 matrix core, 2 workgroups per CU at most
+        const uint32_t blocks = std::min<uint32_t>((nb + 3) / 4, c->wide_cov_blocks);
+        hipLaunchKernelGGL(bazwide::cov_wide_mfma_kernel, dim3(blocks), dim3(256), 0, c->stream,
+                           reinterpret_cast<const float2*>(d_in), dR, nb, c->m, c->K);
+    } else {
+        hipLaunchKernelGGL(bazwide::cov_wide_kernel, dim3(nb), dim3(bazwide::WB), (size_t)bazwide::COV_TC * c->m * sizeof(float2),
+                           c->stream, reinterpret_cast<const float2*>(d_in), dR, c->m, c->K);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return BAZ_MUSIC_OK;
+}
+
+// The plain covariances of `batch` items -> dR, by the kernel of the context's shape
 int launch_cov(baz_music_ctx* c, const float* d_in, uint32_t batch, double2* dR)
 {
+    if (c->wide) return launch_cov_wide(c, d_in, batch, dR);
     ProfScope ps(c, BAZ_MUSIC_STAGE_COV);
 #define BAZ_CALL(MV) launch_cov_t<MV>(c, d_in, batch, dR)
     switch (c->m) {
@@ -1129,18 +1191,37 @@ int launch_whiten(baz_music_ctx* c, const double2* dRin, uint32_t batch, double2
 #undef BAZ_CALL
 }
 
+// The buffers of the two opt-in stages between covariance and EVD, for launches of up to `items` items
+int ensure_cov_stages(baz_music_ctx* c, uint32_t items)
+{
+    const int r = c->avg_window > 1 ? ensure_average(c, c->avg_window, items) : BAZ_MUSIC_OK;
+    return (r == BAZ_MUSIC_OK && c->tab.wh_on) ? ensure_whiten(c, items, true) : r;
+}
+
+// The covariance chain of every launch sequence: the plain covariances of `batch` items into c->dR, their averages where averaging is on
+// (the history runs from launch to launch), either whitened where whitening is on.  The result lies where cov_in_force() points.
+// ensure_cov_stages() came first.
+int launch_cov_stages(baz_music_ctx* c, const float* in, uint32_t batch)
+{
+    const double2* R = c->dR;
+    int r = launch_cov(c, in, batch, c->dR);
+    if (r == BAZ_MUSIC_OK && c->avg_window > 1) {
+        r = launch_average(c, R, batch, c->dRavg);
+        R = c->dRavg;
+    }
+    if (r == BAZ_MUSIC_OK && c->tab.wh_on) r = launch_whiten(c, R, batch, c->dRwh);
+    return r;
+}
+
 // Covariance + EVD of `batch` items: the projector coefficients into `dQ` (the workspace's c->dQ, or a debug tap's own buffer), the
 // noise eigenvectors into c->dG.  The fused kernel where it applies, else two kernels through c->dR.  ensure_workspace() came first.
 int launch_frontend(baz_music_ctx* c, const void* d_in, uint32_t batch, double* dQ, uint32_t qstride)
 {
     const float* in = static_cast<const float*>(d_in);
     if (c->avg_window > 1 || c->tab.wh_on) {   // opt-in averaging / whitening: always two kernels through c->dR, the stages between them
-        int ra = launch_cov(c, in, batch, c->dR);       // (ensure_average() came first; average first, whiten second)
-        if (ra == BAZ_MUSIC_OK && c->avg_window > 1) ra = launch_average(c, c->dR, batch, c->dRavg);
-        if (ra == BAZ_MUSIC_OK && c->tab.wh_on) {
-            ra = ensure_whiten(c, batch, true);
-            if (ra == BAZ_MUSIC_OK) ra = launch_whiten(c, c->avg_window > 1 ? c->dRavg : c->dR, batch, c->dRwh);
-        }
+        // (ensure_average() came first; R' is sized here as well: a debug tap comes without a sequence in front)
+        int ra = c->tab.wh_on ? ensure_whiten(c, batch, true) : BAZ_MUSIC_OK;
+        if (ra == BAZ_MUSIC_OK) ra = launch_cov_stages(c, in, batch);
         return ra ? ra : launch_evd(c, cov_in_force(c), batch, dQ, qstride, c->dG);
     }
     // (power / beam mode on: the fused kernel also stores its R, the tap baz_music_debug_cov uses -- same kernel, same Q and G bits)
@@ -1398,12 +1479,17 @@ ScanForm scan_form(const baz_music_ctx* c, bool spec)
 
 // One scan launch over the workspace: c->dQ (c->dSs: the short form) -> candidates in c->dCand; spec: where a spectrum is written (vec4: 16-byte stores)
 struct ScanCall { uint32_t batch, qstride; float* spec; bool vec4; };
+ScanCall scan_call(const baz_music_ctx* c, uint32_t batch, uint32_t qstride, float* spec)
+{
+    return {batch, qstride, spec, spec && (c->res % 4u) == 0 && (reinterpret_cast<uintptr_t>(spec) % 16u) == 0};
+}
 
 // What a scan launch did, for the merge that folds its candidate lists (nsplit: bin ranges per item)
 struct ScanDone {
     int rc;
     ScanKind kind;
     uint32_t nsplit;
+    bool last_pass = true;  // the merge behind it clears the NEXT call's statistic counter (17 .. 64 antennas: the last pass's merge only)
 #ifdef BAZ_MUSIC_LAB
     bool sorted = false;    // (BAZ_MUSIC_SORT) the gated scan walked the items through its index list
 #endif
@@ -1645,7 +1731,7 @@ ScanDone launch_scan(baz_music_ctx* c, uint32_t qstride, uint32_t batch, float* 
 {
     ProfScope ps(c, BAZ_MUSIC_STAGE_SCAN);
     const ScanForm form = scan_form(c, d_spec != nullptr);
-    const ScanCall s{batch, qstride, d_spec, d_spec && (c->res % 4u) == 0 && (reinterpret_cast<uintptr_t>(d_spec) % 16u) == 0};
+    const ScanCall s = scan_call(c, batch, qstride, d_spec);
 #define BAZ_CALL(MV) launch_scan_m<MV>(c, form, s)
     switch (c->m) {
         BAZ_M_CASES(BAZ_CALL)
@@ -1675,7 +1761,7 @@ int launch_merge(baz_music_ctx* c, const ScanDone& scan, uint32_t batch, float* 
     }
 #endif
     hipLaunchKernelGGL(kernel, dim3((batch + 255) / 256), dim3(256), 0, c->stream, c->dCand, d_spec, d_ang, d_lvl, batch, c->res, c->n,
-                       scan.nsplit, c->keep_mask, c->dRefined + (c->stat_parity ^ 1), fire_dev, fire_host, fire_tag);
+                       scan.nsplit, c->keep_mask, scan.last_pass ? c->dRefined + (c->stat_parity ^ 1) : nullptr, fire_dev, fire_host, fire_tag);
     return launch_rc(c);
 }
 
@@ -1731,185 +1817,157 @@ size_t wide_cand_entries(const baz_music_ctx* c, uint32_t pass)
     return std::max<size_t>(worst, (size_t)pass * W.nsplit) * W.nk;
 }
 
-int ensure_wide_workspace(baz_music_ctx* c, uint32_t items)
+// the items of the largest launch of a call of `batch` items: the call itself, or a pass of it at 17 .. 64 antennas
+uint32_t largest_launch_items(const baz_music_ctx* c, uint32_t batch) { return c->wide ? std::min(batch, wide_pass_items(c)) : batch; }
+
+// Which scan a launch of this sequence takes.  One place: process_wide_locked launches by it, baz_music_reserve sizes the candidate
+// lists by it, check_launch_pointers demands the table images by it.  MFMA (n <= 8): the short form on the fp64 matrix core
+// (scan_wide_mfma_kernel), candidates for bazmusic's merge; SHORT, LITERAL: scan_wide_kernel, with ||a||^2 - ||S^H a||^2 away from the
+// nulls where the emitters are few (2n <= m), or the literal form throughout.
+enum WideScanForm { WIDE_SCAN_MFMA, WIDE_SCAN_SHORT, WIDE_SCAN_LITERAL };
+WideScanForm wide_scan_form(const baz_music_ctx* c)
 {
-    if (items <= c->wide_cap) return BAZ_MUSIC_OK;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->dR) { (void)dev_free(c->dR); c->dR = nullptr; }
-    if (c->dGw) { (void)dev_free(c->dGw); c->dGw = nullptr; }
-    if (c->dWS) { (void)dev_free(c->dWS); c->dWS = nullptr; }
-    if (c->dSw) { (void)dev_free(c->dSw); c->dSw = nullptr; }
-    if (c->dRedo) { (void)dev_free(c->dRedo); c->dRedo = nullptr; }
-    c->wide_cap = 0;
-    const size_t mm = (size_t)c->m * c->m;
-    HIP_TRY(c, dev_malloc((void**)&c->dR, (size_t)items * mm * sizeof(double2)));
-    HIP_TRY(c, dev_malloc((void**)&c->dGw, (size_t)items * (c->m - c->n) * c->m * sizeof(double2)));
-    HIP_TRY(c, dev_malloc((void**)&c->dWS, (size_t)items * c->res * sizeof(double)));
-    HIP_TRY(c, dev_malloc((void**)&c->dSw, (size_t)items * c->n * c->m * sizeof(double2)));
-    HIP_TRY(c, dev_malloc((void**)&c->dRedo, (size_t)items));
-    c->wide_cap = items;
+    if (c->wide_literal_only) return WIDE_SCAN_LITERAL;
+    if (c->wide_mfma) return WIDE_SCAN_MFMA;
+    return 2 * c->n <= c->m ? WIDE_SCAN_SHORT : WIDE_SCAN_LITERAL;
+}
+
+// The device pointers a launch sequence of this context's shape hands to its kernels (refuse_null)
+int check_launch_pointers(baz_music_ctx* c)
+{
+    BAZ_REQUIRE(c, dRefined);
+    BAZ_REQUIRE(c, dR);
+    BAZ_REQUIRE(c, dRedo);
+    if (c->avg_window > 1) { BAZ_REQUIRE(c, dRavg); BAZ_REQUIRE(c, dAvgHist[0]); BAZ_REQUIRE(c, dAvgHist[1]); }
+    if (c->tab.wh_on) { BAZ_REQUIRE(c, dRwh); BAZ_REQUIRE_TAB(c, dWh); }
+    if (c->wide) {
+        BAZ_REQUIRE(c, dGw); BAZ_REQUIRE(c, dWS); BAZ_REQUIRE(c, dSw); BAZ_REQUIRE_TAB(c, dTA); BAZ_REQUIRE_TAB(c, dA2);
+        if (wide_scan_form(c) == WIDE_SCAN_MFMA) { BAZ_REQUIRE_TAB(c, dTB); BAZ_REQUIRE_TAB(c, dA2p); }
+        return BAZ_MUSIC_OK;
+    }
+    BAZ_REQUIRE(c, dQ); BAZ_REQUIRE(c, dG); BAZ_REQUIRE(c, dCand); BAZ_REQUIRE_TAB(c, dFB); BAZ_REQUIRE_TAB(c, dTB);
+    if (short_form_applies(c->m, c->n)) { BAZ_REQUIRE(c, dSs); BAZ_REQUIRE_TAB(c, dA2p); }
+    if (c->tab.cs_ok) BAZ_REQUIRE_TAB(c, dCS);
+    if (c->tab.i8_ok && wants_i8_image(c)) BAZ_REQUIRE_TAB(c, dIB);
     return BAZ_MUSIC_OK;
 }
 
-int launch_cov_wide(baz_music_ctx* c, const float* d_in, uint32_t nb, double2* dR)
+template <bool TRI>
+auto* sub_wide_kernel_n(uint32_t n)      // (n >= 1: baz_music_create)
 {
-    ProfScope ps(c, BAZ_MUSIC_STAGE_COV);
-    if (c->wide_cov_mfma && c->m > 32) {   // 33 <= m <= 64: one wave per (item, pair of 16-antenna blocks)
-        const uint32_t nblk = (c->m + 15u) / 16u, npairs = nblk * (nblk + 1u) / 2u;
-        const uint64_t tasks = (uint64_t)nb * npairs;
-        const uint32_t blocks = (uint32_t)std::min<uint64_t>((tasks + 3) / 4, 8u * (uint64_t)c->wide_cov_blocks);
-        hipLaunchKernelGGL(bazwide::cov_wide_pairs_kernel, dim3(blocks), dim3(256), 0, c->stream,
-                           reinterpret_cast<const float2*>(d_in), dR, nb, c->m, c->K, npairs);
-        HIP_TRY(c, hipGetLastError());
-        return BAZ_MUSIC_OK;
-    }
-    if (c->wide_cov_mfma) {         // 17 <= m <= 32: one wave per item on the fp64 matrix core, 2 workgroups per CU at most
-        const uint32_t blocks = std::min<uint32_t>((nb + 3) / 4, c->wide_cov_blocks);
-        hipLaunchKernelGGL(bazwide::cov_wide_mfma_kernel, dim3(blocks), dim3(256), 0, c->stream,
-                           reinterpret_cast<const float2*>(d_in), dR, nb, c->m, c->K);
-        HIP_TRY(c, hipGetLastError());
-        return BAZ_MUSIC_OK;
-    }
-    hipLaunchKernelGGL(bazwide::cov_wide_kernel, dim3(nb), dim3(bazwide::WB), (size_t)bazwide::COV_TC * c->m * sizeof(float2),
-                       c->stream, reinterpret_cast<const float2*>(d_in), dR, c->m, c->K);
-    HIP_TRY(c, hipGetLastError());
-    return BAZ_MUSIC_OK;
+    using namespace bazwide;
+    decltype(&sub_wide_kernel<1, TRI>) const kernels[8] = {&sub_wide_kernel<1, TRI>, &sub_wide_kernel<2, TRI>, &sub_wide_kernel<3, TRI>, &sub_wide_kernel<4, TRI>,
+                                                           &sub_wide_kernel<5, TRI>, &sub_wide_kernel<6, TRI>, &sub_wide_kernel<7, TRI>, &sub_wide_kernel<8, TRI>};
+    return kernels[std::min(n, 8u) - 1];
 }
 
-int check_launch_pointers(baz_music_ctx* c);       // (below, next to process_device_locked)
-int refuse_null(baz_music_ctx* c, const void* p, const char* name);
+// The EVD of a pass of nb items: noise eigenvectors into c->dGw, signal eigenvectors into c->dSw
+int launch_evd_wide(baz_music_ctx* c, const double2* R, uint32_t nb)
+{
+    ProfScope ps(c, BAZ_MUSIC_STAGE_EVD);
+    const uint8_t* only = nullptr;
+    if (c->sub_evd && c->n <= 8) {     // few emitters: signal subspace by orthogonal iteration, Jacobi for what it hands back
+        // from 50 antennas on the lower triangle of R only (sub_wide_kernel, TRI): four workgroups per CU instead of two or three
+        const bool tri = c->m >= 50;
+        const size_t lds = ((tri ? (size_t)c->m * (c->m + 1) / 2 : (size_t)c->m * (c->m + 1)) + (size_t)c->n * 64) * sizeof(double2);
+        auto* kernel = tri ? sub_wide_kernel_n<true>(c->n) : sub_wide_kernel_n<false>(c->n);
+        hipLaunchKernelGGL(kernel, dim3(nb), dim3(64), lds, c->stream, R, c->dGw, c->dSw, c->dRedo, c->m);
+        HIP_TRY(c, hipGetLastError());
+        only = c->dRedo;
+    }
+    hipLaunchKernelGGL(bazwide::evd_wide_kernel, dim3(nb), dim3(bazwide::WB), wide_evd_lds(c->m), c->stream, R, c->dGw, c->dSw, c->m, c->n, only);
+    return launch_rc(c);
+}
 
+// PMAX: staged phases per step (2 to 32 antennas, 4 to 64); NOUT: outputs per item (4: n <= 2, 8: n = 3, 4)
+template <int PMAX, int NOUT>
+auto* scan_wide_mfma_kernel_for(const ScanCall& s)
+{
+    if (s.vec4) return &bazwide::scan_wide_mfma_kernel<true, true, PMAX, NOUT>;
+    if (s.spec) return &bazwide::scan_wide_mfma_kernel<true, false, PMAX, NOUT>;
+    return &bazwide::scan_wide_mfma_kernel<false, false, PMAX, NOUT>;
+}
+template <int PMAX>
+auto* scan_wide_mfma_kernel_n(uint32_t n, const ScanCall& s)
+{
+    if (n <= 2) return scan_wide_mfma_kernel_for<PMAX, 4>(s);
+    if (n <= 4) return scan_wide_mfma_kernel_for<PMAX, 8>(s);
+    return scan_wide_mfma_kernel_for<PMAX, 16>(s);
+}
+
+// WIDE_SCAN_MFMA over a pass of s.batch items: c->dSw, c->dGw -> candidates per bin range in c->dCand, for launch_merge
+ScanDone launch_scan_wide_mfma(baz_music_ctx* c, const ScanCall& s)
+{
+    ProfScope ps(c, BAZ_MUSIC_STAGE_SCAN);
+    const WideScanGeom W = wide_scan_geometry(c, s.batch);
+    auto* kernel = c->m <= 32 ? scan_wide_mfma_kernel_n<2>(c->n, s) : scan_wide_mfma_kernel_n<4>(c->n, s);
+    hipLaunchKernelGGL(kernel, dim3(W.groups * W.nsplit), dim3(256), 0, c->stream, c->dSw, c->dGw, c->tab.dTB + c->tb_step_elems, c->tab.dA2p + 64,
+                       c->tab.dTA, s.spec, c->dCand, s.batch, c->m, c->n, c->res, W.nsplit, c->keep_mask, c->tab.refine_below,
+                       c->dRefined + c->stat_parity);
+    return {launch_rc(c), SCAN_FP64, W.nsplit};   // (the kind: what launch_merge knows as a scan without a fire statistic)
+}
+
+// WIDE_SCAN_SHORT / _LITERAL over a pass of nb items: the fp64 strengths of every bin into c->dWS, for launch_topn_wide
+int launch_scan_wide_plain(baz_music_ctx* c, uint32_t nb, float* spec, bool short_form)
+{
+    ProfScope ps(c, BAZ_MUSIC_STAGE_SCAN);
+    // enough workgroups for a small batch: split the bins of an item over several
+    const uint32_t max_y = (c->res + bazwide::WB - 1) / bazwide::WB;
+    const uint32_t ny = std::max(1u, std::min(max_y, (2048u + nb - 1) / nb));
+    const uint32_t bpb = round_up((c->res + ny - 1) / ny, bazwide::WB);
+    const uint32_t rows = c->m - c->n + (short_form ? c->n : 0u);      // the noise basis and, for the short form, the signal basis
+    hipLaunchKernelGGL(bazwide::scan_wide_kernel, dim3(nb, (c->res + bpb - 1) / bpb), dim3(bazwide::WB), (size_t)rows * c->m * sizeof(double2),
+                       c->stream, c->dGw, short_form ? c->dSw : nullptr, c->tab.dTA, c->tab.dA2, c->tab.refine_below, c->dWS, spec, c->m, c->n,
+                       c->res, bpb);
+    return launch_rc(c);
+}
+
+int launch_topn_wide(baz_music_ctx* c, uint32_t nb, float* d_ang, float* d_lvl)
+{
+    ProfScope ps(c, BAZ_MUSIC_STAGE_MERGE);
+    hipLaunchKernelGGL(bazwide::topn_wide_kernel, dim3(nb), dim3(bazwide::WB), 0, c->stream, c->dWS, d_ang, d_lvl, c->res, c->n);
+    return launch_rc(c);
+}
+
+// One call of `batch` items at 17 .. 64 antennas, in passes of at most wide_pass_items(): each pass is the whole sequence over its
+// slice of in / ang / lvl / spec.  The averaging history runs from pass to pass; the passes' scan statistics add up.
 int process_wide_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, void* d_ang, void* d_lvl, void* d_spec)
 {
-    const uint32_t pass = std::min(batch, wide_pass_items(c));
-    int r = ensure_wide_workspace(c, pass);
-    if (r) return r;
-    if (c->avg_window > 1) {
-        r = ensure_average(c, c->avg_window, pass);
-        if (r) return r;
-    }
-    if (c->tab.wh_on) {
-        r = ensure_whiten(c, pass, true);
-        if (r) return r;
-    }
-    r = check_launch_pointers(c);
+    const uint32_t pass = largest_launch_items(c, batch);
+    int r = ensure_workspace(c, pass);
+    if (r == BAZ_MUSIC_OK) r = ensure_cov_stages(c, pass);
+    if (r == BAZ_MUSIC_OK) r = check_launch_pointers(c);
     if (r) return r;
     const float* in = static_cast<const float*>(d_in);
     float* ang = static_cast<float*>(d_ang);
     float* lvl = static_cast<float*>(d_lvl);
     float* spec = static_cast<float*>(d_spec);
-    const uint32_t nn = c->m - c->n;
+    const WideScanForm form = wide_scan_form(c);
     for (uint32_t off = 0; off < batch; off += pass) {
         const uint32_t nb = std::min(pass, batch - off);
-        r = launch_cov_wide(c, in + (size_t)off * c->nsamples * 2, nb, c->dR);
+        float* const p_ang = ang + (size_t)off * c->n;
+        float* const p_lvl = lvl ? lvl + (size_t)off * c->n : nullptr;
+        float* const p_spec = spec ? spec + (size_t)off * c->res : nullptr;
+        r = launch_cov_stages(c, in + (size_t)off * c->nsamples * 2, nb);
+        if (r == BAZ_MUSIC_OK) r = launch_evd_wide(c, cov_in_force(c), nb);
         if (r) return r;
-        // what the EVD reads: the pass's plain covariances, or their averages (the history runs from pass to pass), or either whitened
-        if (c->avg_window > 1) {
-            r = launch_average(c, c->dR, nb, c->dRavg);
+        if (form != WIDE_SCAN_MFMA) {
+            r = launch_scan_wide_plain(c, nb, p_spec, form == WIDE_SCAN_SHORT);
+            if (r == BAZ_MUSIC_OK) r = launch_topn_wide(c, nb, p_ang, p_lvl);
             if (r) return r;
-        }
-        if (c->tab.wh_on) {
-            r = launch_whiten(c, c->avg_window > 1 ? c->dRavg : c->dR, nb, c->dRwh);
-            if (r) return r;
-        }
-        const double2* const Rw = cov_in_force(c);
-        {
-            ProfScope ps(c, BAZ_MUSIC_STAGE_EVD);
-            const uint8_t* only = nullptr;
-            if (c->sub_evd && c->n <= 8) {     // few emitters: signal subspace by orthogonal iteration, Jacobi for what it hands back
-                // from 50 antennas on the lower triangle of R only (sub_wide_kernel, TRI): four workgroups per CU instead of two or three
-                const bool tri = c->m >= 50;
-                const size_t lds = ((tri ? (size_t)c->m * (c->m + 1) / 2 : (size_t)c->m * (c->m + 1)) + (size_t)c->n * 64) * sizeof(double2);
-#define BAZ_SUB_WIDE(P)                                                                                                          \
-    do {                                                                                                                         \
-        if (tri) hipLaunchKernelGGL((bazwide::sub_wide_kernel<P, true>), dim3(nb), dim3(64), lds, c->stream, Rw, c->dGw, c->dSw, c->dRedo, c->m);  \
-        else hipLaunchKernelGGL((bazwide::sub_wide_kernel<P, false>), dim3(nb), dim3(64), lds, c->stream, Rw, c->dGw, c->dSw, c->dRedo, c->m);     \
-    } while (0)
-                switch (c->n) {
-                    case 1: BAZ_SUB_WIDE(1); break;
-                    case 2: BAZ_SUB_WIDE(2); break;
-                    case 3: BAZ_SUB_WIDE(3); break;
-                    case 4: BAZ_SUB_WIDE(4); break;
-                    case 5: BAZ_SUB_WIDE(5); break;
-                    case 6: BAZ_SUB_WIDE(6); break;
-                    case 7: BAZ_SUB_WIDE(7); break;
-                    default: BAZ_SUB_WIDE(8); break;
-                }
-#undef BAZ_SUB_WIDE
-                HIP_TRY(c, hipGetLastError());
-                only = c->dRedo;
-            }
-            hipLaunchKernelGGL(bazwide::evd_wide_kernel, dim3(nb), dim3(bazwide::WB), wide_evd_lds(c->m), c->stream, Rw,
-                               c->dGw, c->dSw, c->m, c->n, only);
-            HIP_TRY(c, hipGetLastError());
-        }
-        if (c->wide_mfma && !c->wide_literal_only) {
-            // 17 <= m <= 64, n <= 8: the short form on the fp64 matrix core, candidates per bin range, bazmusic's merge
-            const WideScanGeom W = wide_scan_geometry(c, nb);
-            const uint32_t nk = W.nk, groups = W.groups, nsplit = W.nsplit;
-            r = ensure_candidates(c, std::max(wide_cand_entries(c, pass), (size_t)nb * nsplit * nk));
-            if (r) return r;
-            r = refuse_null(c, c->dCand, "dCand");
-            if (r) return r;
-            float* sp = spec ? spec + (size_t)off * c->res : nullptr;
-            {
-                ProfScope ps(c, BAZ_MUSIC_STAGE_SCAN);
-                const bool vec4 = sp && (c->res % 4u) == 0 && (reinterpret_cast<uintptr_t>(sp) % 16u) == 0;
-#define BAZ_WIDE_ARGS dim3(groups * nsplit), dim3(256), 0, c->stream, c->dSw, c->dGw, c->tab.dTB + c->tb_step_elems, c->tab.dA2p + 64, c->tab.dTA, sp, \
-                      c->dCand, nb, c->m, c->n, c->res, nsplit, c->keep_mask, c->tab.refine_below, c->dRefined + c->stat_parity
-#define BAZ_WIDE_LAUNCH(PMAX, NOUT)                                                                                       \
-    do {                                                                                                                  \
-        if (sp && vec4) hipLaunchKernelGGL((bazwide::scan_wide_mfma_kernel<true, true, PMAX, NOUT>), BAZ_WIDE_ARGS);      \
-        else if (sp) hipLaunchKernelGGL((bazwide::scan_wide_mfma_kernel<true, false, PMAX, NOUT>), BAZ_WIDE_ARGS);        \
-        else hipLaunchKernelGGL((bazwide::scan_wide_mfma_kernel<false, false, PMAX, NOUT>), BAZ_WIDE_ARGS);               \
-    } while (0)
-                // PMAX: staged phases per step (2 to 32 antennas, 4 to 64); NOUT: outputs per item (4: n <= 2, 8: n = 3, 4)
-                if (c->m <= 32 && c->n <= 2) BAZ_WIDE_LAUNCH(2, 4);
-                else if (c->m <= 32 && c->n <= 4) BAZ_WIDE_LAUNCH(2, 8);
-                else if (c->m <= 32) BAZ_WIDE_LAUNCH(2, 16);
-                else if (c->n <= 2) BAZ_WIDE_LAUNCH(4, 4);
-                else if (c->n <= 4) BAZ_WIDE_LAUNCH(4, 8);
-                else BAZ_WIDE_LAUNCH(4, 16);
-#undef BAZ_WIDE_LAUNCH
-#undef BAZ_WIDE_ARGS
-                HIP_TRY(c, hipGetLastError());
-            }
-            {
-                ProfScope ps(c, BAZ_MUSIC_STAGE_MERGE);
-                // the statistic counter of the NEXT call is cleared by the last pass's merge only (the passes of one call add up)
-                unsigned long long* next_stat = (off + nb >= batch) ? c->dRefined + (c->stat_parity ^ 1) : nullptr;
-#define BAZ_WIDE_MERGE(NK)                                                                                               \
-    hipLaunchKernelGGL((topn_merge_kernel<NK>), dim3((nb + 255) / 256), dim3(256), 0, c->stream, c->dCand, sp,          \
-                       ang + (size_t)off * c->n, lvl ? lvl + (size_t)off * c->n : nullptr, nb, c->res, c->n, nsplit,    \
-                       c->keep_mask, next_stat)
-                if (nk == 2) BAZ_WIDE_MERGE(2);
-                else if (nk == 4) BAZ_WIDE_MERGE(4);
-                else BAZ_WIDE_MERGE(8);
-#undef BAZ_WIDE_MERGE
-                HIP_TRY(c, hipGetLastError());
-            }
             continue;
         }
-        {
-            ProfScope ps(c, BAZ_MUSIC_STAGE_SCAN);
-            // enough workgroups for a small batch: split the bins of an item over several
-            const uint32_t max_y = (c->res + bazwide::WB - 1) / bazwide::WB;
-            const uint32_t ny = std::max(1u, std::min(max_y, (2048u + nb - 1) / nb));
-            const uint32_t bpb = round_up((c->res + ny - 1) / ny, bazwide::WB);
-            const bool short_form = 2 * c->n <= c->m && !c->wide_literal_only;     // few emitters: ||a||^2 - ||S^H a||^2 away from the nulls
-            hipLaunchKernelGGL(bazwide::scan_wide_kernel, dim3(nb, (c->res + bpb - 1) / bpb), dim3(bazwide::WB),
-                               (size_t)(nn + (short_form ? c->n : 0u)) * c->m * sizeof(double2), c->stream, c->dGw,
-                               short_form ? c->dSw : nullptr, c->tab.dTA, c->tab.dA2, c->tab.refine_below, c->dWS,
-                               spec ? spec + (size_t)off * c->res : nullptr, c->m, c->n, c->res, bpb);
-            HIP_TRY(c, hipGetLastError());
-        }
-        {
-            ProfScope ps(c, BAZ_MUSIC_STAGE_MERGE);
-            hipLaunchKernelGGL(bazwide::topn_wide_kernel, dim3(nb), dim3(bazwide::WB), 0, c->stream, c->dWS,
-                               ang + (size_t)off * c->n, lvl ? lvl + (size_t)off * c->n : nullptr, c->res, c->n);
-            HIP_TRY(c, hipGetLastError());
-        }
+        const WideScanGeom W = wide_scan_geometry(c, nb);
+        r = ensure_candidates(c, std::max(wide_cand_entries(c, pass), (size_t)nb * W.nsplit * W.nk));
+        if (r == BAZ_MUSIC_OK) r = refuse_null(c, c->dCand, "dCand");
+        if (r) return r;
+        ScanDone scan = launch_scan_wide_mfma(c, scan_call(c, nb, 0, p_spec));
+        if (scan.rc) return scan.rc;
+        scan.last_pass = off + nb >= batch;      // the statistic counter of the NEXT call is cleared by the last pass's merge only
+        r = launch_merge(c, scan, nb, p_ang, p_lvl, p_spec);
+        if (r) return r;
     }
+    c->stat_next_clean = true;     // (the last pass's merge cleared the next call's statistic counter; the plain scan counts nothing)
     return BAZ_MUSIC_OK;
 }
 
@@ -1919,10 +1977,6 @@ using TableSet = baz_music_ctx::TableSet;
 size_t coarse_image_bytes(const baz_music_ctx* c)
 {
     return ((size_t)(c->cs_tiles + 1) * cs_c_units((int)c->m) + (size_t)c->cs_tiles * CS_X_UNITS * cs_groups((int)c->m)) * 16;
-}
-bool wants_i8_image(const baz_music_ctx* c)
-{
-    return !c->wide && c->m >= 6 && c->n <= 4 && i8_image_bytes(c->m, c->fb_steps) <= I8_IMAGE_LIMIT;
 }
 
 // one set of buffers for the configuration of `c` (what baz_music_create used to allocate in place)
@@ -2364,44 +2418,6 @@ int begin_statistic(baz_music_ctx* c)
     return BAZ_MUSIC_OK;
 }
 
-// A launch sequence is REFUSED (BAZ_MUSIC_E_HIP, message in baz_music_last_hip_error) when a device pointer it is about to hand to a
-// kernel -- or to offset -- is null: a bug of that kind must come back as an error code, never as a GPU memory fault that takes the
-// process down (BENCH_r05: "Memory access fault ... on address 0x10000").  Host-side, a dozen compares per call.
-int refuse_null(baz_music_ctx* c, const void* p, const char* name)
-{
-    if (p) return BAZ_MUSIC_OK;
-    snprintf(c->hip_err, sizeof(c->hip_err), "internal: device pointer %s is null at launch (m=%u n=%u res=%u): launch refused", name, c->m, c->n, c->res);
-    return BAZ_MUSIC_E_HIP;
-}
-#define BAZ_REQUIRE(c, ptr)                                  \
-    do {                                                     \
-        if (const int rn__ = refuse_null((c), (c)->ptr, #ptr)) return rn__; \
-    } while (0)
-
-#define BAZ_REQUIRE_TAB(c, ptr)                              \
-    do {                                                     \
-        if (const int rn__ = refuse_null((c), (c)->tab.ptr, #ptr)) return rn__; \
-    } while (0)
-
-int check_launch_pointers(baz_music_ctx* c)
-{
-    BAZ_REQUIRE(c, dRefined);
-    BAZ_REQUIRE(c, dR);
-    BAZ_REQUIRE(c, dRedo);
-    if (c->avg_window > 1) { BAZ_REQUIRE(c, dRavg); BAZ_REQUIRE(c, dAvgHist[0]); BAZ_REQUIRE(c, dAvgHist[1]); }
-    if (c->tab.wh_on) { BAZ_REQUIRE(c, dRwh); BAZ_REQUIRE_TAB(c, dWh); }
-    if (c->wide) {
-        BAZ_REQUIRE(c, dGw); BAZ_REQUIRE(c, dWS); BAZ_REQUIRE(c, dSw); BAZ_REQUIRE_TAB(c, dTA); BAZ_REQUIRE_TAB(c, dA2);
-        if (c->wide_mfma) { BAZ_REQUIRE_TAB(c, dTB); BAZ_REQUIRE_TAB(c, dA2p); }
-        return BAZ_MUSIC_OK;
-    }
-    BAZ_REQUIRE(c, dQ); BAZ_REQUIRE(c, dG); BAZ_REQUIRE(c, dCand); BAZ_REQUIRE_TAB(c, dFB); BAZ_REQUIRE_TAB(c, dTB);
-    if (short_form_applies(c->m, c->n)) { BAZ_REQUIRE(c, dSs); BAZ_REQUIRE_TAB(c, dA2p); }
-    if (c->tab.cs_ok) BAZ_REQUIRE_TAB(c, dCS);
-    if (c->tab.i8_ok && wants_i8_image(c)) BAZ_REQUIRE_TAB(c, dIB);
-    return BAZ_MUSIC_OK;
-}
-
 // Opt-in sub-bin refinement of the chunk's entries (refine_kernels.hip.h): reads the staged ang | lvl, the item's projector / noise
 // vectors of this launch sequence and the raw image of the table in force; writes the caller's ang / lvl and this chunk's offsets.
 template <int M>
@@ -2618,100 +2634,50 @@ int launch_topn_spec(baz_music_ctx* c, uint32_t batch, float* d_ang, float* d_lv
     return launch_rc(c);
 }
 
-int process_device_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void* d_ang, void* d_lvl, void* d_spec);
-int process_estimator_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void* d_ang, void* d_lvl, void* d_spec);
-
-// One launch sequence over `batch` items.  Averaging on: a sequence that fails forgets the history (the stream position the host
-// keeps no longer describes what the device holds); the next item is t = 0.
-int process_device_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, void* d_ang, void* d_lvl,
-                          void* d_spec)
+// ---- the tail of the 2 .. 16 antenna sequences: the pickers' staging, and what runs behind the pickers --------------------------------
+// Where the pickers of a chunk write ang / lvl.  Refinement / power / beam mode: into the staging buffer of this context, ang | lvl
+// (lvl always: it marks the real entries), and refine_kernel / power_kernel / beam_weights_kernel write the caller's -- which may be
+// host memory mapped over the link, never read back.  Otherwise: the caller's.
+struct PickerOut { float *ang, *lvl; };
+int stage_picker_out(baz_music_ctx* c, uint32_t batch, void* d_ang, void* d_lvl, PickerOut& out)
 {
-    const int r = process_device_body(c, d_in, batch, d_ang, d_lvl, d_spec);
-    if (r != BAZ_MUSIC_OK) c->avg_hist = 0;
-    return r;
+    out = {static_cast<float*>(d_ang), static_cast<float*>(d_lvl)};
+    if (!c->refine_mode && !c->power_mode && !c->beam_mode) return BAZ_MUSIC_OK;
+    const size_t entries = (size_t)batch * c->n;
+    if (const int r = grow(c, c->dRefAl, c->ref_al_cap, entries * 2)) return r;
+    out = {c->dRefAl, c->dRefAl + entries};
+    return BAZ_MUSIC_OK;
 }
 
-int process_device_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void* d_ang, void* d_lvl, void* d_spec)
+// What follows the pickers where a mode staged them: refinement (MUSIC only: the setters refuse it under an estimator), power, beam
+// weights and beam apply, in this order, each where its mode is on; each adds the chunk to its side output.  All read the staging
+// buffer.  A caller-visible word is written exactly once, by the last kernel that has something to say about it: the angle by
+// refine_kernel, the level by power_kernel in power mode 2 (lvl carries P); a word nobody has anything to say about by the first
+// kernel that runs.  The caller's pointers each kernel receives (-: null; port 1 not wired: lvl is null in every column; beam mode
+// on / off changes no row):
+//   refine  power | refine_kernel  power_kernel  beam_weights_kernel
+//   off     0     |                               ang  lvl
+//   off     1, 2  |                ang  lvl        -    -
+//   on      0     |  ang  lvl                      -    -
+//   on      1     |  ang  lvl       -    -         -    -
+//   on      2     |  ang   -        -   lvl        -    -
+int launch_after_pickers(baz_music_ctx* c, const void* d_in, uint32_t batch, uint32_t qstride, void* d_ang, void* d_lvl)
 {
-    if (c->wide) {
-        const int rw = process_wide_locked(c, d_in, batch, d_ang, d_lvl, d_spec);
-        if (rw == BAZ_MUSIC_OK) c->stat_next_clean = true;    // (no scan statistic on this path: the counters stay 0)
-        return rw;
-    }
-    if (c->estimator) return process_estimator_body(c, d_in, batch, d_ang, d_lvl, d_spec);
-    int r = ensure_workspace(c, batch);
-    if (r) return r;
-    r = reserve_candidates(c, batch);
-    if (r) return r;
-    if (c->avg_window > 1) {
-        r = ensure_average(c, c->avg_window, batch);
-        if (r) return r;
-    }
-    if (c->tab.wh_on) {
-        r = ensure_whiten(c, batch, true);
-        if (r) return r;
-    }
-    r = check_launch_pointers(c);
-    if (r) return r;
-    const uint32_t qstride = baz_music_q_stride(batch);
-    // the modes' side outputs: this chunk's go behind those of the call's earlier chunks (order_begin sized the buffers for the call)
-    for (const SideMode& md : side_modes(c))
-        if (const int rs = side_refuse(c, md, batch)) return rs;
-    uint8_t* const ord = c->order_mode ? c->out_ord.chunk<uint8_t>() : nullptr;
-    c->ord_cur = ord;
-    r = launch_frontend(c, d_in, batch, c->dQ, qstride);
-    c->ord_cur = nullptr;
-    if (r) return r;
-    float* spec = static_cast<float*>(d_spec);
-    if (c->peak_mode && !spec) {   // the peak picker reads the spectrum: keep a private one when port 2 is not wired
-        r = grow(c, c->dPeakSpec, c->peak_spec_cap, (size_t)batch * c->res);
-        if (r) return r;
-        spec = c->dPeakSpec;
-    }
-    // refinement / power / beam mode: the pickers write ang | lvl (lvl always: it marks the real entries) into a staging buffer of this context
-    // and refine_kernel / power_kernel / beam_weights_kernel write the caller's -- which may be host memory mapped over the link, never read back
-    float* ang = static_cast<float*>(d_ang);
-    float* lvl = static_cast<float*>(d_lvl);
-    const size_t entries = (size_t)batch * c->n;
-    if (c->refine_mode || c->power_mode || c->beam_mode) {
-        r = grow(c, c->dRefAl, c->ref_al_cap, entries * 2);
-        if (r) return r;
-        ang = c->dRefAl;
-        lvl = c->dRefAl + entries;
-    }
-    const ScanDone scan = launch_scan(c, qstride, batch, spec);
-    if (scan.rc) return scan.rc;
-    r = launch_merge(c, scan, batch, ang, lvl, spec);
-    if (r) return r;
-    c->stat_next_clean = true;     // the merge cleared the next call's statistic counter
-    if (c->peak_mode) {
-        r = launch_peaks(c, batch, ang, lvl, spec);
-        if (r) return r;
-    }
-    if (ord) {                     // (0, 0) at and beyond every item's own count: the n - k weakest entries of either picker
-        ProfScope ps(c, BAZ_MUSIC_STAGE_MERGE);
-        hipLaunchKernelGGL(bazorder::order_truncate_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, c->stream,
-                           ang, lvl, ord, batch, c->n);
-        HIP_TRY(c, hipGetLastError());
-        c->out_ord.count += batch;
-    }
+    enum Writer { REFINE, POWER, BEAM };
+    const Writer ang_by = c->refine_mode ? REFINE : (c->power_mode ? POWER : BEAM);
+    const Writer lvl_by = c->power_mode == 2 ? POWER : ang_by;
+    const auto ang = [&](Writer w) { return w == ang_by ? static_cast<float*>(d_ang) : nullptr; };
+    const auto lvl = [&](Writer w) { return w == lvl_by ? static_cast<float*>(d_lvl) : nullptr; };
     if (c->refine_mode) {
-        // (with power mode 2 and port 1 wired, power_kernel writes lvl: every caller-visible word is written once)
-        const bool lvl_later = c->power_mode == 2 && d_lvl;
-        r = launch_refine(c, batch, qstride, static_cast<float*>(d_ang), lvl_later ? nullptr : static_cast<float*>(d_lvl));
-        if (r) return r;
+        if (const int r = launch_refine(c, batch, qstride, ang(REFINE), lvl(REFINE))) return r;
         c->out_ref.count += batch;
     }
-    if (c->power_mode) {           // ang / lvl where refine_kernel has not written them
-        float* const p_ang = c->refine_mode ? nullptr : static_cast<float*>(d_ang);
-        float* const p_lvl = (c->refine_mode && c->power_mode != 2) ? nullptr : static_cast<float*>(d_lvl);
-        r = launch_power(c, batch, p_ang, p_lvl);
-        if (r) return r;
+    if (c->power_mode) {
+        if (const int r = launch_power(c, batch, ang(POWER), lvl(POWER))) return r;
         c->out_pow.count += batch;
     }
-    if (c->beam_mode) {            // the last two launches: ang / lvl where neither refine_kernel nor power_kernel has written them
-        const bool earlier = c->refine_mode || c->power_mode;
-        r = launch_beam_weights(c, batch, earlier ? nullptr : static_cast<float*>(d_ang), earlier ? nullptr : static_cast<float*>(d_lvl));
+    if (c->beam_mode) {
+        int r = launch_beam_weights(c, batch, ang(BEAM), lvl(BEAM));
         if (r == BAZ_MUSIC_OK) r = launch_beam_apply(c, d_in, batch);
         if (r) return r;
         c->out_beam.count += batch;
@@ -2728,17 +2694,13 @@ int process_device_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void
 int process_estimator_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void* d_ang, void* d_lvl, void* d_spec)
 {
     int r = ensure_workspace(c, batch);
+    if (r == BAZ_MUSIC_OK) r = ensure_cov_stages(c, batch);    // (whitening is refused under an estimator: the averaging buffers)
     if (r) return r;
-    if (c->avg_window > 1) {
-        r = ensure_average(c, c->avg_window, batch);
-        if (r) return r;
-        BAZ_REQUIRE(c, dRavg); BAZ_REQUIRE(c, dAvgHist[0]); BAZ_REQUIRE(c, dAvgHist[1]);
-    }
+    if (c->avg_window > 1) { BAZ_REQUIRE(c, dRavg); BAZ_REQUIRE(c, dAvgHist[0]); BAZ_REQUIRE(c, dAvgHist[1]); }
     BAZ_REQUIRE(c, dRefined); BAZ_REQUIRE(c, dR); BAZ_REQUIRE_TAB(c, dRW);
     for (const SideMode& md : side_modes(c))
         if (const int rs = side_refuse(c, md, batch)) return rs;
-    r = launch_cov(c, static_cast<const float*>(d_in), batch, c->dR);
-    if (r == BAZ_MUSIC_OK && c->avg_window > 1) r = launch_average(c, c->dR, batch, c->dRavg);
+    r = launch_cov_stages(c, static_cast<const float*>(d_in), batch);
     if (r) return r;
     float* spec = static_cast<float*>(d_spec);
     if (!spec) {                   // the pickers read the spectrum: the private one when port 2 is not wired
@@ -2746,32 +2708,69 @@ int process_estimator_body(baz_music_ctx* c, const void* d_in, uint32_t batch, v
         if (r) return r;
         spec = c->dPeakSpec;
     }
-    float* ang = static_cast<float*>(d_ang);
-    float* lvl = static_cast<float*>(d_lvl);
-    const size_t entries = (size_t)batch * c->n;
-    if (c->power_mode || c->beam_mode) {   // the pickers' staging, as on the MUSIC sequence
-        r = grow(c, c->dRefAl, c->ref_al_cap, entries * 2);
-        if (r) return r;
-        ang = c->dRefAl;
-        lvl = c->dRefAl + entries;
-    }
-    r = launch_spectrum(c, batch, spec);
+    PickerOut al;
+    r = stage_picker_out(c, batch, d_ang, d_lvl, al);
+    if (r == BAZ_MUSIC_OK) r = launch_spectrum(c, batch, spec);
     if (r) return r;
-    r = c->peak_mode ? launch_peaks(c, batch, ang, lvl, spec) : launch_topn_spec(c, batch, ang, lvl, spec);
+    r = c->peak_mode ? launch_peaks(c, batch, al.ang, al.lvl, spec) : launch_topn_spec(c, batch, al.ang, al.lvl, spec);
+    return r ? r : launch_after_pickers(c, d_in, batch, baz_music_q_stride(batch), d_ang, d_lvl);
+}
+
+// The MUSIC sequence of 2 .. 16 antennas; the contexts of the two other sequences leave it at the top
+int process_device_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void* d_ang, void* d_lvl, void* d_spec)
+{
+    if (c->wide) return process_wide_locked(c, d_in, batch, d_ang, d_lvl, d_spec);
+    if (c->estimator) return process_estimator_body(c, d_in, batch, d_ang, d_lvl, d_spec);
+    int r = ensure_workspace(c, batch);
+    if (r == BAZ_MUSIC_OK) r = reserve_candidates(c, batch);
+    if (r == BAZ_MUSIC_OK) r = ensure_cov_stages(c, batch);
+    if (r == BAZ_MUSIC_OK) r = check_launch_pointers(c);
     if (r) return r;
-    if (c->power_mode) {
-        r = launch_power(c, batch, static_cast<float*>(d_ang), static_cast<float*>(d_lvl));
+    const uint32_t qstride = baz_music_q_stride(batch);
+    // the modes' side outputs: this chunk's go behind those of the call's earlier chunks (order_begin sized the buffers for the call)
+    for (const SideMode& md : side_modes(c))
+        if (const int rs = side_refuse(c, md, batch)) return rs;
+    uint8_t* const ord = c->order_mode ? c->out_ord.chunk<uint8_t>() : nullptr;
+    c->ord_cur = ord;
+    r = launch_frontend(c, d_in, batch, c->dQ, qstride);
+    c->ord_cur = nullptr;
+    if (r) return r;
+    float* spec = static_cast<float*>(d_spec);
+    if (c->peak_mode && !spec) {   // the peak picker reads the spectrum: keep a private one when port 2 is not wired
+        r = grow(c, c->dPeakSpec, c->peak_spec_cap, (size_t)batch * c->res);
         if (r) return r;
-        c->out_pow.count += batch;
+        spec = c->dPeakSpec;
     }
-    if (c->beam_mode) {
-        const bool earlier = c->power_mode != 0;
-        r = launch_beam_weights(c, batch, earlier ? nullptr : static_cast<float*>(d_ang), earlier ? nullptr : static_cast<float*>(d_lvl));
-        if (r == BAZ_MUSIC_OK) r = launch_beam_apply(c, d_in, batch);
+    PickerOut al;
+    r = stage_picker_out(c, batch, d_ang, d_lvl, al);
+    if (r) return r;
+    const ScanDone scan = launch_scan(c, qstride, batch, spec);
+    if (scan.rc) return scan.rc;
+    r = launch_merge(c, scan, batch, al.ang, al.lvl, spec);
+    if (r) return r;
+    c->stat_next_clean = true;     // the merge cleared the next call's statistic counter
+    if (c->peak_mode) {
+        r = launch_peaks(c, batch, al.ang, al.lvl, spec);
         if (r) return r;
-        c->out_beam.count += batch;
     }
-    return BAZ_MUSIC_OK;
+    if (ord) {                     // (0, 0) at and beyond every item's own count: the n - k weakest entries of either picker
+        ProfScope ps(c, BAZ_MUSIC_STAGE_MERGE);
+        hipLaunchKernelGGL(bazorder::order_truncate_kernel, dim3((unsigned)(((size_t)batch * c->n + 255) / 256)), dim3(256), 0, c->stream,
+                           al.ang, al.lvl, ord, batch, c->n);
+        HIP_TRY(c, hipGetLastError());
+        c->out_ord.count += batch;
+    }
+    return launch_after_pickers(c, d_in, batch, qstride, d_ang, d_lvl);
+}
+
+// One launch sequence over `batch` items.  Averaging on: a sequence that fails forgets the history (the stream position the host
+// keeps no longer describes what the device holds); the next item is t = 0.
+int process_device_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, void* d_ang, void* d_lvl,
+                          void* d_spec)
+{
+    const int r = process_device_body(c, d_in, batch, d_ang, d_lvl, d_spec);
+    if (r != BAZ_MUSIC_OK) c->avg_hist = 0;
+    return r;
 }
 
 int ensure_h_al_big(baz_music_ctx* c, size_t floats)
@@ -3342,21 +3341,17 @@ int baz_music_reserve(baz_music_ctx* c, uint32_t max_batch)
         const int rs = grow(c, c->sm.dY, c->sm.y_cap, (size_t)chunk * c->sm.Kp * c->sm.ms);
         return rs ? rs : baz_music_reserve(c->sm.inner, chunk);
     }
-    if (c->avg_window > 1) {     // averaging: both history buffers and the averaged covariances of the largest launch
-        const int ra = ensure_average(c, c->avg_window, c->wide ? std::min(max_batch, wide_pass_items(c)) : max_batch);
-        if (ra) return ra;
-    }
-    if (c->tab.wh_on) {          // whitening: R' of the largest launch (and the pass between the two products at 17 .. 64 antennas)
-        const int rh = ensure_whiten(c, c->wide ? std::min(max_batch, wide_pass_items(c)) : max_batch, true);
-        if (rh) return rh;
-    }
+    // averaging: both history buffers and the averaged covariances of the largest launch; whitening: its R' (and the pass between the
+    // two products at 17 .. 64 antennas)
+    const uint32_t items = largest_launch_items(c, max_batch);
+    int r = ensure_cov_stages(c, items);
+    if (r) return r;
     if (c->wide) {
-        const uint32_t pass = std::min(max_batch, wide_pass_items(c));
-        const int rw = ensure_wide_workspace(c, pass);
+        r = ensure_workspace(c, items);
         // ... and the candidate lists of the matrix-core scan's largest pass (they used to be allocated inside the first process call)
-        return (rw || !c->wide_mfma || c->wide_literal_only) ? rw : ensure_candidates(c, wide_cand_entries(c, pass));
+        return (r || wide_scan_form(c) != WIDE_SCAN_MFMA) ? r : ensure_candidates(c, wide_cand_entries(c, items));
     }
-    int r = ensure_workspace(c, max_batch);
+    r = ensure_workspace(c, max_batch);
     if (r == BAZ_MUSIC_OK && (c->refine_mode || c->power_mode || c->beam_mode)) r = grow(c, c->dRefAl, c->ref_al_cap, (size_t)max_batch * c->n * 2);   // (the pickers' staging)
     if (r == BAZ_MUSIC_OK && c->estimator) r = grow(c, c->dPeakSpec, c->peak_spec_cap, (size_t)max_batch * c->res);   // (the private spectrum of calls without port 2)
 #ifdef BAZ_MUSIC_LAB
@@ -3678,7 +3673,6 @@ int baz_music_debug_cov(baz_music_ctx* c, const void* d_in, uint32_t batch, void
     std::lock_guard<std::mutex> lk(c->mtx);
     DeviceGuard guard(c->device);
     if (c->sm.inner) return BAZ_MUSIC_E_UNSUPPORTED;
-    if (c->wide) return launch_cov_wide(c, static_cast<const float*>(d_in), batch, static_cast<double2*>(d_R));
     if (c->fused_covevd) {   // the product's covariance lives inside the fused kernel: run THAT with its R tap
         int r = ensure_workspace(c, batch);
         if (r) return r;
@@ -4745,7 +4739,7 @@ int calib_mean_locked(baz_music_ctx* c, const void* in, bool in_on_host, uint32_
     const uint32_t ncomp = 2u * c->m * c->m;
     const bazcalib::MeanGeometry G = bazcalib::mean_geometry(batch, c->m);
     const uint32_t chunk = std::min(G.chunk, batch);
-    int r = c->wide ? ensure_wide_workspace(c, chunk) : ensure_workspace(c, chunk);
+    int r = ensure_workspace(c, chunk);
     if (r == BAZ_MUSIC_OK) r = grow(c, c->dCalPart, c->cal_part_cap, (size_t)(G.groups + 1) * ncomp);
     if (r == BAZ_MUSIC_OK && in_on_host) r = grow(c, c->dCalIn, c->cal_in_cap, (size_t)chunk * c->nsamples * 2);
     if (r) return r;
@@ -4758,7 +4752,7 @@ int calib_mean_locked(baz_music_ctx* c, const void* in, bool in_on_host, uint32_
             HIP_TRY(c, hipMemcpyAsync(c->dCalIn, d_in, (size_t)nb * c->nsamples * 8, hipMemcpyHostToDevice, c->stream));
             d_in = c->dCalIn;
         }
-        r = c->wide ? launch_cov_wide(c, d_in, nb, c->dR) : launch_cov(c, d_in, nb, c->dR);
+        r = launch_cov(c, d_in, nb, c->dR);
         if (r) return r;
         ProfScope ps(c, BAZ_MUSIC_STAGE_MERGE);             // (the covariance counts under COV, the two levels of the mean under MERGE)
         const uint32_t runs = (nb + G.run - 1) / G.run;

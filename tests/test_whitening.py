@@ -15,11 +15,7 @@ def _capi():
     return capi
 
 
-def _hpd(m, seed, cond=1.0):
-    """A random Hermitian positive-definite matrix: A A^H / m + cond I."""
-    rng = np.random.default_rng(seed)
-    A = rng.standard_normal((m, m)) + 1j * rng.standard_normal((m, m))
-    return A @ A.conj().T / m + cond * np.eye(m)
+_hpd = wr.hpd
 
 
 # ---- 1. the factor ---------------------------------------------------------------------------------------------------------------------

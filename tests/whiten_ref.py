@@ -17,6 +17,13 @@ from oracle import music_oracle as mo
 U64 = 2.0 ** -53
 
 
+def hpd(m, seed, cond=1.0):
+    """A random Hermitian positive-definite matrix: A A^H / m + cond I."""
+    rng = np.random.default_rng(seed)
+    A = rng.standard_normal((m, m)) + 1j * rng.standard_normal((m, m))
+    return A @ A.conj().T / m + cond * np.eye(m)
+
+
 def hermitian_from_lower(R):
     """(.., m, m): the Hermitian matrix the lower triangle and the real diagonal describe."""
     R = np.asarray(R, dtype=np.complex128)
