@@ -9,7 +9,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libbaz_agc_hip.so")
 
-SYMBOLS = ["baz_agc_create", "baz_agc_destroy", "baz_agc_process", "baz_agc_process_device", "baz_agc_process_device_interleaved", "baz_agc_reset", "baz_agc_debug_selfcheck",
+SYMBOLS = ["baz_agc_create", "baz_agc_destroy", "baz_agc_process", "baz_agc_process_device", "baz_agc_process_device_interleaved", "baz_agc_reset", "baz_agc_debug_selfcheck", "baz_agc_debug_live_buffers",
            "baz_agc_set_stream", "baz_agc_sync", "baz_agc_count", "baz_agc_strerror"]
 
 _vp = ctypes.c_void_p
@@ -52,10 +52,19 @@ def lib():
     L.baz_agc_count.argtypes = [_vp]
     L.baz_agc_debug_selfcheck.restype = ctypes.c_int
     L.baz_agc_debug_selfcheck.argtypes = [_vp, _vp, _vp, _u64, ctypes.POINTER(_u64)]
+    L.baz_agc_debug_live_buffers.restype = None
+    L.baz_agc_debug_live_buffers.argtypes = [ctypes.POINTER(_u64)]
     L.baz_agc_strerror.restype = ctypes.c_char_p
     L.baz_agc_strerror.argtypes = [ctypes.c_int]
     _lib = L
     return L
+
+
+def debug_live_buffers():
+    """(device, page-locked) allocations of the library that are live in this process (baz_agc_debug_live_buffers)."""
+    out = (_u64 * 2)()
+    lib().baz_agc_debug_live_buffers(out)
+    return int(out[0]), int(out[1])
 
 
 class Agc:

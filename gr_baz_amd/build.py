@@ -63,11 +63,11 @@ def build_hip(force=False, verbose=False):
                   os.path.join(CSRC, "whiten_kernels.hip.h"),
                   os.path.join(CSRC, "spectrum_kernels.hip.h"),
                   os.path.join(CSRC, "evd_lds_kernel.inc.h"), os.path.join(CSRC, "cov4_evd_kernel.inc.h"),
-                  os.path.join(INCLUDE, "baz_music_hip.h")]
+                  os.path.join(CSRC, "device_buffer.hip.h"), os.path.join(INCLUDE, "baz_music_hip.h")]
     agc_srcs = [os.path.join(CSRC, "baz_agc_hip.hip"), os.path.join(CSRC, "agc_kernels.hip.h"),
-                os.path.join(INCLUDE, "baz_agc_hip.h")]
+                os.path.join(CSRC, "device_buffer.hip.h"), os.path.join(INCLUDE, "baz_agc_hip.h")]
     rs_srcs = [os.path.join(CSRC, "baz_resamp_hip.hip"), os.path.join(CSRC, "resamp_kernels.hip.h"),
-               os.path.join(INCLUDE, "baz_resamp_hip.h")]
+               os.path.join(CSRC, "device_buffer.hip.h"), os.path.join(INCLUDE, "baz_resamp_hip.h")]
     jobs = []
     for target, srcs, extra in ((HIP_LIB, music_srcs, []), (HIP_LAB_LIB, music_srcs, ["-DBAZ_MUSIC_LAB"]),
                                 (AGC_LIB, agc_srcs, []), (RESAMP_LIB, rs_srcs, [])):

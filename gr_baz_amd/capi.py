@@ -34,7 +34,7 @@ SYMBOLS = [
     "baz_music_host_register", "baz_music_set_host_pinning", "baz_music_host_unregister_all", "baz_music_host_pinned_bytes",
     "baz_music_debug_i8_margin", "baz_music_debug_i8_stats", "baz_music_uses_i8_scan", "baz_music_debug_i8_image",
     "baz_music_debug_i8_nsplit", "baz_music_debug_sort_state", "baz_music_last_retune_ms", "baz_music_debug_table_image", "baz_music_debug_host_table_image",
-    "baz_music_debug_guard_check", "baz_music_debug_guard_active",
+    "baz_music_debug_guard_check", "baz_music_debug_guard_active", "baz_music_debug_live_buffers",
     "baz_music_set_smoothing", "baz_music_get_smoothing", "baz_music_smoothing_check",
     "baz_music_set_order_mode", "baz_music_get_order_mode", "baz_music_last_orders", "baz_music_last_orders_device",
     "baz_music_order_estimate",
@@ -170,6 +170,8 @@ def _bind(L):
                                            ctypes.POINTER(ctypes.c_double)]
     L.baz_music_debug_guard_check.restype = ctypes.c_int
     L.baz_music_debug_guard_check.argtypes = []
+    L.baz_music_debug_live_buffers.restype = None
+    L.baz_music_debug_live_buffers.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     L.baz_music_debug_guard_active.restype = ctypes.c_int
     L.baz_music_debug_guard_active.argtypes = []
     L.baz_music_debug_sort_state.restype = ctypes.c_int
@@ -929,6 +931,16 @@ def guard_active(lab=True):
 def guard_check(lab=True):
     """Guard zones found overwritten since the process started (lab library under BAZ_MUSIC_GUARD=1; synchronises the device); 0 otherwise."""
     return int(lib(lab).baz_music_debug_guard_check())
+
+
+def live_buffers(lab=None):
+    """(device, page-locked) allocations of the library that are live in this process (baz_music_debug_live_buffers).
+    lab=None: the form of the library a Context() loads (the lab form where BAZ_MUSIC_LAB_LIB is set)."""
+    if lab is None:
+        lab = bool(os.environ.get("BAZ_MUSIC_LAB_LIB"))
+    out = (ctypes.c_uint64 * 2)()
+    lib(lab).baz_music_debug_live_buffers(out)
+    return int(out[0]), int(out[1])
 
 
 def q_stride(batch):

@@ -3,6 +3,7 @@
 // No CPU arithmetic fallback: without a gfx950 device baz_agc_create() fails.
 #include "../../include/baz_agc_hip.h"
 #include "agc_kernels.hip.h"
+#include "device_buffer.hip.h"
 
 #include <cmath>
 #include <cstdio>
@@ -12,6 +13,10 @@
 #include <new>
 
 using namespace bazagc;
+using bazbuf::DeviceGuard;
+using bazbuf::drain;
+
+template <typename T> using DevBuf = bazbuf::Buffer<T, bazbuf::Counted<bazbuf::HipDevice, &bazbuf::LiveCounts::device>>;
 
 struct baz_agc_ctx {
     uint32_t nstreams = 0;
@@ -19,12 +24,12 @@ struct baz_agc_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
     uint64_t count = 0;            // _count (identical for every stream of the context)
-    double* d_env = nullptr;       // _env per stream
-    double* d_pw = nullptr;        // per-lane powers of a^IE for the fast path (AgcParams::pw)
-    double2* d_pair = nullptr;     // per-chunk maps
-    double* d_carry = nullptr;     // per-chunk carry-in
+    DevBuf<double> d_env;          // _env per stream
+    DevBuf<double> d_pw;           // per-lane powers of a^IE for the fast path (AgcParams::pw)
+    DevBuf<double2> d_pair;        // per-chunk maps
+    DevBuf<double> d_carry;        // per-chunk carry-in
     size_t chunk_cap = 0;          // chunks per stream the workspace holds
-    float *s_in = nullptr, *s_out = nullptr, *s_env = nullptr, *s_mul = nullptr;   // host-path staging
+    DevBuf<float> s_in, s_out, s_env, s_mul;   // host-path staging (s_in / s_out: two floats per sample)
     size_t s_cap = 0;              // samples (all streams)
     std::mutex mtx;
 };
@@ -36,29 +41,15 @@ namespace {
         if ((call) != hipSuccess) return BAZ_AGC_E_HIP; \
     } while (0)
 
-struct DeviceGuard {
-    int prev = -1;
-    bool changed = false;
-    explicit DeviceGuard(int dev)
-    {
-        if (hipGetDevice(&prev) == hipSuccess && prev != dev) changed = (hipSetDevice(dev) == hipSuccess);
-    }
-    ~DeviceGuard()
-    {
-        if (changed) (void)hipSetDevice(prev);
-    }
-};
-
 int ensure_chunks(baz_agc_ctx* c, size_t nchunks)
 {
     if (nchunks <= c->chunk_cap) return BAZ_AGC_OK;
-    // launches of earlier calls may still use the tables freed below: drain them first (round 6: nothing relies on hipFree synchronising)
-    if (c->chunk_cap) AGC_TRY(hipStreamSynchronize(c->stream));
-    if (c->d_pair) (void)hipFree(c->d_pair);
-    if (c->d_carry) (void)hipFree(c->d_carry);
-    c->d_pair = nullptr; c->d_carry = nullptr; c->chunk_cap = 0;
-    AGC_TRY(hipMalloc((void**)&c->d_pair, nchunks * c->nstreams * sizeof(double2)));
-    AGC_TRY(hipMalloc((void**)&c->d_carry, nchunks * c->nstreams * sizeof(double)));
+    bazbuf::Once once(drain(c));
+    AGC_TRY(c->d_pair.retire(once));
+    AGC_TRY(c->d_carry.retire(once));
+    c->chunk_cap = 0;
+    AGC_TRY(c->d_pair.allocate(nchunks * c->nstreams));
+    AGC_TRY(c->d_carry.allocate(nchunks * c->nstreams));
     c->chunk_cap = nchunks;
     return BAZ_AGC_OK;
 }
@@ -141,7 +132,7 @@ int baz_agc_create(baz_agc_ctx** out, uint32_t nstreams, float rate, float refer
     c->device = dev;
     DeviceGuard guard(dev);
     if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc((void**)&c->d_env, nstreams * sizeof(double)) != hipSuccess ||
+        c->d_env.allocate(nstreams) != hipSuccess ||
         // (hipMemset of device memory may return before the fill has run, and the null stream does not order it against this context's
         // non-blocking stream: the fill goes on the stream that will use the buffer -- round 6, found with the MUSIC library's guard allocator)
         hipMemsetAsync(c->d_env, 0, nstreams * sizeof(double), c->own_stream) != hipSuccess) {
@@ -169,7 +160,7 @@ int baz_agc_create(baz_agc_ctx** out, uint32_t nstreams, float rate, float refer
             h[4 * l + 2] = (double)powl(a4, (long double)l);
             h[4 * l + 3] = 0.0;
         }
-        if (hipMalloc((void**)&c->d_pw, sizeof(h)) != hipSuccess || hipMemcpy(c->d_pw, h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess) {
+        if (c->d_pw.allocate(64 * 4) != hipSuccess || hipMemcpy(c->d_pw, h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess) {
             baz_agc_destroy(c);
             return BAZ_AGC_E_HIP;
         }
@@ -185,17 +176,9 @@ void baz_agc_destroy(baz_agc_ctx* c)
     {
         DeviceGuard guard(c->device);
         if (c->stream) (void)hipStreamSynchronize(c->stream);
-        if (c->d_env) (void)hipFree(c->d_env);
-        if (c->d_pw) (void)hipFree(c->d_pw);
-        if (c->d_pair) (void)hipFree(c->d_pair);
-        if (c->d_carry) (void)hipFree(c->d_carry);
-        if (c->s_in) (void)hipFree(c->s_in);
-        if (c->s_out) (void)hipFree(c->s_out);
-        if (c->s_env) (void)hipFree(c->s_env);
-        if (c->s_mul) (void)hipFree(c->s_mul);
         if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+        delete c;   // (the owners release on the context's device)
     }
-    delete c;
 }
 
 int baz_agc_process_device(baz_agc_ctx* c, const void* d_in, uint64_t n, uint64_t stride, void* d_out, void* d_env,
@@ -225,17 +208,13 @@ int baz_agc_process(baz_agc_ctx* c, const float* in_ri, uint64_t n, uint64_t str
     DeviceGuard guard(c->device);
     const size_t total = (c->nstreams > 1) ? (size_t)stride * c->nstreams : (size_t)n;
     if (total > c->s_cap) {
-        AGC_TRY(hipStreamSynchronize(c->stream));
-        if (c->s_in) (void)hipFree(c->s_in);
-        if (c->s_out) (void)hipFree(c->s_out);
-        if (c->s_env) (void)hipFree(c->s_env);
-        if (c->s_mul) (void)hipFree(c->s_mul);
-        c->s_in = c->s_out = c->s_env = c->s_mul = nullptr;
+        bazbuf::Once once(drain(c));
+        for (auto* b : {&c->s_in, &c->s_out, &c->s_env, &c->s_mul}) AGC_TRY(b->retire(once));
         c->s_cap = 0;
-        AGC_TRY(hipMalloc((void**)&c->s_in, total * 8));
-        AGC_TRY(hipMalloc((void**)&c->s_out, total * 8));
-        AGC_TRY(hipMalloc((void**)&c->s_env, total * 4));
-        AGC_TRY(hipMalloc((void**)&c->s_mul, total * 4));
+        AGC_TRY(c->s_in.allocate(total * 2));
+        AGC_TRY(c->s_out.allocate(total * 2));
+        AGC_TRY(c->s_env.allocate(total));
+        AGC_TRY(c->s_mul.allocate(total));
         c->s_cap = total;
     }
     const uint64_t st = (c->nstreams > 1) ? stride : n;
@@ -285,8 +264,8 @@ int baz_agc_debug_selfcheck(baz_agc_ctx* c, const void* d_a, const void* d_b, ui
     if (!c || !d_a || !d_b || !mismatches || n == 0 || n > 0x7FFFFFFFull * 256ull) return BAZ_AGC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
     DeviceGuard guard(c->device);
-    unsigned long long* d_bad = nullptr;
-    AGC_TRY(hipMalloc((void**)&d_bad, 2 * sizeof(unsigned long long)));
+    DevBuf<unsigned long long> d_bad;
+    AGC_TRY(d_bad.allocate(2));
     hipError_t e = hipMemsetAsync(d_bad, 0, 2 * sizeof(unsigned long long), c->stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(agc_selfcheck_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream,
@@ -296,11 +275,15 @@ int baz_agc_debug_selfcheck(baz_agc_ctx* c, const void* d_a, const void* d_b, ui
     unsigned long long h[2] = {0, 0};
     if (e == hipSuccess) e = hipMemcpyAsync(h, d_bad, sizeof(h), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_bad);
     if (e != hipSuccess) return BAZ_AGC_E_HIP;
     mismatches[0] = h[0];
     mismatches[1] = h[1];
     return BAZ_AGC_OK;
+}
+
+void baz_agc_debug_live_buffers(uint64_t out[2])
+{
+    if (out) bazbuf::g_live.report(out);
 }
 
 const char* baz_agc_strerror(int code)

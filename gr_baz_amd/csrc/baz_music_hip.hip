@@ -22,6 +22,7 @@
 #include "whiten_kernels.hip.h"
 #include "average_kernels.hip.h"
 #include "spectrum_kernels.hip.h"
+#include "device_buffer.hip.h"
 
 #include <algorithm>
 #include <array>
@@ -131,6 +132,17 @@ hipError_t dev_free(void* p)
 #endif
     return hipFree(p);
 }
+
+// ... through their owners (device_buffer.hip.h): a buffer is freed when its owner goes or regrows, nowhere else
+struct GuardedDevice {
+    using status = hipError_t;
+    static hipError_t alloc(void** p, size_t bytes) { return dev_malloc(p, bytes); }
+    static void release(void* p) { (void)dev_free(p); }
+};
+template <typename T> using DevBuf = bazbuf::Buffer<T, bazbuf::Counted<GuardedDevice, &bazbuf::LiveCounts::device>>;
+template <typename T> using PinBuf = bazbuf::PinnedBuffer<T>;
+using bazbuf::DeviceGuard;
+using bazbuf::drain;
 }  // namespace
 
 namespace {
@@ -156,8 +168,7 @@ constexpr int BAZ_MUSIC_NSLOT = 4;
 // functions below; every mode goes through them.
 struct SideOut {
     struct Buf {
-        uint8_t* p = nullptr;
-        size_t cap = 0;              // bytes
+        DevBuf<uint8_t> p;
         size_t item_bytes = 0;       // bytes per item of a call (baz_music_create); 0: this mode has no such buffer
     } buf[2];
     uint32_t count = 0;              // items of the call in flight / the last call recorded so far (the next chunk's offset)
@@ -178,19 +189,18 @@ struct baz_music_ctx {
     uint32_t nclass = 1;     // row classes of the spectrum port: 64 / gcd(res, 64) when res % 4 == 0, else 1
     uint32_t keep_mask = 0;  // low-word mask of the top-n key (bin index lives in the cleared bits)
     // per-range top-n candidate keys (scan_mfma_kernel -> topn_merge_kernel)
-    double* dCand = nullptr;
-    size_t cand_cap = 0;     // entries
+    DevBuf<double> dCand;
     // workspace
-    double2* dR = nullptr;
-    double* dQ = nullptr;
+    DevBuf<double2> dR;
+    DevBuf<double> dQ;
     uint32_t cap = 0;   // items
     // host-fed path (baz_music_process): two device-side slots so that the H2D copy of chunk i+1, the kernels
     // of chunk i and the D2H copy of chunk i-1 overlap on three streams
     struct Slot {
-        float* in = nullptr;
-        float* al = nullptr;         // ang then lvl of the chunk in flight, back to back (2 * cap * n floats)
-        float* h_al = nullptr;       // page-locked host image of `al`: ONE small D2H per chunk, then a CPU copy to the caller
-        float* spec = nullptr;
+        DevBuf<float> in;
+        DevBuf<float> al;            // ang then lvl of the chunk in flight, back to back (2 * cap * n floats)
+        PinBuf<float> h_al;          // page-locked host image of `al`: ONE small D2H per chunk, then a CPU copy to the caller
+        DevBuf<float> spec;
         hipEvent_t h2d = nullptr, comp = nullptr, d2h = nullptr;
         bool busy = false;
         uint32_t pend_done = 0, pend_nb = 0;   // the chunk whose ang / lvl still sit in h_al
@@ -208,18 +218,18 @@ struct baz_music_ctx {
         // steering table as the real bilinear-form table F[bin][m*m] (fp64) in MFMA B-operand order:
         // FB[step][chunk][lane] (double2), see build_FB; one padded step in front of step 0 and one behind the last
         // (the scan's row classes read shifted windows), dFB points at the allocation, step 0 is dFB + fb_step_elems
-        double2* dFB = nullptr;
-        double2* dTB = nullptr;          // raw steering table as fp64 MFMA B-operand image (build_TB), padded like dFB
-        uint4* dCS = nullptr;            // coarse-gated scan, per 16-bin tile: f16 hi/lo pieces of the scaled table (B32, B16) + the fp64 B operand (X)
-        uint4* dIB = nullptr;            // int8-matrix-core scan: digit image of the table (build_i8_image)
-        double* dA2p = nullptr;          // short_form_applies(): ||a||^2 per bin, padded like dFB (fb_steps + 2 steps of 64)
-        float2* dTA = nullptr;           // wide arrays: steering table transposed, [m][res] complex64
-        double* dA2 = nullptr;           // wide arrays: ||a||^2 per bin
-        float2* dRW = nullptr;           // the raw table as delivered, [res][m] complex64: what refine_kernel gathers its steering rows from
+        DevBuf<double2> dFB;
+        DevBuf<double2> dTB;             // raw steering table as fp64 MFMA B-operand image (build_TB), padded like dFB
+        DevBuf<uint4> dCS;               // coarse-gated scan, per 16-bin tile: f16 hi/lo pieces of the scaled table (B32, B16) + the fp64 B operand (X)
+        DevBuf<uint4> dIB;               // int8-matrix-core scan: digit image of the table (build_i8_image)
+        DevBuf<double> dA2p;             // short_form_applies(): ||a||^2 per bin, padded like dFB (fb_steps + 2 steps of 64)
+        DevBuf<float2> dTA;              // wide arrays: steering table transposed, [m][res] complex64
+        DevBuf<double> dA2;              // wide arrays: ||a||^2 per bin
+        DevBuf<float2> dRW;              // the raw table as delivered, [res][m] complex64: what refine_kernel gathers its steering rows from
                                          // (dRaw is the upload staging buffer: the next set_table overwrites it under batches in flight)
 #ifdef BAZ_MUSIC_LAB
-        uint4* dIP = nullptr;            // level-packed int8 operands (m <= 4; shares i8 / i8_ok with dIB: a configuration has one of the two)
-        float* dKT = nullptr;            // float32 table at the sort key's sample bins (sort_kernels.hip.h; m <= 8)
+        DevBuf<uint4> dIP;               // level-packed int8 operands (m <= 4; shares i8 / i8_ok with dIB: a configuration has one of the two)
+        DevBuf<float> dKT;               // float32 table at the sort key's sample bins (sort_kernels.hip.h; m <= 8)
 #endif
         CoarseParams cs = {0.0f, 0.0f, 0.0, 0.0, 1};
         I8Params i8 = {};
@@ -228,27 +238,26 @@ struct baz_music_ctx {
         double refine_below = 0.0;       // literal-form refinement: threshold on d = a^H Q a
         // opt-in noise pre-whitening (whiten_kernels.hip.h): the W this set's images were built under, m x m row-major.  It lives here so
         // that the swap of a retune exchanges (images, W) together: a batch whitens with the W its table was whitened with.
-        double2* dWh = nullptr;          // allocated by the first build with the mode on
+        DevBuf<double2> dWh;             // allocated by the first build with the mode on
         bool wh_on = false;              // the whiten stage runs for batches that read this set
     } tab, shadow;
     std::mutex tab_mtx;              // retunes among themselves (held for a whole baz_music_set_table; never while `mtx` is wanted by work())
     hipStream_t s_tab = nullptr;     // side stream of the table builders (highest priority: they are tiny)
     hipEvent_t ev_swap = nullptr;    // recorded on the launch stream at every swap: batches that still read the retired set
     bool swap_recorded = false;
-    float* dRaw = nullptr;           // the raw fp32 table on the device (resolution x m complex64)
-    float* hRaw = nullptr;           // its page-locked staging copy (the caller's vector may be pageable and short-lived)
-    void* dTabStats = nullptr;       // baztab::TableStats
-    void* hTabStats = nullptr;       // ... page-locked
-    float* h_al_big = nullptr;                          // host-fed zero-copy calls: page-locked ang / lvl image of a whole call
-    size_t h_al_big_cap = 0;                            // floats
+    DevBuf<float> dRaw;              // the raw fp32 table on the device (resolution x m complex64)
+    PinBuf<float> hRaw;              // its page-locked staging copy (the caller's vector may be pageable and short-lived)
+    DevBuf<baztab::TableStats> dTabStats;
+    PinBuf<baztab::TableStats> hTabStats;   // ... page-locked
+    PinBuf<float> h_al_big;                             // host-fed zero-copy calls: page-locked ang / lvl image of a whole call
     double last_retune_ms = 0.0;     // wall time of the last baz_music_set_table, of which ...
     double last_swap_wait_ms = 0.0;  // ... waiting for and holding `mtx`
     int profiling = 0;      // 0 off, 1 every stage, 2 only the dominant (scan) stage
     int lab_variant = 0;
     // literal-form refinement of near-null tiles (literal_tile() inside the scan)
-    double* dG = nullptr;          // noise eigenvectors, item-minor like dQ (cap * m*m * 2 doubles)
+    DevBuf<double> dG;             // noise eigenvectors, item-minor like dQ (cap * m*m * 2 doubles)
     size_t tb_step_elems = 0;      // double2 elements per step of TB (2 * ceil(2m/4) * 64)
-    unsigned long long* dRefined = nullptr;   // statistic: (item, bin) values recomputed, [2]: double-buffered by API call
+    DevBuf<unsigned long long> dRefined;      // statistic: (item, bin) values recomputed, [2]: double-buffered by API call
     int stat_parity = 0;                      // the scan adds to dRefined[stat_parity]; the merge clears the other one
     bool stat_next_clean = true;              // false after a call that failed before its merge ran
     int refine_off = 0;            // lab (BAZ_MUSIC_NO_REFINE=1): projector form everywhere
@@ -256,17 +265,17 @@ struct baz_music_ctx {
     int force_nsplit = 0;          // tests / lab (BAZ_MUSIC_NSPLIT=k): bin ranges per row in the scan, 0 = by batch size
     // wide arrays (17 <= m <= BAZ_MUSIC_MAX_M): the run-time-m kernels of music_wide_kernels.hip.h
     bool wide = false;
-    double2* dGw = nullptr;        // noise eigenvectors, [items][m - n][m]
-    double* dWS = nullptr;         // fp64 strengths, [items][res] (the top-n's input)
-    double2* dSw = nullptr;        // signal eigenvectors, [items][n][m] (the scan's short form where 2n <= m)
+    DevBuf<double2> dGw;           // noise eigenvectors, [items][m - n][m]
+    DevBuf<double> dWS;            // fp64 strengths, [items][res] (the top-n's input)
+    DevBuf<double2> dSw;           // signal eigenvectors, [items][n][m] (the scan's short form where 2n <= m)
     int wide_literal_only = 0;     // lab (BAZ_MUSIC_WIDE_LITERAL=1): no short form in scan_wide_kernel
     uint32_t wide_cov_blocks = 512;
     int wide_cov_mfma = 0;         // 17 <= m <= 32: cov_wide_mfma_kernel, 33 <= m <= 64: cov_wide_pairs_kernel (BAZ_MUSIC_WIDE_COV_MFMA=0: lab)
     int wide_mfma = 0;             // 17 <= m <= 64, n <= 8: the scan on the fp64 matrix core (scan_wide_mfma_kernel; BAZ_MUSIC_WIDE_MFMA=0: lab)
     uint32_t wide_cap = 0;         // items the three buffers above (and dR) hold
-    double* dSs = nullptr;         // short_form_applies(): coefficient vectors of the scan's short form, [2n * 2m][q_stride]
+    DevBuf<double> dSs;            // short_form_applies(): coefficient vectors of the scan's short form, [2n * 2m][q_stride]
     int sig_scan = 1;              // lab / tests: BAZ_MUSIC_SIG_SCAN=0 keeps the projector GEMM
-    uint8_t* dRedo = nullptr;      // [cap] items evd_sub_kernel hands back to the Jacobi
+    DevBuf<uint8_t> dRedo;         // [cap] items evd_sub_kernel hands back to the Jacobi
     int sub_evd = 1;               // signal subspace by orthogonal iteration where n <= 4 (run-time-m kernels: n <= 8) (lab: BAZ_MUSIC_SUB_EVD=0)
     int fused_covevd = 0;          // m = 4, K % 256 == 0: covariance + EVD in one kernel (BAZ_MUSIC_FUSE=0: lab, two kernels)
     uint32_t covevd_blocks = 512u; // grid of cov4_evd_kernel: the workgroups resident at once (2 per CU)
@@ -279,16 +288,16 @@ struct baz_music_ctx {
     int coarse_rg = 4;             // BAZ_MUSIC_COARSE_RG: row groups (x 16 items) per wave, 2 or 4 (lab)
     int coarse_lab = 0;            // BAZ_MUSIC_COARSE_LAB=1: never run an exact tile (cost of the coarse passes alone; wrong results)
     int coarse_stats = 0;          // BAZ_MUSIC_COARSE_STATS=1: count exact tile evaluations (baz_music_debug_coarse_fired)
-    unsigned long long* dMargin = nullptr;   // baz_music_debug_coarse_margin: worst error / allowance (float bits << 32 | where)
+    DevBuf<unsigned long long> dMargin;      // baz_music_debug_coarse_margin: worst error / allowance (float bits << 32 | where)
 #ifdef BAZ_MUSIC_LAB
     // Sorting the items of a batch by their nulls in front of the gated scan (sort_kernels.hip.h), while that scan reports many fired tiles
-    uint16_t* dKeys = nullptr;
-    uint32_t* dHist = nullptr;     // items per key (KEY_BUCKETS)
-    uint32_t* dCursor = nullptr;   // items per range of keys (KEY_BLOCKS)
-    uint32_t* dPerm = nullptr;
+    DevBuf<uint16_t> dKeys;
+    DevBuf<uint32_t> dHist;        // items per key (KEY_BUCKETS)
+    DevBuf<uint32_t> dCursor;      // items per range of keys (KEY_BLOCKS)
+    DevBuf<uint32_t> dPerm;
     uint32_t sort_cap = 0;         // items dKeys / dPerm hold
-    unsigned long long* dFire = nullptr;        // [2] exact evaluations / (row group, tile) pairs walked by the gated scan of the call in flight
-    unsigned long long* hFire = nullptr;        // page-locked [4]: the same of a FINISHED call, [2] = its tag (call number << 1 | sorted), written by its merge
+    DevBuf<unsigned long long> dFire;           // [2] exact evaluations / (row group, tile) pairs walked by the gated scan of the call in flight
+    PinBuf<unsigned long long> hFire;           // page-locked [4]: the same of a FINISHED call, [2] = its tag (call number << 1 | sorted), written by its merge
     unsigned long long* hFireDev = nullptr;     // ... its device address
     unsigned long long fire_calls = 0, fire_seen = 0;
     int sort_mode = 0;             // 0 never (the product), 1 always, -1 adaptive -- LAB builds only (BAZ_MUSIC_SORT).  Measured and not shipped:
@@ -314,10 +323,9 @@ struct baz_music_ctx {
     int refine_nocount = 0;        // lab (BAZ_MUSIC_NO_REFINE_COUNT): the scans do not count the values they recompute
     uint32_t num_cus = 256;        // compute units of the device (launch geometry of scan_i8_kernel)
     int i8_wgs_per_cu[2][2][2] = {{{0, 0}, {0, 0}}, {{0, 0}, {0, 0}}};   // [NMAX > 2][SPEC][VEC4]: resident workgroups per CU (occupancy API, on first use)
-    unsigned long long* dI8Stat = nullptr;   // [0] wave tiles that ran the refined form, [1] wave tiles walked, [2] .. [4] VAL margins
+    DevBuf<unsigned long long> dI8Stat;      // [0] wave tiles that ran the refined form, [1] wave tiles walked, [2] .. [4] VAL margins
     int peak_mode = 0;      // 0: the reference's n strongest bins; 1 (opt-in extension): n strongest local maxima
-    float* dPeakSpec = nullptr;   // internal spectrum when peak mode runs without the spectrum port
-    size_t peak_spec_cap = 0;     // floats
+    DevBuf<float> dPeakSpec;      // internal spectrum when peak mode runs without the spectrum port
     uint32_t call_items = 0;        // items of the last process*() call: what the reader of a mode that was off reports on (the out_* below)
     // Opt-in per-item emitter count (baz_music_set_order_mode; NOT reference behaviour; order_kernels.hip.h).  While
     // order_mode is 0 none of the mode's kernels is launched and nothing below is allocated on the process path.
@@ -326,13 +334,11 @@ struct baz_music_ctx {
     SideOut out_ord;                // one count (uint8) per item; after a call with the mode off every count is n
     bool ord_driven = false;        // an inner context of the smoothing mode: the outer context opens the call (order_begin)
     uint8_t* ord_cur = nullptr;     // where the EVD launched next writes its counts (null: a debug tap -> dOrdTap)
-    uint8_t* dOrdTap = nullptr;     // counts of the debug taps' EVD launches (never read back)
-    size_t ord_tap_cap = 0;
+    DevBuf<uint8_t> dOrdTap;        // counts of the debug taps' EVD launches (never read back)
     // Opt-in sub-bin angle refinement (baz_music_set_refine_mode; NOT reference behaviour; refine_kernels.hip.h).  While
     // refine_mode is 0 its kernel is not launched and nothing below is allocated.
     int refine_mode = 0;            // 0: ang on the grid (the reference); 1: parabolic fit of the null
-    float* dRefAl = nullptr;        // ang | lvl of the chunk in flight as the pickers leave them (refine_kernel writes the caller's)
-    size_t ref_al_cap = 0;          // floats
+    DevBuf<float> dRefAl;           // ang | lvl of the chunk in flight as the pickers leave them (refine_kernel writes the caller's)
     SideOut out_ref;                // delta (double) per (item, slot); after a call with the mode off every offset is 0
     // Opt-in per-emitter Capon power (baz_music_set_power_mode; NOT reference behaviour; power_kernels.hip.h).  While
     // power_mode is 0 its kernel is not launched and nothing below is allocated.  The pickers' staging buffer is dRefAl, shared with
@@ -354,20 +360,16 @@ struct baz_music_ctx {
     bazavg::AvgTable avg_tab = {};  // weights and normalisations of (W, beta): handed to average_kernel by value
     uint32_t avg_hist = 0;          // plain covariances of the stream so far that the history holds: min(t, W - 1), t = items since create / reset
     int avg_parity = 0;             // dAvgHist[avg_parity] is the history the next launch reads; it writes the other one
-    double2* dAvgHist[2] = {nullptr, nullptr};   // [W - 1][m*m] each: the last W - 1 plain covariances, oldest first
-    size_t avg_hist_cap[2] = {0, 0};             // double2 elements
-    double2* dRavg = nullptr;       // averaged covariances of the launch in flight (what the EVD reads while the mode is on)
-    size_t ravg_cap = 0;            // double2 elements
+    DevBuf<double2> dAvgHist[2];    // [W - 1][m*m] each: the last W - 1 plain covariances, oldest first
+    DevBuf<double2> dRavg;          // averaged covariances of the launch in flight (what the EVD reads while the mode is on)
     // Opt-in per-antenna gain / phase calibration (baz_music_set_calibration; NOT reference behaviour; calib_kernels.hip.h).
     // While calib_on is false build_tables_device launches what it launched before the mode existed; hRaw always holds the caller's
     // table.  calib_on / calib_gamma change under `tab_mtx` (they are read by the table builders only).  The estimator's buffers are
     // allocated by its first call.
     bool calib_on = false;
     bazcalib::CalibGamma calib_gamma = {};   // gamma_r, r < m
-    float* dCalIn = nullptr;        // baz_music_calibrate: the chunk's input on the device
-    size_t cal_in_cap = 0;          // floats
-    double* dCalPart = nullptr;     // the runs' partial sums, [groups][2 m^2], then R-bar, [2 m^2]
-    size_t cal_part_cap = 0;        // doubles
+    DevBuf<float> dCalIn;           // baz_music_calibrate: the chunk's input on the device
+    DevBuf<double> dCalPart;        // the runs' partial sums, [groups][2 m^2], then R-bar, [2 m^2]
     // Opt-in noise pre-whitening (baz_music_set_noise_covariance; NOT reference behaviour; whiten_kernels.hip.h).  While it
     // is off build_tables_device and the launch sequences launch what they launched before the mode existed and nothing below is
     // allocated.  wh_on / wh_Rn / hWh change under `tab_mtx` (the table builders read them); wh_want -- the mode is on or being switched
@@ -375,11 +377,9 @@ struct baz_music_ctx {
     bool wh_on = false;
     bool wh_want = false;
     std::vector<double> wh_Rn;      // Rn as given (m*m complex128), for get_noise_covariance
-    double2* hWh = nullptr;         // W, m x m row-major, page-locked: the builders copy it into the set they build
-    double2* dRwh = nullptr;        // R' of the launch in flight (what the EVD reads while the mode is on)
-    size_t rwh_cap = 0;             // double2 elements
-    double2* dWhT = nullptr;        // 17 .. 64 antennas: (W R)^H between the two passes
-    size_t wht_cap = 0;             // double2 elements
+    PinBuf<double2> hWh;            // W, m x m row-major, page-locked: the builders copy it into the set they build
+    DevBuf<double2> dRwh;           // R' of the launch in flight (what the EVD reads while the mode is on)
+    DevBuf<double2> dWhT;           // 17 .. 64 antennas: (W R)^H between the two passes
     // Opt-in choice of estimator (baz_music_set_estimator; NOT reference behaviour; spectrum_kernels.hip.h).  While
     // estimator is 0 none of the mode's kernels is launched and nothing is allocated for it.  With it on the spectrum is written to
     // port 2 or, where that is not wired, to the private spectrum peak mode keeps (dPeakSpec).
@@ -408,12 +408,10 @@ struct baz_music_ctx {
         uint32_t ms = 0, L = 1, Kp = 0;          // subarray size, subarrays, columns of a re-stacked item
         int fb = 0;
         bazsmooth::Perm perm = {};
-        float2* dY = nullptr;                    // re-stacked chunk (BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES)
-        size_t y_cap = 0;                        // complex values
-        float* dX = nullptr;                     // host path: the chunk's input ...
-        float* dAl = nullptr;                    // ... its ang | lvl ...
-        float* dSpec = nullptr;                  // ... and its spectrum on the device
-        size_t x_cap = 0, al_cap = 0, spec_cap = 0;   // floats
+        DevBuf<float2> dY;                       // re-stacked chunk (BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES)
+        DevBuf<float> dX;                        // host path: the chunk's input ...
+        DevBuf<float> dAl;                       // ... its ang | lvl ...
+        DevBuf<float> dSpec;                     // ... and its spectrum on the device
     } sm;
 };
 
@@ -431,19 +429,6 @@ int hip_fail(baz_music_ctx* c, hipError_t e, const char* what)
         hipError_t e__ = (call);                                   \
         if (e__ != hipSuccess) return hip_fail((ctx), e__, #call); \
     } while (0)
-
-struct DeviceGuard {
-    int prev = -1;
-    bool changed = false;
-    explicit DeviceGuard(int dev)
-    {
-        if (hipGetDevice(&prev) == hipSuccess && prev != dev) changed = (hipSetDevice(dev) == hipSuccess);
-    }
-    ~DeviceGuard()
-    {
-        if (changed) (void)hipSetDevice(prev);
-    }
-};
 
 // F[bin][i*m+j]: i==j |a_i|^2 ; i<j Re(conj(a_i) a_j) ; i>j Im(conj(a_j) a_i)  (pair (j,i), j<i).
 // The fp32 table entries are widened exactly (.cc:110-112); the products are fp64.
@@ -745,20 +730,20 @@ bool short_form_in_use(const baz_music_ctx* c)
     return short_form_applies(c->m, c->n) && c->sig_scan && c->dSs && c->tab.dA2p && !c->lab_variant && !i8_active(c);
 }
 
-// The buffers of one workspace grow together, to `items` items (contents are not kept; bytes == 0: the shape has no such buffer).
-// Batches launched earlier may still use the buffers freed here: where one exists the stream is drained first (hipFree happens to
-// synchronise the device today; nothing here relies on it).
-struct WorkBuf { void** p; size_t bytes; };
-int regrow_workspace(baz_music_ctx* c, uint32_t& cap, uint32_t items, std::initializer_list<WorkBuf> bufs)
+// The buffers of one workspace grow together, to `items` items (contents are not kept; n == 0: the shape has no such buffer):
+// one drain where any of them exists, all released, then all allocated.
+template <typename T> struct WorkBuf { DevBuf<T>& buf; size_t n; };
+template <typename T> WorkBuf<T> sized(DevBuf<T>& buf, size_t n) { return {buf, n}; }
+template <typename... T>
+int regrow_workspace(baz_music_ctx* c, uint32_t& cap, uint32_t items, WorkBuf<T>... bufs)
 {
-    bool any = false;
-    for (const WorkBuf& b : bufs) any = any || *b.p;
-    if (any) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (const WorkBuf& b : bufs)
-        if (*b.p) { (void)dev_free(*b.p); *b.p = nullptr; }
+    bazbuf::Once once(drain(c));
+    hipError_t e = hipSuccess;
+    (void)(... && ((e = bufs.buf.retire(once)) == hipSuccess));
+    HIP_TRY(c, e);
     cap = 0;
-    for (const WorkBuf& b : bufs)
-        if (b.bytes) HIP_TRY(c, dev_malloc(b.p, b.bytes));
+    (void)(... && ((e = bufs.n ? bufs.buf.allocate(bufs.n) : hipSuccess) == hipSuccess));
+    HIP_TRY(c, e);
     cap = items;
     return BAZ_MUSIC_OK;
 }
@@ -768,12 +753,8 @@ int ensure_wide_workspace(baz_music_ctx* c, uint32_t items)
 {
     if (items <= c->wide_cap) return BAZ_MUSIC_OK;
     const size_t mm = (size_t)c->m * c->m;
-    return regrow_workspace(c, c->wide_cap, items,
-                            {{(void**)&c->dR, (size_t)items * mm * sizeof(double2)},
-                             {(void**)&c->dGw, (size_t)items * (c->m - c->n) * c->m * sizeof(double2)},
-                             {(void**)&c->dWS, (size_t)items * c->res * sizeof(double)},
-                             {(void**)&c->dSw, (size_t)items * c->n * c->m * sizeof(double2)},
-                             {(void**)&c->dRedo, (size_t)items}});
+    return regrow_workspace(c, c->wide_cap, items, sized(c->dR, items * mm), sized(c->dGw, (size_t)items * (c->m - c->n) * c->m),
+                            sized(c->dWS, (size_t)items * c->res), sized(c->dSw, (size_t)items * c->n * c->m), sized(c->dRedo, items));
 }
 
 // The workspace of the context's shape, for launches of up to `batch` items
@@ -783,12 +764,8 @@ int ensure_workspace(baz_music_ctx* c, uint32_t batch)
     if (batch <= c->cap) return BAZ_MUSIC_OK;
     const uint32_t cap = round_up(batch, 64);
     const size_t mm = (size_t)c->m * c->m;
-    return regrow_workspace(c, c->cap, cap,
-                            {{(void**)&c->dR, (size_t)cap * mm * sizeof(double2)},
-                             {(void**)&c->dQ, (size_t)cap * mm * sizeof(double)},
-                             {(void**)&c->dG, (size_t)cap * mm * 2 * sizeof(double)},
-                             {(void**)&c->dRedo, (size_t)cap},
-                             {(void**)&c->dSs, short_form_applies(c->m, c->n) ? (size_t)cap * 4 * c->n * c->m * sizeof(double) : 0}});
+    return regrow_workspace(c, c->cap, cap, sized(c->dR, cap * mm), sized(c->dQ, cap * mm), sized(c->dG, cap * mm * 2), sized(c->dRedo, cap),
+                            sized(c->dSs, short_form_applies(c->m, c->n) ? (size_t)cap * 4 * c->n * c->m : 0));
 }
 
 struct ProfScope {
@@ -831,26 +808,16 @@ void prof_collect(baz_music_ctx* c)
     }
 }
 
-// Grows one device buffer to `need` elements (contents are not kept).  A buffer that exists is freed behind a drain of the stream:
-// a batch in flight may still read or write it (hipFree happens to synchronise the device today; nothing here relies on it).
-// Nothing in flight can reference a buffer that does not exist yet: the first allocation does not wait.
-template <typename T>
-int grow(baz_music_ctx* c, T*& p, size_t& cap, size_t need)
+// Grows one buffer to `need` elements (contents are not kept): the owner's regrow, drained on the context's stream.
+template <typename Buf>
+int grow(baz_music_ctx* c, Buf& buf, size_t need)
 {
-    if (need <= cap) return BAZ_MUSIC_OK;
-    if (p) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        (void)dev_free(p);
-        p = nullptr;
-    }
-    cap = 0;
-    HIP_TRY(c, dev_malloc((void**)&p, need * sizeof(T)));
-    cap = need;
+    HIP_TRY(c, buf.regrow(need, drain(c)));
     return BAZ_MUSIC_OK;
 }
 
 // ---- the opt-in modes' per-call side outputs (SideOut) --------------------------------------------------------------------------
-int grow_bytes(baz_music_ctx* c, uint8_t*& p, size_t& cap, size_t need) { return grow(c, p, cap, (need + 255) / 256 * 256); }
+int grow_bytes(baz_music_ctx* c, DevBuf<uint8_t>& p, size_t need) { return grow(c, p, (need + 255) / 256 * 256); }
 
 // the four records of a context, each with whether its mode is on now
 struct SideMode { SideOut* out; bool mode_on; };
@@ -863,7 +830,7 @@ std::array<SideMode, 4> side_modes(baz_music_ctx* c)
 int side_grow(baz_music_ctx* c, SideOut& s, uint32_t items)
 {
     for (SideOut::Buf& b : s.buf)
-        if (const int r = grow_bytes(c, b.p, b.cap, (size_t)items * b.item_bytes)) return r;
+        if (const int r = grow_bytes(c, b.p, (size_t)items * b.item_bytes)) return r;
     return BAZ_MUSIC_OK;
 }
 
@@ -899,7 +866,7 @@ int side_refuse(baz_music_ctx* c, const SideMode& md, uint32_t batch)
     if (!md.mode_on) return BAZ_MUSIC_OK;
     bool fits = md.out->on;
     for (const SideOut::Buf& b : md.out->buf)
-        fits = fits && (!b.item_bytes || (b.p && ((size_t)md.out->count + batch) * b.item_bytes <= b.cap));
+        fits = fits && (!b.item_bytes || (b.p && ((size_t)md.out->count + batch) * b.item_bytes <= b.p.cap()));
     return fits ? BAZ_MUSIC_OK : refuse_null(c, nullptr, md.out->what);
 }
 
@@ -924,7 +891,7 @@ int order_args(baz_music_ctx* c, uint32_t batch, OrderArgs& oa)
 {
     oa.ord = c->ord_cur;
     if (!oa.ord) {
-        const int r = grow_bytes(c, c->dOrdTap, c->ord_tap_cap, batch);
+        const int r = grow_bytes(c, c->dOrdTap, batch);
         if (r) return r;
         oa.ord = c->dOrdTap;
     }
@@ -1102,12 +1069,12 @@ int ensure_average(baz_music_ctx* c, uint32_t W, uint32_t items)
 {
     const size_t E = (size_t)c->m * c->m, need = (size_t)(W - 1) * E;
     for (int k = 0; k < 2; ++k) {
-        if (need <= c->avg_hist_cap[k]) continue;
-        const int r = grow(c, c->dAvgHist[k], c->avg_hist_cap[k], need);
+        if (need <= c->dAvgHist[k].cap()) continue;
+        const int r = grow(c, c->dAvgHist[k], need);
         if (r) return r;
         HIP_TRY(c, hipMemsetAsync(c->dAvgHist[k], 0, need * sizeof(double2), c->stream));
     }
-    return items ? grow(c, c->dRavg, c->ravg_cap, (size_t)round_up(items, 64) * E) : BAZ_MUSIC_OK;
+    return items ? grow(c, c->dRavg, (size_t)round_up(items, 64) * E) : BAZ_MUSIC_OK;
 }
 
 // The averaging stage of one launch sequence: dRout[i] = R-bar of item i of `batch` plain covariances dRin, then the history of the
@@ -1119,7 +1086,7 @@ int launch_average(baz_music_ctx* c, const double2* dRin, uint32_t batch, double
     const uint32_t E = c->m * c->m, W = c->avg_window;
     const double2* const Ho = c->dAvgHist[c->avg_parity];
     double2* const Hn = c->dAvgHist[c->avg_parity ^ 1];
-    if (!Ho || !Hn || !dRin || !dRout || c->avg_hist_cap[0] < (size_t)(W - 1) * E || c->avg_hist_cap[1] < (size_t)(W - 1) * E)
+    if (!Ho || !Hn || !dRin || !dRout || c->dAvgHist[0].cap() < (size_t)(W - 1) * E || c->dAvgHist[1].cap() < (size_t)(W - 1) * E)
         return refuse_null(c, nullptr, "dAvgHist / dRavg (ensure_average)");
     // items per lane: 8 up to a window of 8 (R is read at most 15/8 times), 16 beyond (79/16 times at W = 64)
     const uint32_t T = W <= 8 ? 8u : 16u;
@@ -1150,8 +1117,8 @@ double2* cov_in_force(const baz_music_ctx* c)
 int ensure_whiten(baz_music_ctx* c, uint32_t items, bool want_out)
 {
     const size_t need = (size_t)round_up(items, 64) * c->m * c->m;
-    int r = want_out ? grow(c, c->dRwh, c->rwh_cap, need) : BAZ_MUSIC_OK;
-    if (r == BAZ_MUSIC_OK && c->wide) r = grow(c, c->dWhT, c->wht_cap, need);
+    int r = want_out ? grow(c, c->dRwh, need) : BAZ_MUSIC_OK;
+    if (r == BAZ_MUSIC_OK && c->wide) r = grow(c, c->dWhT, need);
     return r;
 }
 
@@ -1173,7 +1140,7 @@ int launch_whiten(baz_music_ctx* c, const double2* dRin, uint32_t batch, double2
     if (const int rn = refuse_null(c, c->tab.dWh, "dWh")) return rn;
     if (!dRin || !dRout) return refuse_null(c, nullptr, "dRwh (ensure_whiten)");
     if (c->wide) {
-        if (c->wht_cap < (size_t)batch * c->m * c->m) return refuse_null(c, nullptr, "dWhT (ensure_whiten)");
+        if (c->dWhT.cap() < (size_t)batch * c->m * c->m) return refuse_null(c, nullptr, "dWhT (ensure_whiten)");
         const size_t lds = (size_t)c->m * (c->m + 1) / 2 * sizeof(double2);
         hipLaunchKernelGGL((bazwhiten::whiten_wide_kernel<true>), dim3(batch), dim3(bazwhiten::WHITEN_THREADS), lds, c->stream, dRin, c->dWhT,
                            c->tab.dWh, c->m);
@@ -1307,7 +1274,7 @@ size_t i8_cand_ranges(const baz_music_ctx* c, uint32_t batch)
     return std::max(exact, std::min<size_t>((size_t)batch * I8_MAX_NSPLIT, (size_t)64u * I8_MAX_ROUNDS * 4u * c->num_cus + (size_t)batch));
 }
 
-int ensure_candidates(baz_music_ctx* c, size_t entries) { return grow(c, c->dCand, c->cand_cap, entries); }
+int ensure_candidates(baz_music_ctx* c, size_t entries) { return grow(c, c->dCand, entries); }
 
 // The coarse-gated scan applies: spectrum port not wired, m <= 8, n <= 4, the table's scale representable.
 bool coarse_applies(const baz_music_ctx* c)
@@ -1361,27 +1328,21 @@ int ensure_sort_workspace(baz_music_ctx* c, uint32_t batch)
 {
     if (c->sort_mode == 0) return BAZ_MUSIC_OK;                   // (nothing of the sorting exists unless it was asked for)
     if (!c->dFire) {
-        HIP_TRY(c, dev_malloc((void**)&c->dFire, 2 * sizeof(unsigned long long)));
+        HIP_TRY(c, c->dFire.allocate(2));
         HIP_TRY(c, hipMemsetAsync(c->dFire, 0, 2 * sizeof(unsigned long long), c->stream));
-        HIP_TRY(c, hipHostMalloc((void**)&c->hFire, 4 * sizeof(unsigned long long), hipHostMallocDefault));
+        HIP_TRY(c, c->hFire.allocate(4));
         std::memset(c->hFire, 0, 4 * sizeof(unsigned long long));
         HIP_TRY(c, hipHostGetDevicePointer((void**)&c->hFireDev, c->hFire, 0));
     }
     if (!c->tab.dKT) return BAZ_MUSIC_OK;
     if (!c->dHist) {
-        HIP_TRY(c, dev_malloc((void**)&c->dHist, bazsort::KEY_BUCKETS * sizeof(uint32_t)));
-        HIP_TRY(c, dev_malloc((void**)&c->dCursor, bazsort::KEY_BUCKETS * sizeof(uint32_t)));
+        HIP_TRY(c, c->dHist.allocate(bazsort::KEY_BUCKETS));
+        HIP_TRY(c, c->dCursor.allocate(bazsort::KEY_BUCKETS));
         HIP_TRY(c, hipMemsetAsync(c->dHist, 0, bazsort::KEY_BUCKETS * sizeof(uint32_t), c->stream));
     }
     if (batch > c->sort_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (c->dKeys) (void)dev_free(c->dKeys);
-        if (c->dPerm) (void)dev_free(c->dPerm);
-        c->dKeys = nullptr; c->dPerm = nullptr; c->sort_cap = 0;
         const uint32_t cap = round_up(batch, 4096);
-        HIP_TRY(c, dev_malloc((void**)&c->dKeys, (size_t)cap * sizeof(uint16_t)));
-        HIP_TRY(c, dev_malloc((void**)&c->dPerm, (size_t)cap * sizeof(uint32_t)));
-        c->sort_cap = cap;
+        if (const int r = regrow_workspace(c, c->sort_cap, cap, sized(c->dKeys, cap), sized(c->dPerm, cap))) return r;
     }
     return BAZ_MUSIC_OK;
 }
@@ -1398,11 +1359,11 @@ bool sort_decide(baz_music_ctx* c, uint32_t batch)
     if (batch < SORT_MIN_BATCH || !c->tab.dKT || !c->hFire || c->m > 4 || c->n > 2 || c->coarse_rg == 2 || c->coarse_lab) return false;
     if (c->sort_mode >= 0) return c->sort_mode != 0;
     ++c->sort_clock;
-    const unsigned long long tag = reinterpret_cast<volatile unsigned long long*>(c->hFire)[2];
+    const unsigned long long tag = static_cast<volatile unsigned long long*>(c->hFire)[2];
     if (tag != c->fire_seen) {
         c->fire_seen = tag;
-        const unsigned long long fired = reinterpret_cast<volatile unsigned long long*>(c->hFire)[0];
-        const unsigned long long walked = reinterpret_cast<volatile unsigned long long*>(c->hFire)[1];
+        const unsigned long long fired = static_cast<volatile unsigned long long*>(c->hFire)[0];
+        const unsigned long long walked = static_cast<volatile unsigned long long*>(c->hFire)[1];
         const double rate = walked ? (double)fired / (double)walked : 0.0;
         if (tag & 1ull) {                              // a sorted call
             if (c->sort_on && rate > 0.6 * c->rate_unsorted) {
@@ -1534,7 +1495,7 @@ ScanDone launch_scan_coarse(baz_music_ctx* c, const ScanCall& s)
     if constexpr (M <= 8 && NMAX <= 4) {
         const CoarseGeom CG = coarse_geometry(c, s.batch);
         ScanDone done{BAZ_MUSIC_OK, SCAN_COARSE, CG.nsplit};
-        if ((size_t)s.batch * CG.nsplit * NMAX > c->cand_cap) return scan_result(c, done, BAZ_MUSIC_E_INVALID);   // reserve_candidates() sized it
+        if ((size_t)s.batch * CG.nsplit * NMAX > c->dCand.cap()) return scan_result(c, done, BAZ_MUSIC_E_INVALID);   // reserve_candidates() sized it
         CoarseLaunch L{CG.groups * CG.nsplit, CG.nphases, CG.nsplit, scan_refine(c, false), c->coarse_stats ? c->dMargin : nullptr};
         auto* kernel = &scan_coarse_kernel<M, NMAX, (M > 4 ? coarse_rg_wide(M, NMAX) : 4), (M > 4 ? 4 : 8)>;
         if constexpr (M <= 4) if (CG.tpp == 4) kernel = &scan_coarse_kernel<M, NMAX, 2, 4>;
@@ -1580,7 +1541,7 @@ ScanDone launch_scan_i8(baz_music_ctx* c, const ScanCall& s)
         }
         const uint32_t nsplit = i8_nsplit(s.batch, c->fb_steps, c->num_cus * (uint32_t)per_cu, c->force_nsplit);
         ScanDone done{BAZ_MUSIC_OK, SCAN_I8, nsplit};
-        if ((size_t)s.batch * nsplit * NMAX > c->cand_cap) return scan_result(c, done, BAZ_MUSIC_E_INVALID);
+        if ((size_t)s.batch * nsplit * NMAX > c->dCand.cap()) return scan_result(c, done, BAZ_MUSIC_E_INVALID);
         const ScanGeom G = scan_geometry(s.batch, c->fb_steps, c->nclass, c->force_nsplit, c->m);     // (its groups: nclass = 1 from m = 6 on)
         I8Launch L{(G.groups / 4) * nsplit, nsplit, scan_n(c), s.spec, scan_refine(c, false), c->dI8Stat, nullptr};
 #ifdef BAZ_MUSIC_LAB
@@ -1624,7 +1585,7 @@ ScanDone launch_scan_i8p(baz_music_ctx* c, const ScanCall& s)
     if constexpr (M <= 4 && NMAX <= 4) {
         const ScanGeom G = scan_geometry(s.batch, c->fb_steps, c->nclass, c->force_nsplit, c->m);
         ScanDone done{BAZ_MUSIC_OK, SCAN_I8P, G.nsplit};
-        if ((size_t)s.batch * G.nsplit * NMAX > c->cand_cap) return scan_result(c, done, BAZ_MUSIC_E_INVALID);
+        if ((size_t)s.batch * G.nsplit * NMAX > c->dCand.cap()) return scan_result(c, done, BAZ_MUSIC_E_INVALID);
         const I8Launch L{G.blocks, G.nsplit, c->n, s.spec, scan_refine(c, false), c->dI8Stat, nullptr};
         auto* kernel = s.vec4 ? &scan_i8p_kernel<M, NMAX, true, true> : &scan_i8p_kernel<M, NMAX, true, false>;
         if constexpr (M == 4 && NMAX == 2) {       // lab (BAZ_MUSIC_I8_ABL): timing ablations (wrong results)
@@ -1664,7 +1625,7 @@ ScanDone launch_scan_fp64(baz_music_ctx* c, const ScanCall& s, bool short_form)
 {
     const ScanGeom G = scan_geometry(s.batch, c->fb_steps, c->nclass, c->force_nsplit, c->m);
     ScanDone done{BAZ_MUSIC_OK, SCAN_FP64, G.nsplit};
-    if ((size_t)s.batch * G.nsplit * NMAX > c->cand_cap) return scan_result(c, done, BAZ_MUSIC_E_INVALID);   // reserve_candidates() sized it
+    if ((size_t)s.batch * G.nsplit * NMAX > c->dCand.cap()) return scan_result(c, done, BAZ_MUSIC_E_INVALID);   // reserve_candidates() sized it
     auto* kernel = scan_fp64_kernel<M, NMAX, 0>(s);
     if constexpr (M >= 6 && NMAX == 2) {
         if (short_form && c->n == 1) kernel = scan_fp64_kernel<M, NMAX, 1>(s);
@@ -1979,49 +1940,32 @@ size_t coarse_image_bytes(const baz_music_ctx* c)
     return ((size_t)(c->cs_tiles + 1) * cs_c_units((int)c->m) + (size_t)c->cs_tiles * CS_X_UNITS * cs_groups((int)c->m)) * 16;
 }
 
-// one set of buffers for the configuration of `c` (what baz_music_create used to allocate in place)
+// One set of buffers for the configuration of `c`.  A failed allocation leaves what it did allocate: the set's owners free it.
 int alloc_table_set(baz_music_ctx* c, TableSet& T)
 {
     const size_t pad_steps = (size_t)c->fb_steps + 2;
+    bool ok = true;
+    const auto want = [&ok](auto& buf, size_t n) { ok = ok && buf.allocate(n) == hipSuccess; };
     if (c->wide) {
-        if (dev_malloc((void**)&T.dTA, (size_t)c->m * c->res * sizeof(float2)) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
-        if (dev_malloc((void**)&T.dA2, (size_t)c->res * sizeof(double)) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
+        want(T.dTA, (size_t)c->m * c->res);
+        want(T.dA2, c->res);
         if (c->wide_mfma) {
-            if (dev_malloc((void**)&T.dTB, pad_steps * c->tb_step_elems * sizeof(double2)) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
-            if (dev_malloc((void**)&T.dA2p, pad_steps * 64 * sizeof(double)) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
+            want(T.dTB, pad_steps * c->tb_step_elems);
+            want(T.dA2p, pad_steps * 64);
         }
-        return BAZ_MUSIC_OK;
+        return ok ? BAZ_MUSIC_OK : BAZ_MUSIC_E_NOMEM;
     }
-    if (dev_malloc((void**)&T.dFB, pad_steps * c->fb_step_elems * sizeof(double2)) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
-    if (dev_malloc((void**)&T.dTB, pad_steps * c->tb_step_elems * sizeof(double2)) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
-    if (dev_malloc((void**)&T.dRW, (size_t)c->res * c->m * sizeof(float2)) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
-    if (c->m <= 8 && dev_malloc((void**)&T.dCS, coarse_image_bytes(c)) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
+    want(T.dFB, pad_steps * c->fb_step_elems);
+    want(T.dTB, pad_steps * c->tb_step_elems);
+    want(T.dRW, (size_t)c->res * c->m);
+    if (c->m <= 8) want(T.dCS, coarse_image_bytes(c) / sizeof(uint4));
 #ifdef BAZ_MUSIC_LAB
-    if (c->m <= 8 && c->sort_mode != 0 &&            // (lab: the sort key's table)
-        dev_malloc((void**)&T.dKT, (size_t)bazsort::key_samples(c->res) * c->m * c->m * sizeof(float)) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
-    if (c->i8p_on && c->m <= 4 && c->n <= 4 && dev_malloc((void**)&T.dIP, i8p_image_bytes(c->fb_steps)) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
+    if (c->m <= 8 && c->sort_mode != 0) want(T.dKT, (size_t)bazsort::key_samples(c->res) * c->m * c->m);   // (lab: the sort key's table)
+    if (c->i8p_on && c->m <= 4 && c->n <= 4) want(T.dIP, i8p_image_bytes(c->fb_steps) / sizeof(uint4));
 #endif
-    if (wants_i8_image(c) && dev_malloc((void**)&T.dIB, i8_image_bytes(c->m, c->fb_steps)) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
-    if (short_form_applies(c->m, c->n) && dev_malloc((void**)&T.dA2p, pad_steps * 64 * sizeof(double)) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
-    return BAZ_MUSIC_OK;
-}
-
-void free_table_set(TableSet& T)
-{
-    if (T.dFB) (void)dev_free(T.dFB);
-    if (T.dTB) (void)dev_free(T.dTB);
-    if (T.dCS) (void)dev_free(T.dCS);
-    if (T.dIB) (void)dev_free(T.dIB);
-#ifdef BAZ_MUSIC_LAB
-    if (T.dIP) (void)dev_free(T.dIP);
-    if (T.dKT) (void)dev_free(T.dKT);
-#endif
-    if (T.dA2p) (void)dev_free(T.dA2p);
-    if (T.dTA) (void)dev_free(T.dTA);
-    if (T.dA2) (void)dev_free(T.dA2);
-    if (T.dRW) (void)dev_free(T.dRW);
-    if (T.dWh) (void)dev_free(T.dWh);
-    T = TableSet();
+    if (wants_i8_image(c)) want(T.dIB, i8_image_bytes(c->m, c->fb_steps) / sizeof(uint4));
+    if (short_form_applies(c->m, c->n)) want(T.dA2p, pad_steps * 64);
+    return ok ? BAZ_MUSIC_OK : BAZ_MUSIC_E_NOMEM;
 }
 
 inline dim3 grid_for(size_t threads) { return dim3((unsigned)((threads + 255) / 256)); }
@@ -2056,28 +2000,28 @@ int build_tables_device(baz_music_ctx* c, TableSet& T)
     HIP_TRY(c, hipHostGetDevicePointer(&zStats, c->hTabStats, 0));
     T.wh_on = c->wh_on;
     if (c->wh_on) {    // opt-in whitening: this set's W first (the stage reads it), then the same read over the link, times gamma where on, times W
-        if (!T.dWh && dev_malloc((void**)&T.dWh, (size_t)m * m * sizeof(double2)) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
+        if (!T.dWh && T.dWh.allocate((size_t)m * m) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
         void* zW = nullptr;
         HIP_TRY(c, hipHostGetDevicePointer(&zW, c->hWh, 0));
         hipLaunchKernelGGL(baztab::copy_words_kernel, dim3((m * m * 2 + 255) / 256), dim3(256), 0, s, static_cast<const unsigned long long*>(zW),
-                           reinterpret_cast<unsigned long long*>(T.dWh), (size_t)m * m * 2);
+                           reinterpret_cast<unsigned long long*>(T.dWh.get()), (size_t)m * m * 2);
         HIP_TRY(c, hipGetLastError());
         const uint32_t bps = bazwhiten::WHITEN_THREADS / m;
         hipLaunchKernelGGL(bazwhiten::table_whiten_kernel, dim3(std::min<uint32_t>(512, (res + bps - 1) / bps)), dim3(bazwhiten::WHITEN_THREADS),
-                           (size_t)m * (m + 1) / 2 * sizeof(double2), s, static_cast<const float2*>(zRaw), reinterpret_cast<float2*>(c->dRaw), res, m,
+                           (size_t)m * (m + 1) / 2 * sizeof(double2), s, static_cast<const float2*>(zRaw), reinterpret_cast<float2*>(c->dRaw.get()), res, m,
                            T.dWh, c->calib_on ? 1 : 0, c->calib_gamma);
     } else if (c->calib_on)   // opt-in calibration: the same read over the link, times gamma (calib_kernels.hip.h); every image below follows from dRaw
         hipLaunchKernelGGL(bazcalib::table_calib_kernel, dim3((unsigned)std::min<size_t>(512, (raw_bytes / 8 + 255) / 256)), dim3(bazcalib::CALIB_THREADS), 0, s,
-                           static_cast<const float2*>(zRaw), reinterpret_cast<float2*>(c->dRaw), raw_bytes / 8, m, c->calib_gamma);
+                           static_cast<const float2*>(zRaw), reinterpret_cast<float2*>(c->dRaw.get()), raw_bytes / 8, m, c->calib_gamma);
     else
         hipLaunchKernelGGL(baztab::copy_words_kernel, dim3((unsigned)std::min<size_t>(512, (raw_bytes / 8 + 255) / 256)), dim3(256), 0, s,
-                           static_cast<const unsigned long long*>(zRaw), reinterpret_cast<unsigned long long*>(c->dRaw), raw_bytes / 8);
+                           static_cast<const unsigned long long*>(zRaw), reinterpret_cast<unsigned long long*>(c->dRaw.get()), raw_bytes / 8);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemsetAsync(c->dTabStats, 0, sizeof(baztab::TableStats), s));
     hipLaunchKernelGGL(baztab::table_stats_kernel, grid_for(res), dim3(256), 0, s, c->dRaw, m, res, c->wide ? 0 : 1,
-                       static_cast<baztab::TableStats*>(c->dTabStats));
+                       c->dTabStats);
     HIP_TRY(c, hipGetLastError());
-    hipLaunchKernelGGL(baztab::copy_words_kernel, dim3(1), dim3(256), 0, s, static_cast<const unsigned long long*>(c->dTabStats),
+    hipLaunchKernelGGL(baztab::copy_words_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<const unsigned long long*>(c->dTabStats.get()),
                        static_cast<unsigned long long*>(zStats), sizeof(baztab::TableStats) / 8);
     HIP_TRY(c, hipGetLastError());
     // (meanwhile: the images that need no scalar)
@@ -2100,11 +2044,11 @@ int build_tables_device(baz_music_ctx* c, TableSet& T)
     }
     if (T.dRW) {    // the set's own copy of the raw table (the refinement's steering rows)
         hipLaunchKernelGGL(baztab::copy_words_kernel, dim3((unsigned)std::min<size_t>(512, (raw_bytes / 8 + 255) / 256)), dim3(256), 0, s,
-                           reinterpret_cast<const unsigned long long*>(c->dRaw), reinterpret_cast<unsigned long long*>(T.dRW), raw_bytes / 8);
+                           reinterpret_cast<const unsigned long long*>(c->dRaw.get()), reinterpret_cast<unsigned long long*>(T.dRW.get()), raw_bytes / 8);
         HIP_TRY(c, hipGetLastError());
     }
     if (T.dTA) {
-        hipLaunchKernelGGL(baztab::build_ta_kernel, grid_for((size_t)m * res), dim3(256), 0, s, reinterpret_cast<const float2*>(c->dRaw), m, res, T.dTA);
+        hipLaunchKernelGGL(baztab::build_ta_kernel, grid_for((size_t)m * res), dim3(256), 0, s, reinterpret_cast<const float2*>(c->dRaw.get()), m, res, T.dTA);
         HIP_TRY(c, hipGetLastError());
     }
 #ifdef BAZ_MUSIC_LAB
@@ -2117,7 +2061,7 @@ int build_tables_device(baz_music_ctx* c, TableSet& T)
     if (T.dCS) HIP_TRY(c, hipMemsetAsync(T.dCS, 0, coarse_image_bytes(c), s));
     if (T.dIB) HIP_TRY(c, hipMemsetAsync(T.dIB, 0, i8_image_bytes(m, steps), s));
     HIP_TRY(c, wait_stream_polling(s));                  // the scalars are on the host
-    const baztab::TableStats st = *static_cast<const baztab::TableStats*>(c->hTabStats);
+    const baztab::TableStats st = *c->hTabStats;
     double fmax, amax2;
     std::memcpy(&fmax, &st.fmax_bits, sizeof(double));
     std::memcpy(&amax2, &st.amax2_bits, sizeof(double));
@@ -2132,7 +2076,7 @@ int build_tables_device(baz_music_ctx* c, TableSet& T)
         if (coarse_params_from(fmax, m, T.cs, FS)) {
             T.cs.lazy = 1;
             if (const char* v = BAZ_LAB_ENV("BAZ_MUSIC_COARSE_LAZY")) T.cs.lazy = atoi(v);            // lab
-            uint8_t* img = reinterpret_cast<uint8_t*>(T.dCS);
+            uint8_t* img = reinterpret_cast<uint8_t*>(T.dCS.get());
             hipLaunchKernelGGL(baztab::build_coarse_c_kernel, grid_for((size_t)(c->cs_tiles + 1) * 16 * m * m), dim3(256), 0, s,
                                c->dRaw, m, res, c->cs_tiles, FS, img);
             HIP_TRY(c, hipGetLastError());
@@ -2157,7 +2101,7 @@ int build_tables_device(baz_music_ctx* c, TableSet& T)
     if (T.dIB && finite) {    // int8-matrix-core scan: the table's digit image
         double sf = 0.0;
         if (i8_params_from(fmax, m, T.i8, sf)) {
-            uint8_t* img = reinterpret_cast<uint8_t*>(T.dIB);
+            uint8_t* img = reinterpret_cast<uint8_t*>(T.dIB.get());
             hipLaunchKernelGGL(baztab::build_i8_kernel, grid_for((size_t)res * i8_nkb((int)m) * 4), dim3(256), 0, s, c->dRaw, m, res,
                                steps, sf, img, img + i8_image_bytes5(m, steps));
             HIP_TRY(c, hipGetLastError());
@@ -2196,13 +2140,10 @@ int retune(baz_music_ctx* c, const float* table_ri, bool first)
     return BAZ_MUSIC_OK;
 }
 
+// the slots' events go and the slots start over (their buffers go with their owners); the caller has drained the stream
 void free_slots(baz_music_ctx* c)
 {
     for (auto& sl : c->slot) {
-        if (sl.in) (void)dev_free(sl.in);
-        if (sl.al) (void)dev_free(sl.al);
-        if (sl.h_al) (void)hipHostFree(sl.h_al);
-        if (sl.spec) (void)dev_free(sl.spec);
         if (sl.h2d) (void)hipEventDestroy(sl.h2d);
         if (sl.comp) (void)hipEventDestroy(sl.comp);
         if (sl.d2h) (void)hipEventDestroy(sl.d2h);
@@ -2215,17 +2156,23 @@ void free_slots(baz_music_ctx* c)
 int ensure_slots(baz_music_ctx* c, uint32_t chunk, bool want_spec)
 {
     if (chunk <= c->s_cap && (!want_spec || c->s_has_spec)) return BAZ_MUSIC_OK;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    bazbuf::Once once(drain(c));
+    for (auto& sl : c->slot) {
+        HIP_TRY(c, sl.in.retire(once));
+        HIP_TRY(c, sl.al.retire(once));
+        HIP_TRY(c, sl.h_al.retire(once));
+        HIP_TRY(c, sl.spec.retire(once));
+    }
     const bool spec = want_spec || c->s_has_spec;
     const uint32_t cap = std::max(chunk, c->s_cap);
     free_slots(c);
     if (!c->s_h2d) HIP_TRY(c, hipStreamCreateWithFlags(&c->s_h2d, hipStreamNonBlocking));
     if (!c->s_d2h) HIP_TRY(c, hipStreamCreateWithFlags(&c->s_d2h, hipStreamNonBlocking));
     for (auto& sl : c->slot) {
-        HIP_TRY(c, dev_malloc((void**)&sl.in, (size_t)cap * c->nsamples * 8));
-        HIP_TRY(c, dev_malloc((void**)&sl.al, (size_t)cap * c->n * 8));
-        HIP_TRY(c, hipHostMalloc((void**)&sl.h_al, (size_t)cap * c->n * 8, hipHostMallocDefault));
-        if (spec) HIP_TRY(c, dev_malloc((void**)&sl.spec, (size_t)cap * c->res * 4));
+        HIP_TRY(c, sl.in.allocate((size_t)cap * c->nsamples * 2));
+        HIP_TRY(c, sl.al.allocate((size_t)cap * c->n * 2));
+        HIP_TRY(c, sl.h_al.allocate((size_t)cap * c->n * 2));
+        if (spec) HIP_TRY(c, sl.spec.allocate((size_t)cap * c->res));
         HIP_TRY(c, hipEventCreateWithFlags(&sl.h2d, hipEventDisableTiming));
         HIP_TRY(c, hipEventCreateWithFlags(&sl.comp, hipEventDisableTiming));
         HIP_TRY(c, hipEventCreateWithFlags(&sl.d2h, hipEventDisableTiming));
@@ -2644,7 +2591,7 @@ int stage_picker_out(baz_music_ctx* c, uint32_t batch, void* d_ang, void* d_lvl,
     out = {static_cast<float*>(d_ang), static_cast<float*>(d_lvl)};
     if (!c->refine_mode && !c->power_mode && !c->beam_mode) return BAZ_MUSIC_OK;
     const size_t entries = (size_t)batch * c->n;
-    if (const int r = grow(c, c->dRefAl, c->ref_al_cap, entries * 2)) return r;
+    if (const int r = grow(c, c->dRefAl, entries * 2)) return r;
     out = {c->dRefAl, c->dRefAl + entries};
     return BAZ_MUSIC_OK;
 }
@@ -2704,7 +2651,7 @@ int process_estimator_body(baz_music_ctx* c, const void* d_in, uint32_t batch, v
     if (r) return r;
     float* spec = static_cast<float*>(d_spec);
     if (!spec) {                   // the pickers read the spectrum: the private one when port 2 is not wired
-        r = grow(c, c->dPeakSpec, c->peak_spec_cap, (size_t)batch * c->res);
+        r = grow(c, c->dPeakSpec, (size_t)batch * c->res);
         if (r) return r;
         spec = c->dPeakSpec;
     }
@@ -2737,7 +2684,7 @@ int process_device_body(baz_music_ctx* c, const void* d_in, uint32_t batch, void
     if (r) return r;
     float* spec = static_cast<float*>(d_spec);
     if (c->peak_mode && !spec) {   // the peak picker reads the spectrum: keep a private one when port 2 is not wired
-        r = grow(c, c->dPeakSpec, c->peak_spec_cap, (size_t)batch * c->res);
+        r = grow(c, c->dPeakSpec, (size_t)batch * c->res);
         if (r) return r;
         spec = c->dPeakSpec;
     }
@@ -2773,15 +2720,13 @@ int process_device_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, vo
     return r;
 }
 
-int ensure_h_al_big(baz_music_ctx* c, size_t floats)
+int ensure_h_al_big(baz_music_ctx* c, size_t floats) { return grow(c, c->h_al_big, floats); }
+
+// baz_music_create: a block of n counters, zero on the context's stream (see there why on that stream)
+int alloc_zeroed(baz_music_ctx* c, DevBuf<unsigned long long>& buf, size_t n)
 {
-    if (floats <= c->h_al_big_cap) return BAZ_MUSIC_OK;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->h_al_big) (void)hipHostFree(c->h_al_big);
-    c->h_al_big = nullptr; c->h_al_big_cap = 0;
-    HIP_TRY(c, hipHostMalloc((void**)&c->h_al_big, floats * sizeof(float), hipHostMallocDefault));
-    c->h_al_big_cap = floats;
-    return BAZ_MUSIC_OK;
+    if (buf.allocate(n) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
+    return hipMemsetAsync(buf, 0, n * sizeof(unsigned long long), c->stream) == hipSuccess ? BAZ_MUSIC_OK : BAZ_MUSIC_E_HIP;
 }
 
 // baz_music_create's last step: both table sets, the builders' side stream and staging buffers, then the first table
@@ -2793,12 +2738,10 @@ int create_tables(baz_music_ctx* c, const float* table_ri)
     if (const char* v = BAZ_LAB_ENV("BAZ_MUSIC_TAB_PRIORITY")) prio = atoi(v) > 0 ? hi : (atoi(v) < 0 ? lo : 0);   // lab: 1 highest, 0 default, -1 lowest
     if (hipStreamCreateWithPriority(&c->s_tab, hipStreamNonBlocking, prio) != hipSuccess) return BAZ_MUSIC_E_HIP;
     if (hipEventCreateWithFlags(&c->ev_swap, hipEventDisableTiming) != hipSuccess) return BAZ_MUSIC_E_HIP;
-    const size_t raw_bytes = (size_t)c->res * c->m * 2 * sizeof(float);
-    if (dev_malloc((void**)&c->dRaw, raw_bytes) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
-    if (hipHostMalloc((void**)&c->hRaw, raw_bytes, hipHostMallocDefault) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
-    if (dev_malloc(&c->dTabStats, sizeof(baztab::TableStats)) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
-    if (hipHostMalloc(&c->hTabStats, sizeof(baztab::TableStats), hipHostMallocDefault) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
-    int r = alloc_table_set(c, c->tab);                   // (a failed allocation leaves what it did allocate in the set: destroy frees it)
+    const size_t raw_floats = (size_t)c->res * c->m * 2;
+    if (c->dRaw.allocate(raw_floats) != hipSuccess || c->hRaw.allocate(raw_floats) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
+    if (c->dTabStats.allocate(1) != hipSuccess || c->hTabStats.allocate(1) != hipSuccess) return BAZ_MUSIC_E_NOMEM;
+    int r = alloc_table_set(c, c->tab);
     if (r == BAZ_MUSIC_OK) r = alloc_table_set(c, c->shadow);
     if (r != BAZ_MUSIC_OK) return r;
     std::lock_guard<std::mutex> tl(c->tab_mtx);
@@ -2931,17 +2874,6 @@ std::vector<float> sub_table(const float* table_ri, uint32_t m, uint32_t res, ui
     return sub;
 }
 
-void free_smoothing_buffers(baz_music_ctx* c)
-{
-    auto& S = c->sm;
-    if (S.dY) (void)dev_free(S.dY);
-    if (S.dX) (void)dev_free(S.dX);
-    if (S.dAl) (void)dev_free(S.dAl);
-    if (S.dSpec) (void)dev_free(S.dSpec);
-    S.dY = nullptr; S.dX = nullptr; S.dAl = nullptr; S.dSpec = nullptr;
-    S.y_cap = S.x_cap = S.al_cap = S.spec_cap = 0;
-}
-
 // items per chunk: the re-stacked chunk stays within BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES (at least one item)
 uint32_t smooth_chunk(const baz_music_ctx* c, uint32_t batch)
 {
@@ -2968,7 +2900,7 @@ int smooth_device_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, voi
 {
     auto& S = c->sm;
     const uint32_t chunk = smooth_chunk(c, batch);
-    int r = grow(c, S.dY, S.y_cap, (size_t)chunk * S.Kp * S.ms);
+    int r = grow(c, S.dY, (size_t)chunk * S.Kp * S.ms);
     for (uint32_t done = 0; done < batch && r == BAZ_MUSIC_OK; done += chunk) {
         const uint32_t nb = std::min(chunk, batch - done);
         r = launch_restack(c, static_cast<const float2*>(d_in) + (size_t)done * c->nsamples, nb);
@@ -2988,9 +2920,9 @@ int smooth_host_locked(baz_music_ctx* c, const float* in_ri, uint32_t batch, flo
 {
     auto& S = c->sm;
     const uint32_t chunk = smooth_chunk(c, batch);
-    int r = grow(c, S.dX, S.x_cap, (size_t)chunk * c->nsamples * 2);
-    if (r == BAZ_MUSIC_OK) r = grow(c, S.dAl, S.al_cap, (size_t)chunk * c->n * 2);
-    if (r == BAZ_MUSIC_OK && spectrum) r = grow(c, S.dSpec, S.spec_cap, (size_t)chunk * c->res);
+    int r = grow(c, S.dX, (size_t)chunk * c->nsamples * 2);
+    if (r == BAZ_MUSIC_OK) r = grow(c, S.dAl, (size_t)chunk * c->n * 2);
+    if (r == BAZ_MUSIC_OK && spectrum) r = grow(c, S.dSpec, (size_t)chunk * c->res);
     if (r) return r;
     for (uint32_t done = 0; done < batch && r == BAZ_MUSIC_OK; done += chunk) {
         const uint32_t nb = std::min(chunk, batch - done);
@@ -3070,8 +3002,8 @@ int baz_music_create(baz_music_ctx** out, uint32_t m, uint32_t n, uint32_t nsamp
     do {
         if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) { r = BAZ_MUSIC_E_HIP; break; }
         c->stream = c->own_stream;
-        // (every fill of a device buffer below is a hipMemsetAsync ON THIS STREAM: hipMemset of device memory may return before the fill has run, and
-        // the null stream orders nothing against a non-blocking stream -- round 6, found when the guard allocator's own prefill raced with a scan)
+        // (every fill of a device buffer below is alloc_zeroed's hipMemsetAsync ON THIS STREAM: hipMemset of device memory may return before the fill has
+        // run, and the null stream orders nothing against a non-blocking stream -- round 6, found when the guard allocator's own prefill raced with a scan)
         c->wide = wide;
         if (wide) {   // run-time-m kernels: only the transposed table and the statistic counters (which stay 0)
             if (resolution > (1u << 20)) { r = BAZ_MUSIC_E_UNSUPPORTED; break; }
@@ -3099,8 +3031,7 @@ int baz_music_create(baz_music_ctx** out, uint32_t m, uint32_t n, uint32_t nsamp
             }
             if (const char* v = BAZ_LAB_ENV("BAZ_MUSIC_SUB_EVD")) c->sub_evd = atoi(v);                   // lab / tests
             if (const char* v = BAZ_LAB_ENV("BAZ_MUSIC_WIDE_LITERAL")) c->wide_literal_only = atoi(v);   // lab / tests
-            if (dev_malloc((void**)&c->dRefined, 2 * sizeof(unsigned long long)) != hipSuccess) { r = BAZ_MUSIC_E_NOMEM; break; }
-            if (hipMemsetAsync(c->dRefined, 0, 2 * sizeof(unsigned long long), c->stream) != hipSuccess) { r = BAZ_MUSIC_E_HIP; break; }
+            if ((r = alloc_zeroed(c, c->dRefined, 2)) != BAZ_MUSIC_OK) break;
             c->wide_cov_mfma = 1;
             c->wide_cov_blocks = 2u * (uint32_t)std::max(1, prop.multiProcessorCount);
             if (const char* v = BAZ_LAB_ENV("BAZ_MUSIC_WIDE_COV_MFMA")) c->wide_cov_mfma = (c->wide_cov_mfma && atoi(v)) ? 1 : 0;   // lab / tests
@@ -3155,8 +3086,7 @@ int baz_music_create(baz_music_ctx** out, uint32_t m, uint32_t n, uint32_t nsamp
         if (const char* v = BAZ_LAB_ENV("BAZ_MUSIC_COARSE_STATS")) c->coarse_stats = atoi(v);          // lab
         if (m <= 8) {
             c->cs_tiles = round_up((resolution + 15) / 16, 8);
-            if (dev_malloc((void**)&c->dMargin, sizeof(unsigned long long)) != hipSuccess) { r = BAZ_MUSIC_E_NOMEM; break; }
-            if (hipMemsetAsync(c->dMargin, 0, sizeof(unsigned long long), c->stream) != hipSuccess) { r = BAZ_MUSIC_E_HIP; break; }
+            if ((r = alloc_zeroed(c, c->dMargin, 1)) != BAZ_MUSIC_OK) break;
         }
         if (const char* v = getenv("BAZ_MUSIC_EXACT")) c->i8_on = atoi(v) ? 0 : 1;                // A/B: 1 = the fp64 scan everywhere
         if (const char* v = BAZ_LAB_ENV("BAZ_MUSIC_I8_ABL")) c->i8_abl = atoi(v);                  // lab
@@ -3171,8 +3101,7 @@ int baz_music_create(baz_music_ctx** out, uint32_t m, uint32_t n, uint32_t nsamp
         wants_i8_stat = wants_i8_stat || (c->i8p_on && m <= 4 && n <= 4);
 #endif
         if (wants_i8_stat) {
-            if (dev_malloc((void**)&c->dI8Stat, 8 * sizeof(unsigned long long)) != hipSuccess) { r = BAZ_MUSIC_E_NOMEM; break; }
-            if (hipMemsetAsync(c->dI8Stat, 0, 8 * sizeof(unsigned long long), c->stream) != hipSuccess) { r = BAZ_MUSIC_E_HIP; break; }
+            if ((r = alloc_zeroed(c, c->dI8Stat, 8)) != BAZ_MUSIC_OK) break;
         }
         {
             // ONE workgroup per CU (4 persistent waves, 8 KiB in flight each = 8 MB chip-wide): measured against 2 / 3 / 4 /
@@ -3183,8 +3112,7 @@ int baz_music_create(baz_music_ctx** out, uint32_t m, uint32_t n, uint32_t nsamp
             if (const char* v = BAZ_LAB_ENV("BAZ_MUSIC_COV_BLOCKS_PER_CU"))    // lab: grid of the covariance kernel
                 if (atoi(v) > 0) c->cov4_resident_blocks = (uint32_t)atoi(v) * (uint32_t)std::max(1, prop.multiProcessorCount);
         }
-        if (dev_malloc((void**)&c->dRefined, 2 * sizeof(unsigned long long)) != hipSuccess) { r = BAZ_MUSIC_E_NOMEM; break; }
-        if (hipMemsetAsync(c->dRefined, 0, 2 * sizeof(unsigned long long), c->stream) != hipSuccess) { r = BAZ_MUSIC_E_HIP; break; }
+        if ((r = alloc_zeroed(c, c->dRefined, 2)) != BAZ_MUSIC_OK) break;
         r = create_tables(c, table_ri);
     } while (0);
     if (r != BAZ_MUSIC_OK) {
@@ -3214,69 +3142,23 @@ int baz_music_create(baz_music_ctx** out, uint32_t m, uint32_t n, uint32_t nsamp
     return BAZ_MUSIC_OK;
 }
 
+// What has an order is here; every device and page-locked buffer goes with its owner when the context is deleted, on its device.
 void baz_music_destroy(baz_music_ctx* c)
 {
     if (!c) return;
-    {
-        DeviceGuard guard(c->device);
-        if (c->sm.inner) baz_music_destroy(c->sm.inner);   // (drains this context's stream: the inner one launches on it)
-        c->sm.inner = nullptr;
-        if (c->stream) (void)hipStreamSynchronize(c->stream);
-        free_smoothing_buffers(c);
-        for (auto& p : c->prof)
-            for (auto e : p.ev) (void)hipEventDestroy(e);
-        if (c->h_al_big) (void)hipHostFree(c->h_al_big);
-        if (c->s_tab) (void)hipStreamSynchronize(c->s_tab);
-        free_table_set(c->tab);
-        free_table_set(c->shadow);
-        if (c->dRaw) (void)dev_free(c->dRaw);
-        if (c->hRaw) (void)hipHostFree(c->hRaw);
-        if (c->dTabStats) (void)dev_free(c->dTabStats);
-        if (c->hTabStats) (void)hipHostFree(c->hTabStats);
-        if (c->ev_swap) (void)hipEventDestroy(c->ev_swap);
-        if (c->s_tab) (void)hipStreamDestroy(c->s_tab);
-#ifdef BAZ_MUSIC_LAB
-        if (c->dKeys) (void)dev_free(c->dKeys);
-        if (c->dPerm) (void)dev_free(c->dPerm);
-        if (c->dHist) (void)dev_free(c->dHist);
-        if (c->dCursor) (void)dev_free(c->dCursor);
-        if (c->dFire) (void)dev_free(c->dFire);
-        if (c->hFire) (void)hipHostFree(c->hFire);
-#endif
-        for (const SideMode& md : side_modes(c))
-            for (SideOut::Buf& b : md.out->buf)
-                if (b.p) (void)dev_free(b.p);
-        if (c->dOrdTap) (void)dev_free(c->dOrdTap);
-        if (c->dRefAl) (void)dev_free(c->dRefAl);
-        if (c->dRavg) (void)dev_free(c->dRavg);
-        if (c->dCalIn) (void)dev_free(c->dCalIn);
-        if (c->dRwh) (void)dev_free(c->dRwh);
-        if (c->dWhT) (void)dev_free(c->dWhT);
-        if (c->hWh) (void)hipHostFree(c->hWh);
-        if (c->dCalPart) (void)dev_free(c->dCalPart);
-        if (c->dAvgHist[0]) (void)dev_free(c->dAvgHist[0]);
-        if (c->dAvgHist[1]) (void)dev_free(c->dAvgHist[1]);
-        if (c->dCand) (void)dev_free(c->dCand);
-        if (c->dR) (void)dev_free(c->dR);
-        if (c->dQ) (void)dev_free(c->dQ);
-        if (c->dG) (void)dev_free(c->dG);
-        if (c->dRedo) (void)dev_free(c->dRedo);
-        if (c->dSs) (void)dev_free(c->dSs);
-        if (c->dI8Stat) (void)dev_free(c->dI8Stat);
-        if (c->dMargin) (void)dev_free(c->dMargin);
-        if (c->dRefined) (void)dev_free(c->dRefined);
-        if (c->dPeakSpec) (void)dev_free(c->dPeakSpec);
-        if (c->dGw) (void)dev_free(c->dGw);
-        if (c->dWS) (void)dev_free(c->dWS);
-        if (c->dSw) (void)dev_free(c->dSw);
-        host_unregister_all_locked(c);
-        free_slots(c);
-        if (c->ev_in) (void)hipEventDestroy(c->ev_in);
-        if (c->ev_out) (void)hipEventDestroy(c->ev_out);
-        if (c->s_h2d) (void)hipStreamDestroy(c->s_h2d);
-        if (c->s_d2h) (void)hipStreamDestroy(c->s_d2h);
-        if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    }
+    DeviceGuard guard(c->device);
+    if (c->sm.inner) baz_music_destroy(c->sm.inner);   // (drains this context's stream: the inner one launches on it)
+    c->sm.inner = nullptr;
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->s_tab) (void)hipStreamSynchronize(c->s_tab);
+    for (auto& p : c->prof)
+        for (auto e : p.ev) (void)hipEventDestroy(e);
+    host_unregister_all_locked(c);
+    free_slots(c);
+    for (hipEvent_t e : {c->ev_swap, c->ev_in, c->ev_out})
+        if (e) (void)hipEventDestroy(e);
+    for (hipStream_t s : {c->s_tab, c->s_h2d, c->s_d2h, c->own_stream})
+        if (s) (void)hipStreamDestroy(s);
     delete c;
 }
 
@@ -3338,7 +3220,7 @@ int baz_music_reserve(baz_music_ctx* c, uint32_t max_batch)
     }
     if (c->sm.inner) {   // smoothing on: the inner context's workspace for one chunk, and the re-stacked chunk
         const uint32_t chunk = smooth_chunk(c, max_batch);
-        const int rs = grow(c, c->sm.dY, c->sm.y_cap, (size_t)chunk * c->sm.Kp * c->sm.ms);
+        const int rs = grow(c, c->sm.dY, (size_t)chunk * c->sm.Kp * c->sm.ms);
         return rs ? rs : baz_music_reserve(c->sm.inner, chunk);
     }
     // averaging: both history buffers and the averaged covariances of the largest launch; whitening: its R' (and the pass between the
@@ -3352,8 +3234,8 @@ int baz_music_reserve(baz_music_ctx* c, uint32_t max_batch)
         return (r || wide_scan_form(c) != WIDE_SCAN_MFMA) ? r : ensure_candidates(c, wide_cand_entries(c, items));
     }
     r = ensure_workspace(c, max_batch);
-    if (r == BAZ_MUSIC_OK && (c->refine_mode || c->power_mode || c->beam_mode)) r = grow(c, c->dRefAl, c->ref_al_cap, (size_t)max_batch * c->n * 2);   // (the pickers' staging)
-    if (r == BAZ_MUSIC_OK && c->estimator) r = grow(c, c->dPeakSpec, c->peak_spec_cap, (size_t)max_batch * c->res);   // (the private spectrum of calls without port 2)
+    if (r == BAZ_MUSIC_OK && (c->refine_mode || c->power_mode || c->beam_mode)) r = grow(c, c->dRefAl, (size_t)max_batch * c->n * 2);   // (the pickers' staging)
+    if (r == BAZ_MUSIC_OK && c->estimator) r = grow(c, c->dPeakSpec, (size_t)max_batch * c->res);   // (the private spectrum of calls without port 2)
 #ifdef BAZ_MUSIC_LAB
     if (r == BAZ_MUSIC_OK && c->sort_mode != 0) r = ensure_sort_workspace(c, max_batch);
 #endif
@@ -3716,9 +3598,9 @@ int baz_music_debug_coarse_margin(baz_music_ctx* c, const void* d_in, uint32_t b
     const uint32_t per_group = big ? 64u * (uint32_t)coarse_rg_wide((int)c->m, 2) : 256u;
     // one range per row: every (item, bin) in both forms
     CoarseLaunch L{(batch + per_group - 1) / per_group, c->cs_tiles / (big ? 4u : 8u), 1u, scan_refine_validation(c), c->dMargin};
-    float* d_dump = nullptr;                     // lab (BAZ_MUSIC_DEBUG_DUMP=<file>): every ratio, [item][bin] float32
+    DevBuf<float> d_dump;                        // lab (BAZ_MUSIC_DEBUG_DUMP=<file>): every ratio, [item][bin] float32
     const char* dump_path = BAZ_LAB_ENV("BAZ_MUSIC_DEBUG_DUMP");
-    if (dump_path && dev_malloc((void**)&d_dump, (size_t)batch * c->res * sizeof(float)) != hipSuccess) d_dump = nullptr;
+    if (dump_path) (void)d_dump.allocate((size_t)batch * c->res);
     if (d_dump) (void)hipMemsetAsync(d_dump, 0, (size_t)batch * c->res * sizeof(float), c->stream);
     L.val_dump = d_dump;
 #define BAZ_VAL(MV, NV, RGV, TPV) coarse_launch<MV>(c, &scan_coarse_kernel<MV, NV, RGV, TPV, true>, L, batch, qstride)
@@ -3741,7 +3623,6 @@ int baz_music_debug_coarse_margin(baz_music_ctx* c, const void* d_in, uint32_t b
         std::vector<float> h((size_t)batch * c->res);
         if (hipMemcpy(h.data(), d_dump, h.size() * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess)
             if (FILE* f = fopen(dump_path, "wb")) { fwrite(h.data(), sizeof(float), h.size(), f); fclose(f); }
-        (void)dev_free(d_dump);
     }
     const unsigned int bits = (unsigned int)(packed >> 32);
     std::memcpy(worst, &bits, sizeof(float));
@@ -4136,6 +4017,12 @@ int baz_music_debug_guard_active(void)
 #endif
 }
 
+// the library's live device / page-locked allocations in this process (device_buffer.hip.h counts them where they are made and released)
+void baz_music_debug_live_buffers(uint64_t out[2])
+{
+    if (out) bazbuf::g_live.report(out);
+}
+
 const char* baz_music_strerror(int code)
 {
     switch (code) {
@@ -4303,7 +4190,7 @@ const void* baz_music_last_orders_device(baz_music_ctx* c)
     if (c->out_ord.on) return c->out_ord.count ? b.p : nullptr;
     if (!c->call_items) return nullptr;
     // the call ran with the mode off: the same bytes as baz_music_last_orders, filled here (nothing on the process path)
-    if (grow_bytes(c, b.p, b.cap, c->call_items) != BAZ_MUSIC_OK) return nullptr;
+    if (grow_bytes(c, b.p, c->call_items) != BAZ_MUSIC_OK) return nullptr;
     if (hipMemsetAsync(b.p, (int)c->n, c->call_items, c->stream) != hipSuccess) return nullptr;
     return b.p;
 }
@@ -4740,8 +4627,8 @@ int calib_mean_locked(baz_music_ctx* c, const void* in, bool in_on_host, uint32_
     const bazcalib::MeanGeometry G = bazcalib::mean_geometry(batch, c->m);
     const uint32_t chunk = std::min(G.chunk, batch);
     int r = ensure_workspace(c, chunk);
-    if (r == BAZ_MUSIC_OK) r = grow(c, c->dCalPart, c->cal_part_cap, (size_t)(G.groups + 1) * ncomp);
-    if (r == BAZ_MUSIC_OK && in_on_host) r = grow(c, c->dCalIn, c->cal_in_cap, (size_t)chunk * c->nsamples * 2);
+    if (r == BAZ_MUSIC_OK) r = grow(c, c->dCalPart, (size_t)(G.groups + 1) * ncomp);
+    if (r == BAZ_MUSIC_OK && in_on_host) r = grow(c, c->dCalIn, (size_t)chunk * c->nsamples * 2);
     if (r) return r;
     BAZ_REQUIRE(c, dR); BAZ_REQUIRE(c, dCalPart);
     const dim3 gx((ncomp + bazcalib::MEAN_THREADS - 1) / bazcalib::MEAN_THREADS);
@@ -4757,7 +4644,7 @@ int calib_mean_locked(baz_music_ctx* c, const void* in, bool in_on_host, uint32_
         ProfScope ps(c, BAZ_MUSIC_STAGE_MERGE);             // (the covariance counts under COV, the two levels of the mean under MERGE)
         const uint32_t runs = (nb + G.run - 1) / G.run;
         hipLaunchKernelGGL(bazcalib::cov_mean_kernel, dim3(gx.x, runs), dim3(bazcalib::MEAN_THREADS), 0, c->stream,
-                           reinterpret_cast<const double*>(c->dR), c->dCalPart + (size_t)(off / G.run) * ncomp, nb, G.run, ncomp, 1.0);
+                           reinterpret_cast<const double*>(c->dR.get()), c->dCalPart + (size_t)(off / G.run) * ncomp, nb, G.run, ncomp, 1.0);
         HIP_TRY(c, hipGetLastError());
     }
     double* const dMean = c->dCalPart + (size_t)G.groups * ncomp;
@@ -4881,7 +4768,7 @@ int baz_music_set_noise_covariance(baz_music_ctx* c, const double* Rn_ri)
         old_want = c->wh_want;
         if (Rn_ri) c->wh_want = true;             // (from here set_beam_mode / set_estimator refuse)
     }
-    if (Rn_ri && !c->hWh && hipHostMalloc((void**)&c->hWh, mm * sizeof(double2), hipHostMallocDefault) != hipSuccess) {
+    if (Rn_ri && !c->hWh && c->hWh.allocate(mm) != hipSuccess) {
         (void)hipGetLastError();
         std::lock_guard<std::mutex> lk(c->mtx);
         c->wh_want = old_want;
@@ -4889,7 +4776,7 @@ int baz_music_set_noise_covariance(baz_music_ctx* c, const double* Rn_ri)
     }
     const bool old_on = c->wh_on;
     std::vector<double> old_W;
-    if (old_on) old_W.assign(reinterpret_cast<const double*>(c->hWh), reinterpret_cast<const double*>(c->hWh) + 2 * mm);
+    if (old_on) old_W.assign(reinterpret_cast<const double*>(c->hWh.get()), reinterpret_cast<const double*>(c->hWh.get()) + 2 * mm);
     c->wh_on = Rn_ri != nullptr;
     if (Rn_ri) std::memcpy(c->hWh, W.data(), 2 * mm * sizeof(double));     // (no builder runs: they hold tab_mtx and wait for their stream)
     const int r = retune(c, nullptr, false);

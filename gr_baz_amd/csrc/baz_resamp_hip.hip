@@ -4,6 +4,7 @@
 // gfx950 device baz_resamp_create() fails.
 #include "../../include/baz_resamp_hip.h"
 #include "resamp_kernels.hip.h"
+#include "device_buffer.hip.h"
 
 #include <cmath>
 #include <cstdio>
@@ -14,6 +15,10 @@
 #include <new>
 
 using namespace bazresamp;
+using bazbuf::DeviceGuard;
+using bazbuf::drain;
+
+template <typename T> using DevBuf = bazbuf::Buffer<T, bazbuf::Counted<bazbuf::HipDevice, &bazbuf::LiveCounts::device>>;
 
 typedef unsigned __int128 u128;
 typedef __int128 i128;
@@ -30,15 +35,13 @@ struct baz_resamp_ctx {
     bool update_mu_adj = false; i128 mu_adj = 0;
     bool exact = true;
     float taps[(RS_NSTEPS + 1) * RS_NTAPS];
-    float* d_taps = nullptr;
-    float *s_in = nullptr, *s_out = nullptr;    // host-path staging (device)
-    size_t s_in_cap = 0, s_out_cap = 0;         // complex samples
+    DevBuf<float> d_taps;
+    DevBuf<float> s_in, s_out;                  // host-path staging (device), two floats per complex sample
     // two-input branch (per-sample ratio input): phase table of the walk, its result, ratio staging
-    uint32_t *d_ii = nullptr, *d_imu = nullptr;
+    DevBuf<uint32_t> d_ii, d_imu;
     size_t walk_cap = 0;                        // outputs
-    WalkResult* d_walk = nullptr;
-    float* s_rr = nullptr;
-    size_t s_rr_cap = 0;                        // floats
+    DevBuf<WalkResult> d_walk;
+    DevBuf<float> s_rr;
     std::mutex mtx;
 };
 
@@ -48,19 +51,6 @@ namespace {
     do {                                                   \
         if ((call) != hipSuccess) return BAZ_RESAMP_E_HIP; \
     } while (0)
-
-struct DeviceGuard {
-    int prev = -1;
-    bool changed = false;
-    explicit DeviceGuard(int dev)
-    {
-        if (hipGetDevice(&prev) == hipSuccess && prev != dev) changed = (hipSetDevice(dev) == hipSuccess);
-    }
-    ~DeviceGuard()
-    {
-        if (changed) (void)hipSetDevice(prev);
-    }
-};
 
 const long double TWO64 = 18446744073709551616.0L;
 
@@ -211,16 +201,15 @@ int64_t process2_device_locked(baz_resamp_ctx* c, const void* d_in, uint64_t in_
     if (ninput > 0xFFFFFFFFull) return BAZ_RESAMP_E_UNSUPPORTED;    // the phase table holds 32-bit input indices
     if ((c->mu >> 64) != 0) return BAZ_RESAMP_E_INVALID;            // d_mu is a fraction between calls
     if (noutput > c->walk_cap) {
-        // launches of earlier calls may still use the tables freed below: drain them first (round 6: nothing relies on hipFree synchronising)
-        if (c->walk_cap) RS_TRY(hipStreamSynchronize(c->stream));
-        if (c->d_ii) (void)hipFree(c->d_ii);
-        if (c->d_imu) (void)hipFree(c->d_imu);
-        c->d_ii = c->d_imu = nullptr; c->walk_cap = 0;
-        RS_TRY(hipMalloc((void**)&c->d_ii, (size_t)noutput * 4));
-        RS_TRY(hipMalloc((void**)&c->d_imu, (size_t)noutput * 4));
+        bazbuf::Once once(drain(c));
+        RS_TRY(c->d_ii.retire(once));
+        RS_TRY(c->d_imu.retire(once));
+        c->walk_cap = 0;
+        RS_TRY(c->d_ii.allocate(noutput));
+        RS_TRY(c->d_imu.allocate(noutput));
         c->walk_cap = noutput;
     }
-    if (!c->d_walk) RS_TRY(hipMalloc((void**)&c->d_walk, sizeof(WalkResult)));
+    if (!c->d_walk) RS_TRY(c->d_walk.allocate(1));
     hipLaunchKernelGGL(resamp_walk_kernel, dim3(1), dim3(256), 0, c->stream, static_cast<const float*>(d_ratio), ninput,
                        noutput, (uint64_t)c->mu, c->d_ii, c->d_imu, c->d_walk);
     RS_TRY(hipGetLastError());
@@ -249,19 +238,9 @@ int64_t process2_device_locked(baz_resamp_ctx* c, const void* d_in, uint64_t in_
 
 int ensure_staging(baz_resamp_ctx* c, size_t nin, size_t nout)
 {
-    if ((nin > c->s_in_cap && c->s_in_cap) || (nout > c->s_out_cap && c->s_out_cap)) RS_TRY(hipStreamSynchronize(c->stream));   // (as above)
-    if (nin > c->s_in_cap) {
-        if (c->s_in) (void)hipFree(c->s_in);
-        c->s_in = nullptr; c->s_in_cap = 0;
-        RS_TRY(hipMalloc((void**)&c->s_in, nin * 8));
-        c->s_in_cap = nin;
-    }
-    if (nout > c->s_out_cap) {
-        if (c->s_out) (void)hipFree(c->s_out);
-        c->s_out = nullptr; c->s_out_cap = 0;
-        RS_TRY(hipMalloc((void**)&c->s_out, nout * 8));
-        c->s_out_cap = nout;
-    }
+    bazbuf::Once once(drain(c));
+    RS_TRY(c->s_in.regrow(nin * 2, once));
+    RS_TRY(c->s_out.regrow(nout * 2, once));
     return BAZ_RESAMP_OK;
 }
 
@@ -298,7 +277,7 @@ int baz_resamp_create(baz_resamp_ctx** out, uint32_t nstreams, double phase_shif
     build_taps(c->taps);
     DeviceGuard guard(dev);
     if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc((void**)&c->d_taps, sizeof(c->taps)) != hipSuccess ||
+        c->d_taps.allocate(sizeof(c->taps) / sizeof(float)) != hipSuccess ||
         hipMemcpy(c->d_taps, c->taps, sizeof(c->taps), hipMemcpyHostToDevice) != hipSuccess) {
         baz_resamp_destroy(c);
         return BAZ_RESAMP_E_HIP;
@@ -315,16 +294,9 @@ void baz_resamp_destroy(baz_resamp_ctx* c)
     {
         DeviceGuard guard(c->device);
         if (c->stream) (void)hipStreamSynchronize(c->stream);
-        if (c->d_taps) (void)hipFree(c->d_taps);
-        if (c->s_in) (void)hipFree(c->s_in);
-        if (c->s_out) (void)hipFree(c->s_out);
-        if (c->d_ii) (void)hipFree(c->d_ii);
-        if (c->d_imu) (void)hipFree(c->d_imu);
-        if (c->d_walk) (void)hipFree(c->d_walk);
-        if (c->s_rr) (void)hipFree(c->s_rr);
         if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+        delete c;   // (the owners release on the context's device)
     }
-    delete c;
 }
 
 int64_t baz_resamp_forecast(const baz_resamp_ctx* c, uint32_t noutput)
@@ -385,12 +357,7 @@ int64_t baz_resamp_process2(baz_resamp_ctx* c, const float* in_ri, uint64_t in_s
     DeviceGuard guard(c->device);
     int r = ensure_staging(c, (size_t)ninput * c->nstreams, (size_t)noutput * c->nstreams);
     if (r) return r;
-    if (ninput > c->s_rr_cap) {
-        if (c->s_rr) (void)hipFree(c->s_rr);
-        c->s_rr = nullptr; c->s_rr_cap = 0;
-        RS_TRY(hipMalloc((void**)&c->s_rr, (size_t)ninput * 4));
-        c->s_rr_cap = ninput;
-    }
+    RS_TRY(c->s_rr.regrow(ninput, drain(c)));
     for (uint32_t s = 0; s < c->nstreams; ++s)
         RS_TRY(hipMemcpyAsync(c->s_in + (size_t)s * ninput * 2, in_ri + (size_t)s * in_stride * 2, (size_t)ninput * 8,
                               hipMemcpyHostToDevice, c->stream));
@@ -491,6 +458,11 @@ int baz_resamp_sync(baz_resamp_ctx* c)
     DeviceGuard guard(c->device);
     RS_TRY(hipStreamSynchronize(c->stream));
     return BAZ_RESAMP_OK;
+}
+
+void baz_resamp_debug_live_buffers(uint64_t out[2])
+{
+    if (out) bazbuf::g_live.report(out);
 }
 
 const char* baz_resamp_strerror(int code)

@@ -13,7 +13,7 @@ SYMBOLS = ["baz_resamp_create", "baz_resamp_destroy", "baz_resamp_forecast", "ba
            "baz_resamp_process_device", "baz_resamp_process2", "baz_resamp_process2_device", "baz_resamp_set_mu", "baz_resamp_set_ratio", "baz_resamp_set_ratio_rational",
            "baz_resamp_set_ratio_ppb", "baz_resamp_adjust", "baz_resamp_mu", "baz_resamp_ratio",
            "baz_resamp_phase_exact", "baz_resamp_taps", "baz_resamp_default_taps", "baz_resamp_set_taps", "baz_resamp_set_stream", "baz_resamp_sync",
-           "baz_resamp_strerror"]
+           "baz_resamp_debug_live_buffers", "baz_resamp_strerror"]
 NTAPS, NSTEPS = 8, 128
 
 _vp = ctypes.c_void_p
@@ -74,10 +74,19 @@ def lib():
     L.baz_resamp_set_stream.argtypes = [_vp, _vp]
     L.baz_resamp_sync.restype = ctypes.c_int
     L.baz_resamp_sync.argtypes = [_vp]
+    L.baz_resamp_debug_live_buffers.restype = None
+    L.baz_resamp_debug_live_buffers.argtypes = [ctypes.POINTER(_u64)]
     L.baz_resamp_strerror.restype = ctypes.c_char_p
     L.baz_resamp_strerror.argtypes = [ctypes.c_int]
     _lib = L
     return L
+
+
+def debug_live_buffers():
+    """(device, page-locked) allocations of the library that are live in this process (baz_resamp_debug_live_buffers)."""
+    out = (_u64 * 2)()
+    lib().baz_resamp_debug_live_buffers(out)
+    return int(out[0]), int(out[1])
 
 
 class Resampler:

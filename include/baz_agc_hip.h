@@ -63,6 +63,9 @@ BAZ_AGC_API const char* baz_agc_strerror(int code);
  * on n device-resident doubles a[i] (sqrt(a[i])) and pairs (a[i] / b[i]), bit for bit, wherever the fast path would take
  * them (2^-400 <= v <= 2^400); mismatches[0] = differing square roots, mismatches[1] = differing quotients. */
 BAZ_AGC_API int baz_agc_debug_selfcheck(baz_agc_ctx* ctx, const void* d_a, const void* d_b, uint64_t n, uint64_t mismatches[2]);
+/* Test tap: the library's live allocations in this process, out[0] device buffers, out[1] page-locked host buffers (every one
+ * has an owner, gr_baz_amd/csrc/device_buffer.hip.h; after the last context is destroyed both are what they were before the first). */
+BAZ_AGC_API void baz_agc_debug_live_buffers(uint64_t out[2]);
 
 #ifdef __cplusplus
 }

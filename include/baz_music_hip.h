@@ -203,6 +203,10 @@ BAZ_MUSIC_API int baz_music_debug_sort_state(baz_music_ctx* ctx, uint64_t out[5]
  *                          `guard_active`: 1 when the guard is on.  Both return 0 in the release library. */
 BAZ_MUSIC_API int baz_music_debug_guard_check(void);
 BAZ_MUSIC_API int baz_music_debug_guard_active(void);
+/*   live buffers : the library's live allocations in this process, out[0] device buffers, out[1] page-locked host buffers (release and lab
+ *                          build alike; no lock).  Every one has an owner (gr_baz_amd/csrc/device_buffer.hip.h): after the last context
+ *                          is destroyed both counts are what they were before the first was created. */
+BAZ_MUSIC_API void baz_music_debug_live_buffers(uint64_t out[2]);
 /*   (host only) the bin ranges per item the int8 scan launches with: whole rounds of the `slots` resident workgroups. */
 BAZ_MUSIC_API uint32_t baz_music_debug_i8_nsplit(uint32_t batch, uint32_t nsteps, uint32_t slots);
 BAZ_MUSIC_API uint32_t baz_music_q_stride(uint32_t batch);

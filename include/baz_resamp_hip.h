@@ -136,6 +136,9 @@ BAZ_RESAMP_API int baz_resamp_set_taps(baz_resamp_ctx* ctx, const float* taps);
 
 BAZ_RESAMP_API int baz_resamp_set_stream(baz_resamp_ctx* ctx, void* hip_stream);
 BAZ_RESAMP_API int baz_resamp_sync(baz_resamp_ctx* ctx);
+/* Test tap: the library's live allocations in this process, out[0] device buffers, out[1] page-locked host buffers (every one
+ * has an owner, gr_baz_amd/csrc/device_buffer.hip.h; after the last context is destroyed both are what they were before the first). */
+BAZ_RESAMP_API void baz_resamp_debug_live_buffers(uint64_t out[2]);
 BAZ_RESAMP_API const char* baz_resamp_strerror(int code);
 
 #ifdef __cplusplus
