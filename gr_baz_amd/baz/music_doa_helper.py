@@ -235,6 +235,30 @@ def _noise_covariance(h):
     return numpy.asarray(rn, dtype=numpy.complex128).reshape(h.m, h.m) if len(rn) else None
 
 
+def _set_beamspace(h, T, normalise):
+    # EXTENSION, no reference counterpart: beamspace MUSIC -- every snapshot projected onto B <= 16 beams, y = T^H x, the estimate on
+    # the table T^H a with every opt-in mode, also for 17 .. 64 antennas, see include/baz_music_hip.h.  Stays in force across
+    # set_frequency() (h.array_response stays the caller's table).
+    if T is None:
+        h.impl.set_beamspace([], 0, False)
+        return
+    t = numpy.asarray(T, dtype=numpy.complex128)
+    if t.ndim != 2 or t.shape[0] != h.m:
+        raise ValueError("T must be an m x B = %d x B complex matrix" % h.m)
+    h.impl.set_beamspace([complex(x) for x in t.reshape(-1)], int(t.shape[1]), bool(normalise))
+
+
+def _set_beamspace_sector(h, bin_lo, bin_count, beams, normalise):
+    # EXTENSION: T = the `beams` principal eigenvectors of sum a a^H over the sector's bins of the table in force; returns the
+    # captured fraction of that sum's trace.
+    return float(h.impl.set_beamspace_sector(int(bin_lo), int(bin_count), int(beams), bool(normalise)))
+
+
+def _beamspace(h):
+    t = h.impl.beamspace()
+    return numpy.asarray(t, dtype=numpy.complex128).reshape(h.m, -1) if len(t) else None
+
+
 def _whiten_next(h, items):
     # EXTENSION: measure the noise covariance from the next `items` items of the stream (a noise-only capture: emitters off,
     # or the antennas terminated) and switch the whitening on with it.
@@ -348,6 +372,21 @@ if _HAVE_GR:
             """The m x m complex128 noise covariance in force, or None while off."""
             return _noise_covariance(self)
 
+        def set_beamspace(self, T, normalise=False):
+            """Opt-in (not reference behaviour): beamspace MUSIC with the m x B matrix `T` (n < B <= min(m, 16); orthonormal
+            columns), also after set_frequency() (None: off).  Opens every opt-in mode to 17 .. 64 antennas.  Not available with
+            set_smoothing, a calibration, noise pre-whitening or the beam mode."""
+            _set_beamspace(self, T, normalise)
+
+        def set_beamspace_sector(self, bin_lo, bin_count, beams, normalise=False):
+            """set_beamspace() with the T designed for the `bin_count` bins from `bin_lo` (wrapping) of the table in force;
+            returns the captured fraction."""
+            return _set_beamspace_sector(self, bin_lo, bin_count, beams, normalise)
+
+        def beamspace(self):
+            """The m x B complex128 matrix T in force, or None while off."""
+            return _beamspace(self)
+
         def whiten_next(self, items):
             """Opt-in (not reference behaviour): measure the noise covariance from the next `items` items (a noise-only capture)
             and apply it.  last_whitening_status(): -1 while waiting for the items, 0 once applied, else the error code."""
@@ -447,6 +486,21 @@ else:
         def noise_covariance(self):
             """The m x m complex128 noise covariance in force, or None while off."""
             return _noise_covariance(self)
+
+        def set_beamspace(self, T, normalise=False):
+            """Opt-in (not reference behaviour): beamspace MUSIC with the m x B matrix `T` (n < B <= min(m, 16); orthonormal
+            columns), also after set_frequency() (None: off).  Opens every opt-in mode to 17 .. 64 antennas.  Not available with
+            set_smoothing, a calibration, noise pre-whitening or the beam mode."""
+            _set_beamspace(self, T, normalise)
+
+        def set_beamspace_sector(self, bin_lo, bin_count, beams, normalise=False):
+            """set_beamspace() with the T designed for the `bin_count` bins from `bin_lo` (wrapping) of the table in force;
+            returns the captured fraction."""
+            return _set_beamspace_sector(self, bin_lo, bin_count, beams, normalise)
+
+        def beamspace(self):
+            """The m x B complex128 matrix T in force, or None while off."""
+            return _beamspace(self)
 
         def whiten_next(self, items):
             """Opt-in (not reference behaviour): measure the noise covariance from the next `items` items (a noise-only capture)

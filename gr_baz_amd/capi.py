@@ -49,6 +49,8 @@ SYMBOLS = [
     "baz_music_set_estimator", "baz_music_get_estimator", "baz_music_spectrum_estimate",
     "baz_music_set_noise_covariance", "baz_music_get_noise_covariance", "baz_music_whitening_factor", "baz_music_whiten_table",
     "baz_music_debug_whiten", "baz_music_mean_covariance", "baz_music_mean_covariance_device",
+    "baz_music_set_beamspace", "baz_music_get_beamspace", "baz_music_debug_beamspace", "baz_music_beamspace_apply",
+    "baz_music_beamspace_design",
 ]
 ESTIMATOR_MUSIC, ESTIMATOR_CAPON, ESTIMATOR_BARTLETT = 0, 1, 2   # BAZ_MUSIC_ESTIMATOR_*
 MAX_AVG_WINDOW = 64                 # BAZ_MUSIC_MAX_AVG_WINDOW
@@ -274,6 +276,16 @@ def _bind(L):
     L.baz_music_mean_covariance.argtypes = [_vp, _f32p, _u32, _f64p]
     L.baz_music_mean_covariance_device.restype = ctypes.c_int
     L.baz_music_mean_covariance_device.argtypes = [_vp, _vp, _u32, _f64p]
+    L.baz_music_set_beamspace.restype = ctypes.c_int
+    L.baz_music_set_beamspace.argtypes = [_vp, _u32, _f64p, ctypes.c_int]
+    L.baz_music_get_beamspace.restype = ctypes.c_int
+    L.baz_music_get_beamspace.argtypes = [_vp, ctypes.POINTER(_u32), _f64p, ctypes.POINTER(ctypes.c_int)]
+    L.baz_music_debug_beamspace.restype = ctypes.c_int
+    L.baz_music_debug_beamspace.argtypes = [_vp, _vp, _u32, _vp]
+    L.baz_music_beamspace_apply.restype = ctypes.c_int
+    L.baz_music_beamspace_apply.argtypes = [_u32, _u32, _f64p, ctypes.c_int, _f32p, _u32, _f32p]
+    L.baz_music_beamspace_design.restype = ctypes.c_int
+    L.baz_music_beamspace_design.argtypes = [_u32, _u32, _f32p, _u32, _u32, _u32, _f64p, _f64p]
     return L
 
 
@@ -659,6 +671,34 @@ class Context:
         """The whitening stage alone on `batch` caller-supplied covariances (device pointers, m*m complex128 each, not overlapping)."""
         self._chk(self._L.baz_music_debug_whiten(self._h, _vp(d_R_in), int(batch), _vp(d_R_out)), "baz_music_debug_whiten")
 
+    def set_beamspace(self, T, normalise=False):
+        """Opt-in extension (not reference behaviour): beamspace MUSIC.  `T` (m x B complex, 2 <= B <= min(m, 16), n < B) projects every
+        snapshot onto B beams, y = T^H x, and an inner context of B antennas on the table T^H a does the rest -- with every opt-in
+        mode, also for 17 .. 64 antennas (include/baz_music_hip.h).  None: off (the default)."""
+        if T is None:
+            self._chk(self._L.baz_music_set_beamspace(self._h, 0, None, 0), "baz_music_set_beamspace")
+            return
+        t = np.ascontiguousarray(np.asarray(T, dtype=np.complex128))
+        if t.ndim != 2 or t.shape[0] != self.m or t.shape[1] < 1:
+            raise ValueError("T must be m x B = %d x B complex" % self.m)
+        self._chk(self._L.baz_music_set_beamspace(self._h, t.shape[1], t.view(np.float64).ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                  1 if normalise else 0), "baz_music_set_beamspace")
+
+    def get_beamspace(self):
+        """(T, normalise) in force (T: m x B complex128, as given), or None while the mode is off."""
+        B, nrm = _u32(0), ctypes.c_int(0)
+        self._chk(self._L.baz_music_get_beamspace(self._h, ctypes.byref(B), None, ctypes.byref(nrm)), "baz_music_get_beamspace")
+        if not B.value:
+            return None
+        t = np.zeros((self.m, B.value), np.complex128)
+        self._chk(self._L.baz_music_get_beamspace(self._h, ctypes.byref(B), t.view(np.float64).ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                  ctypes.byref(nrm)), "baz_music_get_beamspace")
+        return t, bool(nrm.value)
+
+    def debug_beamspace(self, d_in, batch, d_out):
+        """The projection alone: `batch` items (device pointer, m K complex64 each) -> batch K B complex64 at d_out (not overlapping)."""
+        self._chk(self._L.baz_music_debug_beamspace(self._h, _vp(d_in), int(batch), _vp(d_out)), "baz_music_debug_beamspace")
+
     def mean_covariance(self, items):
         """The mean covariance Rbar (m x m complex128) of items ((batch, nsamples) complex64 host array): calibrate()'s Rbar without
         a pilot -- of a noise-only capture, an estimate of the noise covariance for set_noise_covariance.  Blocks; changes nothing."""
@@ -870,6 +910,41 @@ def whiten_table(table, w):
     if r != OK:
         raise ValueError("baz_music_whiten_table: %s" % lib().baz_music_strerror(r).decode())
     return out
+
+
+def beamspace_apply(T, x, normalise=False):
+    """HOST-ONLY: rows of m complex64 (`x`: (..., m); items and tables alike) -> rows of B complex64, y = fl32(T^H x) by the library's
+    definition (the projection kernel's own routine, bit for bit; needs no device).  normalise: every row scaled to unit norm."""
+    t = np.ascontiguousarray(np.asarray(T, dtype=np.complex128))
+    if t.ndim != 2:
+        raise ValueError("beamspace_apply: T must be m x B")
+    v = np.ascontiguousarray(np.asarray(x, dtype=np.complex64))
+    if v.ndim < 1 or v.shape[-1] != t.shape[0]:
+        raise ValueError("beamspace_apply: the last axis of x must hold m = %d entries" % t.shape[0])
+    cols = v.size // t.shape[0]
+    out = np.zeros(v.shape[:-1] + (t.shape[1],), np.complex64)
+    r = lib().baz_music_beamspace_apply(t.shape[0], t.shape[1], t.view(np.float64).ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                        1 if normalise else 0, v.view(np.float32).ctypes.data_as(_f32p), cols,
+                                        out.view(np.float32).ctypes.data_as(_f32p))
+    if r != OK:
+        raise ValueError("baz_music_beamspace_apply: %s" % lib().baz_music_strerror(r).decode())
+    return out
+
+
+def beamspace_design(table, bin_lo, bin_count, B):
+    """HOST-ONLY: (T, captured) for the sector of `bin_count` bins from `bin_lo` (wrapping) of `table` (resolution x m): T (m x B
+    complex128) = the B principal eigenvectors of sum a a^H over the sector, orthonormal; captured = their share of the trace."""
+    t = np.ascontiguousarray(np.asarray(table, dtype=np.complex64))
+    if t.ndim != 2 or not t.size:
+        raise ValueError("beamspace_design: table must be resolution x m")
+    if int(B) < 0 or int(bin_lo) < 0 or int(bin_count) < 0:
+        raise ValueError("beamspace_design: negative argument")
+    T, cap = np.zeros((t.shape[1], max(int(B), 1)), np.complex128), ctypes.c_double(0.0)
+    r = lib().baz_music_beamspace_design(t.shape[1], t.shape[0], t.view(np.float32).ctypes.data_as(_f32p), int(bin_lo), int(bin_count),
+                                         int(B), T.view(np.float64).ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.byref(cap))
+    if r != OK:
+        raise ValueError("baz_music_beamspace_design: %s" % lib().baz_music_strerror(r).decode())
+    return T, float(cap.value)
 
 
 def calibration_estimate(rbar, ref):

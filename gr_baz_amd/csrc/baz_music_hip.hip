@@ -20,6 +20,7 @@
 #include "beam_kernels.hip.h"
 #include "calib_kernels.hip.h"
 #include "whiten_kernels.hip.h"
+#include "beamspace_kernels.hip.h"
 #include "average_kernels.hip.h"
 #include "spectrum_kernels.hip.h"
 #include "device_buffer.hip.h"
@@ -403,8 +404,18 @@ struct baz_music_ctx {
     // set, every process* call re-stacks its items (smoothing_kernels.hip.h) into `dY` and runs them through `inner`, a context of
     // shape (ms, n, ms K', res) on the first ms columns of the table, launching on this context's stream.  Null: off -- none of the
     // mode's code runs and every other member keeps the reference's behaviour.  Changed under `tab_mtx` + `mtx`.
+    //
+    // The record is "a front-end with an inner context": the opt-in beamspace mode (baz_music_set_beamspace; beamspace_kernels.hip.h,
+    // DESIGN.md 8k) is the same construction with a projection kernel where the gather is (kind == FRONT_BEAMSPACE: ms = B beams,
+    // Kp = K, the inner context of shape (B, n, B K, res) on the table T^H a).  The two kinds exclude each other; what every forwarder
+    // below does for `inner` serves both.
+    enum { FRONT_SMOOTHING = 0, FRONT_BEAMSPACE = 1 };
     struct Smoothing {
         baz_music_ctx* inner = nullptr;
+        int kind = FRONT_SMOOTHING;              // which front-end feeds `inner` (meaningful while it is set)
+        int bs_norm = 0;                         // beamspace: rows of the table T^H a scaled to unit norm
+        std::vector<double> bs_T;                // beamspace: T as given (m x B complex128), for get_beamspace and retunes
+        DevBuf<double2> dTc;                     // beamspace: conj(T), [m][B], what beamspace_kernel reads
         uint32_t ms = 0, L = 1, Kp = 0;          // subarray size, subarrays, columns of a re-stacked item
         int fb = 0;
         bazsmooth::Perm perm = {};
@@ -2753,6 +2764,71 @@ int create_tables(baz_music_ctx* c, const float* table_ri)
     return r;
 }
 
+// ---- opt-in beamspace front-end (baz_music_set_beamspace; beamspace_kernels.hip.h) ------------------------------------------------
+inline bool beamspace_on(const baz_music_ctx* c) { return c->sm.inner && c->sm.kind == baz_music_ctx::FRONT_BEAMSPACE; }
+
+// conj(T) of an m x B complex128 T, row-major [antenna][beam]: the operand of every routine of beamspace_kernels.hip.h
+std::vector<double2> beamspace_conj(const double* T_ri, uint32_t m, uint32_t B)
+{
+    std::vector<double2> tc((size_t)m * B);
+    for (size_t e = 0; e < tc.size(); ++e) tc[e] = make_double2(T_ri[2 * e], -T_ri[2 * e + 1]);
+    return tc;
+}
+
+// finite entries and no all-zero column
+bool beamspace_T_ok(const double* T_ri, uint32_t m, uint32_t B)
+{
+    for (size_t i = 0; i < (size_t)2 * m * B; ++i)
+        if (!(T_ri[i] - T_ri[i] == 0.0)) return false;
+    for (uint32_t b = 0; b < B; ++b) {
+        bool any = false;
+        for (uint32_t r = 0; r < m && !any; ++r) any = T_ri[2 * ((size_t)r * B + b)] != 0.0 || T_ri[2 * ((size_t)r * B + b) + 1] != 0.0;
+        if (!any) return false;
+    }
+    return true;
+}
+
+// `columns` rows of m complex64 -> rows of B complex64 on the host (the definition's own routine)
+void beamspace_apply_host(uint32_t m, uint32_t B, const double* T_ri, int normalise, const float* in_ri, size_t columns, float* out_ri)
+{
+    const std::vector<double2> tc = beamspace_conj(T_ri, m, B);
+    std::vector<double> s((size_t)2 * B);
+    for (size_t c = 0; c < columns; ++c)
+        bazbeamspace::beamspace_row(tc.data(), m, B, reinterpret_cast<const float2*>(in_ri) + c * m, normalise, s.data(),
+                                    reinterpret_cast<float2*>(out_ri) + c * B);
+}
+
+// the inner context's table a' = T^H a under the T in force (tab_mtx held: sm changes under tab_mtx + mtx)
+std::vector<float> beamspace_table(const baz_music_ctx* c, const float* table_ri)
+{
+    std::vector<float> proj((size_t)c->res * c->sm.ms * 2);
+    beamspace_apply_host(c->m, c->sm.ms, c->sm.bs_T.data(), c->sm.bs_norm, table_ri, c->res, proj.data());
+    return proj;
+}
+
+template <int B>
+int launch_beamspace_t(baz_music_ctx* c, const float2* d_in, uint32_t columns, float2* d_out)
+{
+    const uint32_t tiles = (columns + bazbeamspace::BS_TILE - 1u) / bazbeamspace::BS_TILE;
+    const uint32_t blocks = std::min<uint32_t>(tiles, 3u * c->num_cus);      // three workgroups fit a CU's LDS at m = 64, B = 16
+    hipLaunchKernelGGL((bazbeamspace::beamspace_kernel<B>), dim3(blocks), dim3(bazbeamspace::BS_THREADS), bazbeamspace::bs_lds_bytes(c->m, B),
+                       c->stream, d_in, d_out, c->sm.dTc.get(), c->m, columns);
+    HIP_TRY(c, hipGetLastError());
+    return BAZ_MUSIC_OK;
+}
+
+// the projection of `columns` snapshots (c->mtx held, the mode on)
+int launch_beamspace(baz_music_ctx* c, const float2* d_in, uint32_t columns, float2* d_out)
+{
+    if (!c->sm.dTc || c->sm.ms > c->m) return BAZ_MUSIC_E_INVALID;
+#define BAZ_CALL(B) launch_beamspace_t<B>(c, d_in, columns, d_out)
+    switch (c->sm.ms) {
+        BAZ_M_CASES(BAZ_CALL)
+        default: return BAZ_MUSIC_E_UNSUPPORTED;
+    }
+#undef BAZ_CALL
+}
+
 // ---- opt-in forward-backward averaging / spatial smoothing (baz_music_set_smoothing) ------------------------------------------
 // Structure checks on the fp32 table (include/baz_music_hip.h documents them).  Every product is formed in fp64 from the fp32
 // entries; a relation holds at a bin when its residual is at most SMOOTH_TOL times the bin's scale s = max_k |a_k|^2.
@@ -2884,6 +2960,7 @@ uint32_t smooth_chunk(const baz_music_ctx* c, uint32_t batch)
 int launch_restack(baz_music_ctx* c, const void* d_in, uint32_t nb)
 {
     auto& S = c->sm;
+    if (S.kind == baz_music_ctx::FRONT_BEAMSPACE) return launch_beamspace(c, static_cast<const float2*>(d_in), nb * c->K, S.dY);
     bazsmooth::RestackGeom g;
     g.m = c->m; g.ms = S.ms; g.K = c->K; g.L = S.L; g.per_item = S.Kp * S.ms; g.fb = (uint32_t)S.fb;
     const uint32_t total = nb * g.per_item;     // <= BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES / 8 (or one item, < 2^31: set_smoothing)
@@ -3168,6 +3245,13 @@ int baz_music_set_table(baz_music_ctx* c, const float* table_ri)
     std::lock_guard<std::mutex> tl(c->tab_mtx);   // one retune at a time; work() is held up for the pointer exchange only (retune())
     DeviceGuard guard(c->device);
     if (!c->sm.inner) return retune(c, table_ri, false);
+    if (c->sm.kind == baz_music_ctx::FRONT_BEAMSPACE) {   // beamspace on: a' of the new table under the T in force, forwarded
+        const std::vector<float> proj = beamspace_table(c, table_ri);
+        const int rb = retune(c, table_ri, false);
+        if (rb != BAZ_MUSIC_OK) return rb;
+        std::lock_guard<std::mutex> lk(c->mtx);
+        return baz_music_set_table(c->sm.inner, proj.data());
+    }
     // smoothing on: the new table must keep the mode's premise, else nothing changes
     bazsmooth::Perm perm = {};
     if (smoothing_check(c->m, c->res, table_ri, c->sm.ms, c->sm.fb, perm.p) != BAZ_MUSIC_OK) return BAZ_MUSIC_E_INVALID;
@@ -3816,6 +3900,8 @@ size_t baz_music_debug_table_image(baz_music_ctx* c, int which, void* out, size_
 {
     if (!c) return 0;
     std::lock_guard<std::mutex> lk(c->mtx);
+    if (which >= BAZ_MUSIC_TABLE_IMAGE_INNER)   // beamspace on: the images of the projected table, held by the inner context
+        return beamspace_on(c) ? baz_music_debug_table_image(c->sm.inner, which - BAZ_MUSIC_TABLE_IMAGE_INNER, out, out_bytes) : 0;
     DeviceGuard guard(c->device);
     const size_t pad_steps = (size_t)c->fb_steps + 2;
     const void* src = nullptr;
@@ -4060,7 +4146,7 @@ int baz_music_set_peak_mode(baz_music_ctx* c, int mode)
 {
     if (!c || (mode != 0 && mode != 1)) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
-    if (mode && c->wide) return BAZ_MUSIC_E_UNSUPPORTED;   // the opt-in picker exists for the specialised kernels only
+    if (mode && c->wide && !beamspace_on(c)) return BAZ_MUSIC_E_UNSUPPORTED;   // the opt-in picker exists for the specialised kernels only (beamspace: the inner context runs them)
     if (c->sm.inner) {   // (the inner context is never wider than this one)
         const int r = baz_music_set_peak_mode(c->sm.inner, mode);
         if (r != BAZ_MUSIC_OK) return r;
@@ -4099,6 +4185,8 @@ int baz_music_set_smoothing(baz_music_ctx* c, uint32_t subarray, int forward_bac
     std::lock_guard<std::mutex> tl(c->tab_mtx);   // against set_table: c->hRaw is the table in force while it is held
     DeviceGuard guard(c->device);
     baz_music_ctx* old = nullptr;
+    if (c->sm.inner && c->sm.kind == baz_music_ctx::FRONT_BEAMSPACE)   // (two front-ends would compete for one inner context; sm changes under tab_mtx + mtx)
+        return (subarray == c->m && !fb) ? BAZ_MUSIC_OK : BAZ_MUSIC_E_UNSUPPORTED;
     if (subarray == c->m && !fb) {                // off: the reference
         {
             std::lock_guard<std::mutex> lk(c->mtx);
@@ -4140,6 +4228,7 @@ int baz_music_set_smoothing(baz_music_ctx* c, uint32_t subarray, int forward_bac
             c->out_beam.count = 0;
             old = c->sm.inner;
             c->sm.inner = inner;
+            c->sm.kind = baz_music_ctx::FRONT_SMOOTHING;
             c->sm.ms = subarray; c->sm.L = L; c->sm.Kp = (uint32_t)Kp; c->sm.fb = fb;
             c->sm.perm = perm;
             inner = nullptr;
@@ -4154,7 +4243,7 @@ int baz_music_set_order_mode(baz_music_ctx* c, int criterion)
 {
     if (!c || criterion < 0 || criterion > 2) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
-    if (criterion && c->wide) return BAZ_MUSIC_E_UNSUPPORTED;   // the ORDER epilogues exist for the specialised kernels only
+    if (criterion && c->wide && !beamspace_on(c)) return BAZ_MUSIC_E_UNSUPPORTED;   // the ORDER epilogues exist for the specialised kernels only
     if (criterion && c->estimator) return BAZ_MUSIC_E_UNSUPPORTED;   // (Capon / Bartlett compute no eigenvalues)
     if (c->sm.inner) {   // (the inner context is never wider than this one)
         const int r = baz_music_set_order_mode(c->sm.inner, criterion);
@@ -4212,7 +4301,7 @@ int baz_music_set_refine_mode(baz_music_ctx* c, int mode)
 {
     if (!c || (mode != 0 && mode != 1)) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
-    if (mode && c->wide) return BAZ_MUSIC_E_UNSUPPORTED;   // no peak picker on the run-time-m path: only first entries would move
+    if (mode && c->wide && !beamspace_on(c)) return BAZ_MUSIC_E_UNSUPPORTED;   // no peak picker on the run-time-m path: only first entries would move
     if (mode && c->estimator) return BAZ_MUSIC_E_UNSUPPORTED;   // (the fit is on the MUSIC denominator)
     if (c->sm.inner) {   // (the inner context is never wider than this one)
         const int r = baz_music_set_refine_mode(c->sm.inner, mode);
@@ -4310,7 +4399,7 @@ int baz_music_set_power_mode(baz_music_ctx* c, int mode)
 {
     if (!c || mode < 0 || mode > 2) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
-    if (mode && c->wide) return BAZ_MUSIC_E_UNSUPPORTED;   // (power_kernel is specialised per m, like the pickers it follows)
+    if (mode && c->wide && !beamspace_on(c)) return BAZ_MUSIC_E_UNSUPPORTED;   // (power_kernel is specialised per m, like the pickers it follows)
     if (c->sm.inner) {   // (the inner context is never wider than this one)
         const int r = baz_music_set_power_mode(c->sm.inner, mode);
         if (r != BAZ_MUSIC_OK) return r;
@@ -4350,10 +4439,14 @@ int baz_music_set_estimator(baz_music_ctx* c, int kind)
 {
     if (!c || kind < BAZ_MUSIC_ESTIMATOR_MUSIC || kind > BAZ_MUSIC_ESTIMATOR_BARTLETT) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
-    if (kind && c->wide) return BAZ_MUSIC_E_UNSUPPORTED;   // (spectrum_scan_kernel is specialised per m, like the other modes' kernels)
+    if (kind && c->wide && !beamspace_on(c)) return BAZ_MUSIC_E_UNSUPPORTED;   // (spectrum_scan_kernel is specialised per m, like the other modes' kernels)
     // the emitter-count mode needs eigenvalues, refinement fits the MUSIC denominator, smoothing runs an inner MUSIC context
-    if (kind && (c->order_mode || c->refine_mode || c->sm.inner)) return BAZ_MUSIC_E_UNSUPPORTED;
+    if (kind && (c->order_mode || c->refine_mode || (c->sm.inner && !beamspace_on(c)))) return BAZ_MUSIC_E_UNSUPPORTED;
     if (kind && c->wh_want) return BAZ_MUSIC_E_UNSUPPORTED;   // (whitening on: Capon is invariant under the transform, nothing is gained)
+    if (beamspace_on(c)) {   // beamspace: the inner context evaluates the estimator on the projected items
+        const int r = baz_music_set_estimator(c->sm.inner, kind);
+        if (r != BAZ_MUSIC_OK) return r;
+    }
     c->estimator = kind;
     return BAZ_MUSIC_OK;
 }
@@ -4524,6 +4617,10 @@ int baz_music_calibration_apply(uint32_t m, uint32_t resolution, const float* ta
 // (p, q) with a_pq = g e^{i phi} is J = diag(1, e^{-i phi}) [[c, s], [-s, c]] with the real Jacobi angle of [[a_pp, g], [g, a_qq]];
 // A <- J^H A J, V <- V J.  Pairs at or below 2^-75 of the Frobenius norm are left alone (m^2 of them stay far below the m 2^-52 |A|
 // backward error of the rotations themselves); the sweeps end when one rotates nothing.
+namespace {
+void hermitian_jacobi(uint32_t m, std::vector<std::complex<double>>& A, std::vector<std::complex<double>>& V);
+}
+
 int baz_music_calibration_estimate(uint32_t m, const double* Rbar_ri, const float* ref_ri, double* gamma_ri, double* quality)
 {
     if (m < 1 || m > BAZ_MUSIC_MAX_M || !Rbar_ri || !ref_ri || !gamma_ri || !quality) return BAZ_MUSIC_E_INVALID;
@@ -4534,7 +4631,7 @@ int baz_music_calibration_estimate(uint32_t m, const double* Rbar_ri, const floa
         *quality = 0.0;
         return BAZ_MUSIC_OK;
     };
-    double trace = 0.0, frob2 = 0.0;
+    double trace = 0.0;
     for (size_t i = 0; i < (size_t)2 * m * m; ++i) {
         if (!(Rbar_ri[i] - Rbar_ri[i] == 0.0)) return degenerate();
     }
@@ -4553,6 +4650,42 @@ int baz_music_calibration_estimate(uint32_t m, const double* Rbar_ri, const floa
             A[(size_t)q * m + p] = std::conj(a);
         }
     }
+    hermitian_jacobi(m, A, V);
+    uint32_t top = 0;
+    for (uint32_t p = 1; p < m; ++p)
+        if (A[(size_t)p * m + p].real() > A[(size_t)top * m + top].real()) top = p;
+    const double l1 = ldexp(A[(size_t)top * m + top].real(), ex);
+    double vn = 0.0;
+    for (uint32_t r = 0; r < m; ++r) vn = vn + std::norm(V[(size_t)r * m + top]);
+    vn = std::sqrt(vn);
+    const cd v0 = V[(size_t)0 * m + top];
+    if (v0 == cd(0.0, 0.0) || !(vn > 0.0)) return degenerate();
+    std::vector<cd> gh(m);
+    for (uint32_t r = 0; r < m; ++r) gh[r] = (V[(size_t)r * m + top] / vn) / cd((double)ref_ri[2 * r], (double)ref_ri[2 * r + 1]);
+    const double a0 = std::abs(gh[0]);
+    if (!(a0 > 0.0) || !(a0 - a0 == 0.0)) return degenerate();
+    const cd rot = std::conj(gh[0]) / a0;
+    double s2 = 0.0;
+    for (uint32_t r = 0; r < m; ++r) {
+        gh[r] = r == 0 ? cd(a0, 0.0) : gh[r] * rot;
+        s2 = s2 + std::norm(gh[r]);
+    }
+    const double scale = 1.0 / std::sqrt(s2 / (double)m);
+    for (uint32_t r = 0; r < m; ++r) {
+        gamma_ri[2 * r] = gh[r].real() * scale;
+        gamma_ri[2 * r + 1] = r == 0 ? 0.0 : gh[r].imag() * scale;
+    }
+    *quality = l1 / trace;
+    return BAZ_MUSIC_OK;
+}
+
+namespace {
+// The cyclic Hermitian Jacobi of the comment above, on the host in fp64: A (m x m, Hermitian, row-major) becomes diagonal, V (the
+// identity on entry) collects the rotations: its columns are the eigenvectors.  Shared by the calibration estimate and the beamspace design.
+void hermitian_jacobi(const uint32_t m, std::vector<std::complex<double>>& A, std::vector<std::complex<double>>& V)
+{
+    typedef std::complex<double> cd;
+    double frob2 = 0.0;
     for (const cd& a : A) frob2 += std::norm(a);
     const double small = ldexp(std::sqrt(frob2), -75);
     for (int sweep = 0; sweep < 64; ++sweep) {
@@ -4589,32 +4722,183 @@ int baz_music_calibration_estimate(uint32_t m, const double* Rbar_ri, const floa
             }
         if (!rotated) break;
     }
-    uint32_t top = 0;
-    for (uint32_t p = 1; p < m; ++p)
-        if (A[(size_t)p * m + p].real() > A[(size_t)top * m + top].real()) top = p;
-    const double l1 = ldexp(A[(size_t)top * m + top].real(), ex);
-    double vn = 0.0;
-    for (uint32_t r = 0; r < m; ++r) vn = vn + std::norm(V[(size_t)r * m + top]);
-    vn = std::sqrt(vn);
-    const cd v0 = V[(size_t)0 * m + top];
-    if (v0 == cd(0.0, 0.0) || !(vn > 0.0)) return degenerate();
-    std::vector<cd> gh(m);
-    for (uint32_t r = 0; r < m; ++r) gh[r] = (V[(size_t)r * m + top] / vn) / cd((double)ref_ri[2 * r], (double)ref_ri[2 * r + 1]);
-    const double a0 = std::abs(gh[0]);
-    if (!(a0 > 0.0) || !(a0 - a0 == 0.0)) return degenerate();
-    const cd rot = std::conj(gh[0]) / a0;
-    double s2 = 0.0;
-    for (uint32_t r = 0; r < m; ++r) {
-        gh[r] = r == 0 ? cd(a0, 0.0) : gh[r] * rot;
-        s2 = s2 + std::norm(gh[r]);
-    }
-    const double scale = 1.0 / std::sqrt(s2 / (double)m);
-    for (uint32_t r = 0; r < m; ++r) {
-        gamma_ri[2 * r] = gh[r].real() * scale;
-        gamma_ri[2 * r + 1] = r == 0 ? 0.0 : gh[r].imag() * scale;
-    }
-    *quality = l1 / trace;
+}
+}  // namespace
+
+// ---- opt-in beamspace front-end: the host side (include/baz_music_hip.h; beamspace_kernels.hip.h) ----------------------------------
+int baz_music_beamspace_apply(uint32_t m, uint32_t B, const double* T_ri, int normalise, const float* in_ri, uint32_t columns, float* out_ri)
+{
+    if (m < 2 || m > BAZ_MUSIC_MAX_M || B < 1 || B > m || B > BAZ_MUSIC_FAST_M || !T_ri) return BAZ_MUSIC_E_INVALID;
+    if (columns == 0) return BAZ_MUSIC_OK;
+    if (!in_ri || !out_ri) return BAZ_MUSIC_E_INVALID;
+    beamspace_apply_host(m, B, T_ri, normalise, in_ri, columns, out_ri);
     return BAZ_MUSIC_OK;
+}
+
+// C = sum over the sector's bins of a a^H in fp64, decomposed by hermitian_jacobi (scaled by a power of two first, as the calibration
+// estimate does: exact, and the eigenvectors do not change); T = the eigenvectors of the B largest eigenvalues, descending (ties: the
+// lower Jacobi column first), each of unit norm with its largest-modulus component (lowest index on ties) real and positive.
+int baz_music_beamspace_design(uint32_t m, uint32_t resolution, const float* table_ri, uint32_t bin_lo, uint32_t bin_count, uint32_t B,
+                               double* T_out, double* captured_out)
+{
+    if (m < 2 || m > BAZ_MUSIC_MAX_M || resolution == 0 || !table_ri || !T_out) return BAZ_MUSIC_E_INVALID;
+    if (bin_count == 0 || bin_count > resolution || B < 1 || B > m || B > BAZ_MUSIC_FAST_M) return BAZ_MUSIC_E_INVALID;
+    typedef std::complex<double> cd;
+    std::vector<cd> A((size_t)m * m, cd(0.0, 0.0)), V((size_t)m * m, cd(0.0, 0.0));
+    for (uint32_t i = 0; i < bin_count; ++i) {
+        const float* a = table_ri + 2 * (size_t)(((uint64_t)bin_lo + i) % resolution) * m;
+        for (uint32_t p = 0; p < m; ++p) {
+            const cd ap((double)a[2 * p], (double)a[2 * p + 1]);
+            for (uint32_t q = p; q < m; ++q) A[(size_t)p * m + q] += ap * std::conj(cd((double)a[2 * q], (double)a[2 * q + 1]));
+        }
+    }
+    double trace = 0.0;
+    for (uint32_t p = 0; p < m; ++p) trace = trace + A[(size_t)p * m + p].real();
+    if (!(trace > 0.0) || !(trace - trace == 0.0)) return BAZ_MUSIC_E_INVALID;      // (a non-finite or all-zero sector)
+    int ex = 0;
+    (void)frexp(trace, &ex);
+    for (uint32_t p = 0; p < m; ++p) {
+        V[(size_t)p * m + p] = cd(1.0, 0.0);
+        A[(size_t)p * m + p] = cd(ldexp(A[(size_t)p * m + p].real(), -ex), 0.0);
+        for (uint32_t q = p + 1; q < m; ++q) {
+            const cd a(ldexp(A[(size_t)p * m + q].real(), -ex), ldexp(A[(size_t)p * m + q].imag(), -ex));
+            if (!(a.real() - a.real() == 0.0) || !(a.imag() - a.imag() == 0.0)) return BAZ_MUSIC_E_INVALID;
+            A[(size_t)p * m + q] = a;
+            A[(size_t)q * m + p] = std::conj(a);
+        }
+    }
+    hermitian_jacobi(m, A, V);
+    std::vector<uint32_t> idx(m);
+    for (uint32_t p = 0; p < m; ++p) idx[p] = p;
+    std::stable_sort(idx.begin(), idx.end(), [&](uint32_t x, uint32_t y) { return A[(size_t)x * m + x].real() > A[(size_t)y * m + y].real(); });
+    double top = 0.0, all = 0.0;
+    for (uint32_t p = 0; p < m; ++p) {
+        all = all + A[(size_t)idx[p] * m + idx[p]].real();
+        if (p + 1 == B) top = all;
+    }
+    for (uint32_t b = 0; b < B; ++b) {
+        const uint32_t col = idx[b];
+        uint32_t k = 0;
+        double big = -1.0, n2 = 0.0;
+        for (uint32_t r = 0; r < m; ++r) {
+            const double v = std::norm(V[(size_t)r * m + col]);
+            n2 = n2 + v;
+            if (v > big) { big = v; k = r; }
+        }
+        if (!(big > 0.0)) return BAZ_MUSIC_E_INVALID;
+        const cd vk = V[(size_t)k * m + col];
+        const cd rot = std::conj(vk) / (std::abs(vk) * std::sqrt(n2));
+        for (uint32_t r = 0; r < m; ++r) {
+            const cd t = V[(size_t)r * m + col] * rot;
+            T_out[2 * ((size_t)r * B + b)] = t.real();
+            T_out[2 * ((size_t)r * B + b) + 1] = r == k ? 0.0 : t.imag();
+        }
+    }
+    if (captured_out) *captured_out = top / all;
+    return BAZ_MUSIC_OK;
+}
+
+int baz_music_set_beamspace(baz_music_ctx* c, uint32_t B, const double* T_ri, int normalise)
+{
+    if (!c) return BAZ_MUSIC_E_INVALID;
+    const bool off = B == 0 || !T_ri;
+    std::lock_guard<std::mutex> tl(c->tab_mtx);   // against set_table: c->hRaw is the table in force while it is held
+    DeviceGuard guard(c->device);
+    baz_music_ctx* old = nullptr;
+    DevBuf<double2> old_tc;
+    if (off) {
+        DevBuf<float2> old_y;                     // the front-end's workspace goes with it (released behind the drain below)
+        DevBuf<float> old_x, old_al, old_spec;
+        {
+            std::lock_guard<std::mutex> lk(c->mtx);
+            if (!beamspace_on(c)) return BAZ_MUSIC_OK;   // (off and staying off; smoothing, if on, is not this mode's to end)
+            old = c->sm.inner;
+            c->sm.inner = nullptr;
+            c->sm.kind = baz_music_ctx::FRONT_SMOOTHING;
+            c->sm.ms = 0; c->sm.L = 1; c->sm.Kp = 0; c->sm.fb = 0; c->sm.bs_norm = 0;
+            c->sm.bs_T.clear();
+            old_tc = std::move(c->sm.dTc);
+            old_y = std::move(c->sm.dY); old_x = std::move(c->sm.dX); old_al = std::move(c->sm.dAl); old_spec = std::move(c->sm.dSpec);
+            c->avg_hist = 0;                      // (averaging: the shape of R changes, the history starts over)
+            if (c->wide) {                        // what the run-time-m kernels do not offer goes with the front-end that carried it
+                c->peak_mode = 0; c->order_mode = 0; c->refine_mode = 0; c->power_mode = 0; c->estimator = 0;
+            }
+        }
+        baz_music_destroy(old);                   // (drains the stream first: batches in flight may still use it and conj(T))
+        return BAZ_MUSIC_OK;
+    }
+    if (B < 2 || B > c->m || B > BAZ_MUSIC_FAST_M || B <= c->n || !beamspace_T_ok(T_ri, c->m, B)) return BAZ_MUSIC_E_INVALID;
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);
+        if (c->sm.inner && !beamspace_on(c)) return BAZ_MUSIC_E_UNSUPPORTED;   // (smoothing on: two front-ends, one inner context)
+        if (c->beam_mode) return BAZ_MUSIC_E_UNSUPPORTED;                      // (its weights would be B-vectors)
+    }
+    if (c->calib_on || c->wh_on) return BAZ_MUSIC_E_UNSUPPORTED;   // (both change under tab_mtx; their composition with T^H is not defined here)
+    if ((uint64_t)B * c->K > (1ull << 31)) return BAZ_MUSIC_E_UNSUPPORTED;
+    std::vector<float> proj((size_t)c->res * B * 2);
+    beamspace_apply_host(c->m, B, T_ri, normalise ? 1 : 0, c->hRaw, c->res, proj.data());
+    baz_music_ctx* inner = nullptr;
+    int r = baz_music_create(&inner, B, c->n, B * c->K, c->res, proj.data(), c->device);
+    if (r != BAZ_MUSIC_OK) return r;
+    DevBuf<double2> tc;
+    {
+        const std::vector<double2> h = beamspace_conj(T_ri, c->m, B);
+        hipError_t e = tc.allocate(h.size());
+        if (e == hipSuccess) e = hipMemcpy(tc.get(), h.data(), h.size() * sizeof(double2), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            baz_music_destroy(inner);
+            return hip_fail(c, e, "beamspace: conj(T)");
+        }
+    }
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);   // a batch sees the old setting or the new one
+        r = c->beam_mode ? BAZ_MUSIC_E_UNSUPPORTED : baz_music_set_stream(inner, c->stream);   // (set_beam_mode may have come in between)
+        if (r == BAZ_MUSIC_OK) r = baz_music_set_peak_mode(inner, c->peak_mode);
+        if (r == BAZ_MUSIC_OK) r = baz_music_set_order_mode(inner, c->order_mode);
+        if (r == BAZ_MUSIC_OK) r = baz_music_set_refine_mode(inner, c->refine_mode);
+        if (r == BAZ_MUSIC_OK) r = baz_music_set_power_mode(inner, c->power_mode);
+        if (r == BAZ_MUSIC_OK) r = baz_music_set_estimator(inner, c->estimator);
+        if (r == BAZ_MUSIC_OK) r = baz_music_set_averaging(inner, c->avg_window, c->avg_beta);   // (a new inner context: an empty history)
+        if (r == BAZ_MUSIC_OK) {
+            inner->ord_driven = true;             // (N of the criterion is the inner context's own K)
+            c->out_beam.on = false;               // (calls under the mode run with the beam mode off: last_beams reports zeros)
+            c->out_beam.count = 0;
+            old = c->sm.inner;
+            old_tc = std::move(c->sm.dTc);
+            c->sm.inner = inner;
+            c->sm.dTc = std::move(tc);
+            c->sm.kind = baz_music_ctx::FRONT_BEAMSPACE;
+            c->sm.ms = B; c->sm.L = 1; c->sm.Kp = c->K; c->sm.fb = 0;
+            c->sm.bs_norm = normalise ? 1 : 0;
+            c->sm.bs_T.assign(T_ri, T_ri + (size_t)2 * c->m * B);
+            inner = nullptr;
+        }
+    }
+    baz_music_destroy(inner);                     // (only after a failure)
+    baz_music_destroy(old);                       // (drains the stream; the retired conj(T) goes after it, with old_tc)
+    return r;
+}
+
+int baz_music_get_beamspace(const baz_music_ctx* c, uint32_t* B, double* T_out, int* normalise)
+{
+    if (!c) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(const_cast<baz_music_ctx*>(c)->mtx);
+    const bool on = beamspace_on(c);
+    if (B) *B = on ? c->sm.ms : 0;
+    if (normalise) *normalise = on ? c->sm.bs_norm : 0;
+    if (T_out && on) std::memcpy(T_out, c->sm.bs_T.data(), c->sm.bs_T.size() * sizeof(double));
+    return BAZ_MUSIC_OK;
+}
+
+int baz_music_debug_beamspace(baz_music_ctx* c, const void* d_in, uint32_t batch, void* d_out)
+{
+    if (!c || !d_in || !d_out || d_in == d_out || batch == 0) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    DeviceGuard guard(c->device);
+    if (!beamspace_on(c)) return BAZ_MUSIC_E_UNSUPPORTED;
+    if ((uint64_t)batch * c->K > 0xffffffffull) return BAZ_MUSIC_E_INVALID;
+    (void)hipGetLastError();
+    return launch_beamspace(c, static_cast<const float2*>(d_in), batch * c->K, static_cast<float2*>(d_out));
 }
 
 namespace {
@@ -4844,8 +5128,9 @@ int baz_music_get_smoothing(const baz_music_ctx* c, uint32_t* subarray, int* for
 {
     if (!c) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(const_cast<baz_music_ctx*>(c)->mtx);
-    if (subarray) *subarray = c->sm.inner ? c->sm.ms : c->m;
-    if (forward_backward) *forward_backward = c->sm.inner ? c->sm.fb : 0;
+    const bool on = c->sm.inner && !beamspace_on(c);
+    if (subarray) *subarray = on ? c->sm.ms : c->m;
+    if (forward_backward) *forward_backward = on ? c->sm.fb : 0;
     return BAZ_MUSIC_OK;
 }
 

@@ -311,6 +311,47 @@ std::vector<std::complex<double> > baz_music_doa::noise_covariance()
     return rn;
 }
 
+void baz_music_doa::set_beamspace(const std::vector<std::complex<double> >& T, unsigned int B, bool normalise)
+{
+    if (B != 0 && T.size() != (size_t)d_m * B)
+        throw std::invalid_argument("music_doa: set_beamspace: T must hold m*B values, row-major [antenna][beam] (or B = 0: off)");
+    const int rc = baz_music_set_beamspace(d_ctx, B, B ? reinterpret_cast<const double*>(T.data()) : NULL, normalise ? 1 : 0);
+    if (rc == BAZ_MUSIC_E_INVALID)
+        throw std::invalid_argument("music_doa: set_beamspace: n < B <= min(m, 16), B >= 2, and T finite without an all-zero column are required");
+    if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: set_beamspace: ") + baz_music_strerror(rc));
+}
+
+double baz_music_doa::set_beamspace_sector(unsigned int bin_lo, unsigned int bin_count, unsigned int B, bool normalise)
+{
+    std::vector<float> flat;
+    {
+        gr::thread::scoped_lock guard(d_mutex);
+        flat = flatten_response(d_array_response, d_m, d_resolution);
+    }
+    std::vector<std::complex<double> > T((size_t)d_m * (B ? B : 1));
+    double captured = 0.0;
+    const int rc = baz_music_beamspace_design(d_m, d_resolution, flat.data(), bin_lo, bin_count, B, reinterpret_cast<double*>(T.data()), &captured);
+    if (rc == BAZ_MUSIC_E_INVALID)
+        throw std::invalid_argument("music_doa: set_beamspace_sector: 1 <= bin_count <= resolution and 1 <= B <= min(m, 16) are required");
+    if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: set_beamspace_sector: ") + baz_music_strerror(rc));
+    set_beamspace(T, B, normalise);
+    return captured;
+}
+
+std::vector<std::complex<double> > baz_music_doa::beamspace()
+{
+    uint32_t B = 0;
+    int rc = baz_music_get_beamspace(d_ctx, &B, NULL, NULL);
+    std::vector<std::complex<double> > T((size_t)d_m * B);
+    if (rc == BAZ_MUSIC_OK && B) {
+        uint32_t B2 = 0;
+        rc = baz_music_get_beamspace(d_ctx, &B2, reinterpret_cast<double*>(T.data()), NULL);
+        if (rc == BAZ_MUSIC_OK && B2 != B) T.clear();      /* (the setting changed in between: report it as off) */
+    }
+    if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: beamspace: ") + baz_music_strerror(rc));
+    return T;
+}
+
 void baz_music_doa::whiten_next(unsigned int items)
 {
     if (items == 0) throw std::invalid_argument("music_doa: whiten_next: items > 0 is required");

@@ -121,6 +121,16 @@ public:
     std::vector<std::complex<double> > noise_covariance();
     void whiten_next(unsigned int items);
     int last_whitening_status();
+    /* Extension, off by default (not in the reference): beamspace MUSIC -- every snapshot is projected onto B <= 16 beams, y = T^H x
+     * (T: m*B values, row-major [antenna][beam]), and the estimate runs on the table T^H a with every opt-in mode of this class, also
+     * for 17 .. 64 antennas (baz_music_set_beamspace, include/baz_music_hip.h).  B = 0 is off.  set_beamspace_sector designs T for the
+     * `bin_count` bins from `bin_lo` (wrapping) of the array response in force (baz_music_beamspace_design), sets it and returns the
+     * captured fraction.  beamspace(): the T in force (m*B values; empty while off).  Not available while smoothing, a calibration,
+     * noise pre-whitening or the beam mode is on.  Throws std::invalid_argument unless n < B <= min(m, 16), B >= 2 and T is finite
+     * without an all-zero column. */
+    void set_beamspace(const std::vector<std::complex<double> >& T, unsigned int B, bool normalise = false);
+    double set_beamspace_sector(unsigned int bin_lo, unsigned int bin_count, unsigned int B, bool normalise = false);
+    std::vector<std::complex<double> > beamspace();
 
     /* Page-locking of the scheduler's stream buffers (baz_music_set_host_pinning, include/baz_music_hip.h): work()
      * registers the ranges it is handed the first time it sees them, stop() and the destructor release them.  On by

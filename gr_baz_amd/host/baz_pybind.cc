@@ -272,6 +272,13 @@ PYBIND11_MODULE(_baz_music, mod)
         .def("noise_covariance", [](music_doa_handle& h) { return h.blk->noise_covariance(); })
         .def("whiten_next", [](music_doa_handle& h, unsigned int items) { h.blk->whiten_next(items); }, py::arg("items"))
         .def("last_whitening_status", [](music_doa_handle& h) { return h.blk->last_whitening_status(); })
+        .def("set_beamspace", [](music_doa_handle& h, const std::vector<std::complex<double> >& T, unsigned int B, bool normalise) {
+                 h.blk->set_beamspace(T, B, normalise);
+             }, py::arg("T"), py::arg("B"), py::arg("normalise") = false)
+        .def("set_beamspace_sector", [](music_doa_handle& h, unsigned int bin_lo, unsigned int bin_count, unsigned int B, bool normalise) {
+                 return h.blk->set_beamspace_sector(bin_lo, bin_count, B, normalise);
+             }, py::arg("bin_lo"), py::arg("bin_count"), py::arg("B"), py::arg("normalise") = false)
+        .def("beamspace", [](music_doa_handle& h) { return h.blk->beamspace(); })
         .def("last_orders",
              [](music_doa_handle& h, unsigned int count) {
                  const std::vector<unsigned char> v = h.blk->last_orders(count);

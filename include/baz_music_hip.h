@@ -185,6 +185,9 @@ BAZ_MUSIC_API size_t baz_music_debug_i8_image(uint32_t m, uint32_t resolution, c
  *                          `host_table_image` (needs no device) builds the same image with the round-4 host routines: the
  *                          checker the device builders must agree with byte for byte (tests/test_retune.py). */
 #define BAZ_MUSIC_TABLE_NPARAMS 22
+/* which + BAZ_MUSIC_TABLE_IMAGE_INNER: while baz_music_set_beamspace is on, image `which` of the projected table T^H a that the inner
+ * context holds (0 while the mode is off). */
+#define BAZ_MUSIC_TABLE_IMAGE_INNER 256
 BAZ_MUSIC_API size_t baz_music_debug_table_image(baz_music_ctx* ctx, int which, void* out, size_t out_bytes);
 BAZ_MUSIC_API size_t baz_music_debug_host_table_image(uint32_t m, uint32_t n, uint32_t resolution, const float* table_ri,
                                                       int which, void* out, size_t out_bytes);
@@ -674,6 +677,67 @@ BAZ_MUSIC_API int baz_music_whiten_table(uint32_t m, uint32_t resolution, const 
 BAZ_MUSIC_API int baz_music_debug_whiten(baz_music_ctx* ctx, const void* d_R_in, uint32_t batch, void* d_R_out);
 BAZ_MUSIC_API int baz_music_mean_covariance(baz_music_ctx* ctx, const float* in_ri, uint32_t batch, double* Rbar_ri);
 BAZ_MUSIC_API int baz_music_mean_covariance_device(baz_music_ctx* ctx, const void* d_in, uint32_t batch, double* Rbar_ri);
+/* OPT-IN extension, NOT reference behaviour: BEAMSPACE MUSIC.  Every snapshot x of the m antennas is projected onto
+ * B <= BAZ_MUSIC_FAST_M beams, y = T^H x, and the estimate runs in the B-dimensional space on the table a' = T^H a.  It is what opens
+ * the opt-in modes of this header (peak mode, emitter count, refinement, power mode, the Capon / Bartlett estimators), which exist up
+ * to BAZ_MUSIC_FAST_M antennas, to arrays of 17 .. BAZ_MUSIC_MAX_M antennas.  T_ri: T, m x B complex128, row-major [antenna r][beam b],
+ * re / im interleaved.  B == 0 or T_ri == NULL switches the mode off (the default; off is the reference).
+ *   PROJECTION  for every time column c of every item, x_r(c) = in[c*m + r]:
+ *                 y_b(c) = fl32(sum_{r = 0 .. m-1} conj(T_rb) x_r(c))
+ *               x widened exactly; the sum in fp64 from (+0, +0) with r ascending; each term the four fused multiply-adds
+ *                 re = fma(wr, xr, re); re = fma(-wi, xi, re); im = fma(wr, xi, im); im = fma(wi, xr, im)
+ *               with wr = Re T_rb, wi = -Im T_rb (the chain of the noise pre-whitening above); one round-to-nearest conversion per
+ *               component.  y(b, c) = out[c*B + b]: an item of the shape (B, B K).  A batch is one flat (batch K) x m row-major matrix in
+ *               and one (batch K) x B matrix out; a column never reads another column, so a non-finite sample poisons its own item
+ *               only.  No special cases: overflow to +-inf on conversion is IEEE's.
+ *   TABLE       the table in force for the inner context is the same routine applied to every row of the raw table (a table is laid out
+ *               like an item with K = resolution).  With normalise != 0 a row's unrounded fp64 sums s_b are divided by
+ *               nu = sqrt(sum_b (Re s_b)^2 + (Im s_b)^2) (accumulated with b ascending, re before im, by fma) before the conversion; a
+ *               row whose nu is 0 or not finite becomes zeros.  normalise exists because plain MUSIC does not divide by ||a'||^2: a
+ *               design whose out-of-sector rows nearly vanish (||T^H a|| << ||a||) shows huge pseudo-spectrum values there, which unit
+ *               rows avoid.  Designs whose rows keep a fair share of their norm everywhere do not need it.
+ *   PORTS       ang / lvl / spectrum are what a plain context of shape (B, n, B K, resolution) on the table a' produces for the items y,
+ *               bit for bit (it is such a context that runs: gr_baz_amd/csrc/beamspace_kernels.hip.h projects, the inner context does the
+ *               rest, int8 and f16-gated scans included).  ang is still bin*360/resolution of the caller's own table.
+ *   VALIDITY    2 <= B <= min(m, BAZ_MUSIC_FAST_M), n < B, every antenna count 2 <= m <= BAZ_MUSIC_MAX_M; BAZ_MUSIC_E_INVALID otherwise, and
+ *               for a non-finite entry of T or an all-zero column; the setting in force stays after any error.  MUSIC and the MDL / AIC
+ *               count presume T^H T = I, so that white noise stays white.  THE SETTER DOES NOT ENFORCE IT; baz_music_beamspace_design
+ *               delivers it.
+ *   WHEN        like set_smoothing: the setter is serialised against process*() (a batch sees the old setting or the new one, never a
+ *               mixture); set_table while the mode is on rebuilds a' with the T in force and forwards it (T survives retunes).
+ *   COMPOSES    peak mode, emitter-count mode (N of the criterion is K), refinement, power mode, covariance averaging AND THE ESTIMATOR
+ *               KIND are forwarded to the inner context and survive switching this mode on -- and off, where the plain path offers them:
+ *               switching off on a context of more than BAZ_MUSIC_FAST_M antennas resets peak, emitter-count, refine and power mode and
+ *               the estimator to their defaults, because the run-time-m kernels have none of them.  last_orders, last_refine_offsets,
+ *               last_powers and their device forms answer for the inner context.  reserve, sync, set_stream, host_register /
+ *               set_host_pinning work; every call is cut into chunks whose projected items fit BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES (at
+ *               least one item per chunk), and the host-fed baz_music_process stages the same chunks through device buffers: the same
+ *               bits as the device path.  uses_i8_scan answers for the inner context.
+ *   REFUSES     with BAZ_MUSIC_E_UNSUPPORTED, in both orders, the setting in force staying: smoothing (two front-ends would compete for
+ *               one inner context), calibration and noise pre-whitening (gamma o a -> T^H and W -> T^H are definable but not offered), the
+ *               beam mode (its weights would be B-vectors; w = T w' is not offered).  profile, stage_ms, refined_values / refined_items
+ *               and the debug_ taps that run stages return BAZ_MUSIC_E_UNSUPPORTED and stage_name returns "" while the mode is on, as
+ *               under smoothing; table_image and bytes_per_item describe the full m-antenna table.
+ *   OFF         never set, set to off, or switched on and off again: the kernels, launch counts and every port of a context before the
+ *               mode existed, bit for bit; nothing is allocated.
+ * get_beamspace: *B = 0 while off, else the B in force, T_out (m*B complex128, may be NULL, untouched while off) and *normalise.
+ * debug_beamspace runs the projection alone with the T in force: d_in (batch items of m K complex64) -> d_out (batch K B complex64), device
+ * memory, not overlapping; BAZ_MUSIC_E_UNSUPPORTED while the mode is off.
+ * HOST FUNCTIONS (no device needed):
+ *   beamspace_apply   the routine above over `columns` rows of m complex64 -> rows of B complex64 (items and tables alike; normalise
+ *                     applies per row, as for tables); 1 <= B <= min(m, BAZ_MUSIC_FAST_M); the kernel runs the same text: the same bits.
+ *   beamspace_design  C = sum of a_b a_b^H over the bins (bin_lo + i) mod resolution, i < bin_count, accumulated in fp64 and decomposed by
+ *                     the cyclic Hermitian Jacobi of the calibration estimate; T_out (m x B) = the eigenvectors of the B largest
+ *                     eigenvalues in descending order, unit norm, each scaled so that its largest-modulus component (lowest index on
+ *                     ties) is real and positive; *captured_out (may be NULL) = the sum of those B eigenvalues / trace C.
+ *                     BAZ_MUSIC_E_INVALID for bin_count == 0 or > resolution, B out of range, or a sector that is zero or not finite. */
+BAZ_MUSIC_API int baz_music_set_beamspace(baz_music_ctx* ctx, uint32_t B, const double* T_ri, int normalise);
+BAZ_MUSIC_API int baz_music_get_beamspace(const baz_music_ctx* ctx, uint32_t* B, double* T_out, int* normalise);
+BAZ_MUSIC_API int baz_music_debug_beamspace(baz_music_ctx* ctx, const void* d_in, uint32_t batch, void* d_out);
+BAZ_MUSIC_API int baz_music_beamspace_apply(uint32_t m, uint32_t B, const double* T_ri, int normalise, const float* in_ri, uint32_t columns,
+                                            float* out_ri);
+BAZ_MUSIC_API int baz_music_beamspace_design(uint32_t m, uint32_t resolution, const float* table_ri, uint32_t bin_lo, uint32_t bin_count,
+                                             uint32_t B, double* T_out, double* captured_out);
 /* Statistic: how many (item, bin) values of the LAST process call were recomputed in the reference's literal form
  * ||G^H a||^2 because the projector form a^H Q a put them at or below ~m 1e-8 max||a||^2 (near-nulls of the noise
  * subspace, SNR >~ 55 dB); blocks until that call is done (a host-fed call cut into chunks reports their sum).
