@@ -128,6 +128,8 @@ def _retune(h, frequency):
     h.l = C_LIGHT / frequency
     h.array_response = calculate_antenna_array_response(h.antenna_array, h.angular_resolution, h.l)
     h.impl.set_array_response(h.array_response)
+    if getattr(h, "_subbands", None) is not None:      # the subband mode stays in force: all S tables at the new carrier, at once
+        h.impl.set_subband_tables(_subband_tables(h))
 
 
 def _set_smoothing(h, subarray, forward_backward):
@@ -177,6 +179,7 @@ def _set_estimator(h, kind):
     # EXTENSION, no reference counterpart: the Capon (1) or Bartlett (2) spectrum in place of MUSIC (0, the reference), see
     # include/baz_music_hip.h.  Stays in force across set_frequency().
     h.impl.set_estimator(estimator_kind(kind))
+    h._estimator = estimator_kind(kind)
 
 
 def _set_beam_mode(h, mode, loading):
@@ -257,6 +260,54 @@ def _set_beamspace_sector(h, bin_lo, bin_count, beams, normalise):
 def _beamspace(h):
     t = h.impl.beamspace()
     return numpy.asarray(t, dtype=numpy.complex128).reshape(h.m, -1) if len(t) else None
+
+
+def subband_offset(k, block):
+    """o(k): the frequency offset of DFT index k of a `block`-point DFT in units of sample_rate / block: k below ceil(block / 2),
+    k - block from there on."""
+    return k if k < (block + 1) // 2 else k - block
+
+
+def subband_bins(block, occupied=0.75):
+    """The DFT indices the subband mode uses: all k with |o(k)| / block <= occupied / 2, ascending."""
+    block = int(block)
+    if block < 2 or not (0.0 <= occupied <= 1.0):
+        raise ValueError("subbands need a block of at least 2 samples and 0 <= occupied <= 1")
+    return [k for k in range(block) if abs(subband_offset(k, block)) / block <= occupied / 2]
+
+
+def subband_wavelengths(frequency, sample_rate, block, bins):
+    """The wavelength of every used subband: C / (frequency + o(k) sample_rate / block)."""
+    return [C_LIGHT / (frequency + subband_offset(k, block) * sample_rate / block) for k in bins]
+
+
+def _subband_tables(h):
+    sample_rate, block, bins = h._subbands
+    return [calculate_antenna_array_response(h.antenna_array, h.angular_resolution, l)
+            for l in subband_wavelengths(C_LIGHT / h.l, sample_rate, block, bins)]
+
+
+def _set_subbands(h, sample_rate, block, occupied, combine):
+    # EXTENSION, no reference counterpart: wideband (subband) MUSIC -- a `block`-point DFT per antenna, the estimate per used subband
+    # on the array response at THAT subband's wavelength, the spectra combined, see include/baz_music_hip.h.  Stays in force across
+    # set_frequency(), which recomputes the S tables (h.array_response stays the centre table).
+    if sample_rate is None:
+        h.impl.set_subbands(0, [], [], 0)
+        h._subbands = None
+        return
+    bins = subband_bins(block, occupied)
+    if combine is None:
+        combine = 0 if getattr(h, "_estimator", 0) == 0 else 1        # harmonic under MUSIC, arithmetic for the Capon / Bartlett powers
+    combine = {"harmonic": 0, "arithmetic": 1}.get(combine, combine)
+    if isinstance(combine, bool) or combine not in (0, 1):
+        raise ValueError("combine must be 0 / 'harmonic', 1 / 'arithmetic' or None, not %r" % (combine,))
+    previous = getattr(h, "_subbands", None)
+    h._subbands = (float(sample_rate), int(block), bins)
+    try:
+        h.impl.set_subbands(int(block), bins, _subband_tables(h), int(combine))
+    except Exception:
+        h._subbands = previous
+        raise
 
 
 def _whiten_next(h, items):
@@ -387,6 +438,18 @@ if _HAVE_GR:
             """The m x B complex128 matrix T in force, or None while off."""
             return _beamspace(self)
 
+        def set_subbands(self, sample_rate, block, occupied=0.75, combine=None):
+            """Opt-in (not reference behaviour): wideband MUSIC for a band that one array response does not fit -- items are cut into
+            `block`-sample blocks, a DFT per antenna separates the subbands within `occupied` of the sampled band, each runs on the
+            response at its own wavelength C / (frequency + offset sample_rate / block), and the spectra are combined ("harmonic",
+            the default under MUSIC, or "arithmetic").  Stays in force across set_frequency().  set_subbands(None, 0): off."""
+            _set_subbands(self, sample_rate, block, occupied, combine)
+
+        def subbands(self):
+            """(block, combine, bins) in force, or None while off."""
+            v = list(self.impl.subbands())
+            return (int(v[0]), int(v[1]), [int(k) for k in v[2:]]) if v else None
+
         def whiten_next(self, items):
             """Opt-in (not reference behaviour): measure the noise covariance from the next `items` items (a noise-only capture)
             and apply it.  last_whitening_status(): -1 while waiting for the items, 0 once applied, else the error code."""
@@ -501,6 +564,18 @@ else:
         def beamspace(self):
             """The m x B complex128 matrix T in force, or None while off."""
             return _beamspace(self)
+
+        def set_subbands(self, sample_rate, block, occupied=0.75, combine=None):
+            """Opt-in (not reference behaviour): wideband MUSIC for a band that one array response does not fit -- items are cut into
+            `block`-sample blocks, a DFT per antenna separates the subbands within `occupied` of the sampled band, each runs on the
+            response at its own wavelength C / (frequency + offset sample_rate / block), and the spectra are combined ("harmonic",
+            the default under MUSIC, or "arithmetic").  Stays in force across set_frequency().  set_subbands(None, 0): off."""
+            _set_subbands(self, sample_rate, block, occupied, combine)
+
+        def subbands(self):
+            """(block, combine, bins) in force, or None while off."""
+            v = list(self.impl.subbands())
+            return (int(v[0]), int(v[1]), [int(k) for k in v[2:]]) if v else None
 
         def whiten_next(self, items):
             """Opt-in (not reference behaviour): measure the noise covariance from the next `items` items (a noise-only capture)

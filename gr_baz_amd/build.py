@@ -61,6 +61,7 @@ def build_hip(force=False, verbose=False):
                   os.path.join(CSRC, "power_kernels.hip.h"), os.path.join(CSRC, "beam_kernels.hip.h"),
                   os.path.join(CSRC, "capon_solve.hip.h"), os.path.join(CSRC, "calib_kernels.hip.h"),
                   os.path.join(CSRC, "whiten_kernels.hip.h"), os.path.join(CSRC, "beamspace_kernels.hip.h"),
+                  os.path.join(CSRC, "subband_kernels.hip.h"),
                   os.path.join(CSRC, "spectrum_kernels.hip.h"),
                   os.path.join(CSRC, "evd_lds_kernel.inc.h"), os.path.join(CSRC, "cov4_evd_kernel.inc.h"),
                   os.path.join(CSRC, "device_buffer.hip.h"), os.path.join(INCLUDE, "baz_music_hip.h")]

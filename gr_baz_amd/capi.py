@@ -51,7 +51,12 @@ SYMBOLS = [
     "baz_music_debug_whiten", "baz_music_mean_covariance", "baz_music_mean_covariance_device",
     "baz_music_set_beamspace", "baz_music_get_beamspace", "baz_music_debug_beamspace", "baz_music_beamspace_apply",
     "baz_music_beamspace_design",
+    "baz_music_set_subbands", "baz_music_set_subband_tables", "baz_music_get_subbands", "baz_music_debug_subbands",
+    "baz_music_debug_subband_combine",
+    "baz_music_subband_twiddles", "baz_music_subband_apply",
 ]
+MAX_SUBBANDS = 32                   # BAZ_MUSIC_MAX_SUBBANDS
+SUBBAND_HARMONIC, SUBBAND_ARITHMETIC = 0, 1   # BAZ_MUSIC_SUBBAND_*
 ESTIMATOR_MUSIC, ESTIMATOR_CAPON, ESTIMATOR_BARTLETT = 0, 1, 2   # BAZ_MUSIC_ESTIMATOR_*
 MAX_AVG_WINDOW = 64                 # BAZ_MUSIC_MAX_AVG_WINDOW
 ORDER_MODES = {None: 0, "mdl": 1, "aic": 2}   # baz_music_set_order_mode: criterion by name
@@ -286,6 +291,21 @@ def _bind(L):
     L.baz_music_beamspace_apply.argtypes = [_u32, _u32, _f64p, ctypes.c_int, _f32p, _u32, _f32p]
     L.baz_music_beamspace_design.restype = ctypes.c_int
     L.baz_music_beamspace_design.argtypes = [_u32, _u32, _f32p, _u32, _u32, _u32, _f64p, _f64p]
+    _u32p = ctypes.POINTER(_u32)
+    L.baz_music_set_subbands.restype = ctypes.c_int
+    L.baz_music_set_subbands.argtypes = [_vp, _u32, _u32, _u32p, _f32p, ctypes.c_int]
+    L.baz_music_set_subband_tables.restype = ctypes.c_int
+    L.baz_music_set_subband_tables.argtypes = [_vp, _f32p]
+    L.baz_music_get_subbands.restype = ctypes.c_int
+    L.baz_music_get_subbands.argtypes = [_vp, _u32p, _u32p, _u32p, ctypes.POINTER(ctypes.c_int)]
+    L.baz_music_debug_subbands.restype = ctypes.c_int
+    L.baz_music_debug_subbands.argtypes = [_vp, _vp, _u32, _vp]
+    L.baz_music_debug_subband_combine.restype = ctypes.c_int
+    L.baz_music_debug_subband_combine.argtypes = [_vp, _vp, _u32, _vp]
+    L.baz_music_subband_twiddles.restype = ctypes.c_int
+    L.baz_music_subband_twiddles.argtypes = [_u32, _u32, _u32p, _f64p]
+    L.baz_music_subband_apply.restype = ctypes.c_int
+    L.baz_music_subband_apply.argtypes = [_u32, _u32, _u32, _f64p, _f32p, _u32, _f32p]
     return L
 
 
@@ -699,6 +719,57 @@ class Context:
         """The projection alone: `batch` items (device pointer, m K complex64 each) -> batch K B complex64 at d_out (not overlapping)."""
         self._chk(self._L.baz_music_debug_beamspace(self._h, _vp(d_in), int(batch), _vp(d_out)), "baz_music_debug_beamspace")
 
+    def _subband_tables(self, tables, S):
+        t = np.ascontiguousarray(np.asarray(tables, dtype=np.complex64))
+        if t.shape != (S, self.res, self.m):
+            raise ValueError("tables must be S x resolution x m = %d x %d x %d complex" % (S, self.res, self.m))
+        return t
+
+    def set_subbands(self, F, bins=None, tables=None, combine=SUBBAND_HARMONIC):
+        """Opt-in extension (not reference behaviour): wideband (subband) MUSIC.  Every item is cut into blocks of `F` samples, an F-point
+        DFT per antenna separates the subbands `bins` (distinct DFT indices below F), an inner context per subband runs on
+        `tables[s]` (S x resolution x m complex) and the S spectra are combined (`combine`: SUBBAND_HARMONIC, the sum of the MUSIC
+        denominators, or SUBBAND_ARITHMETIC) into the row the pickers read (include/baz_music_hip.h).  F None or 0: off (the default)."""
+        if not F:
+            self._chk(self._L.baz_music_set_subbands(self._h, 0, 0, None, None, 0), "baz_music_set_subbands")
+            return
+        b = np.ascontiguousarray(np.asarray(bins, dtype=np.int64).reshape(-1))
+        if b.size < 1 or (b < 0).any() or (b > 0xffffffff).any():
+            raise ValueError("bins must be a non-empty list of DFT indices")
+        b = b.astype(np.uint32)
+        t = self._subband_tables(tables, b.size)
+        self._chk(self._L.baz_music_set_subbands(self._h, int(F), b.size, b.ctypes.data_as(ctypes.POINTER(_u32)),
+                                                 t.view(np.float32).ctypes.data_as(_f32p), int(combine)), "baz_music_set_subbands")
+
+    def set_subband_tables(self, tables):
+        """Retunes all S subband tables at once (S x resolution x m complex): a batch sees all old tables or all new ones."""
+        cur = self.get_subbands()
+        if cur is None:
+            raise MusicError(E_UNSUPPORTED, "baz_music_set_subband_tables: the subband mode is off")
+        t = self._subband_tables(tables, len(cur[1]))
+        self._chk(self._L.baz_music_set_subband_tables(self._h, t.view(np.float32).ctypes.data_as(_f32p)), "baz_music_set_subband_tables")
+
+    def get_subbands(self):
+        """(F, bins, combine) in force, or None while the mode is off."""
+        F, S, cmb = _u32(0), _u32(0), ctypes.c_int(0)
+        self._chk(self._L.baz_music_get_subbands(self._h, ctypes.byref(F), ctypes.byref(S), None, ctypes.byref(cmb)), "baz_music_get_subbands")
+        if not F.value:
+            return None
+        bins = np.zeros(MAX_SUBBANDS, np.uint32)
+        self._chk(self._L.baz_music_get_subbands(self._h, ctypes.byref(F), ctypes.byref(S), bins.ctypes.data_as(ctypes.POINTER(_u32)),
+                                                 ctypes.byref(cmb)), "baz_music_get_subbands")
+        return int(F.value), [int(k) for k in bins[:S.value]], int(cmb.value)
+
+    def debug_subbands(self, d_in, batch, d_out):
+        """The channeliser alone: `batch` items (device pointer, m K complex64 each) -> S batch (K/F) m complex64 at d_out, laid out
+        [subband][item][block][antenna] (not overlapping)."""
+        self._chk(self._L.baz_music_debug_subbands(self._h, _vp(d_in), int(batch), _vp(d_out)), "baz_music_debug_subbands")
+
+    def debug_subband_combine(self, d_spectra, batch, d_out):
+        """The combine alone under the S and the rule in force: S batch resolution float32 ([subband][item][bin], device pointer) ->
+        batch resolution float32 at d_out (not overlapping)."""
+        self._chk(self._L.baz_music_debug_subband_combine(self._h, _vp(d_spectra), int(batch), _vp(d_out)), "baz_music_debug_subband_combine")
+
     def mean_covariance(self, items):
         """The mean covariance Rbar (m x m complex128) of items ((batch, nsamples) complex64 host array): calibrate()'s Rbar without
         a pilot -- of a noise-only capture, an estimate of the noise covariance for set_noise_covariance.  Blocks; changes nothing."""
@@ -928,6 +999,41 @@ def beamspace_apply(T, x, normalise=False):
                                         out.view(np.float32).ctypes.data_as(_f32p))
     if r != OK:
         raise ValueError("baz_music_beamspace_apply: %s" % lib().baz_music_strerror(r).decode())
+    return out
+
+
+def subband_twiddles(F, bins):
+    """HOST-ONLY: the twiddles W (S x F complex128) of the subband mode for block length F and the DFT indices `bins`:
+    W[s][t] = exp(-2 pi i ((k_s t) mod F) / F) / sqrt(F) by the library's definition; needs no device."""
+    b = np.asarray(bins, dtype=np.int64).reshape(-1)
+    if int(F) < 0 or int(F) > 0xffffffff or (b < 0).any() or (b > 0xffffffff).any():
+        raise ValueError("subband_twiddles: negative argument")
+    b = np.ascontiguousarray(b.astype(np.uint32))
+    W = np.zeros((max(b.size, 1), max(int(F), 1)), np.complex128)
+    r = lib().baz_music_subband_twiddles(int(F), b.size, b.ctypes.data_as(ctypes.POINTER(_u32)),
+                                         W.view(np.float64).ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    if r != OK:
+        raise ValueError("baz_music_subband_twiddles: %s" % lib().baz_music_strerror(r).decode())
+    return W
+
+
+def subband_apply(W, x):
+    """HOST-ONLY: the channeliser of the subband mode by the library's definition (the kernel's own routine, bit for bit; needs no
+    device).  `W`: S x F complex128; `x`: (..., F, m) complex64, blocks of F snapshots of m antennas.  Returns (S, ..., m) complex64:
+    y[s, ..., r] = fl32(sum_t W[s, t] x[..., t, r])."""
+    w = np.ascontiguousarray(np.asarray(W, dtype=np.complex128))
+    if w.ndim != 2:
+        raise ValueError("subband_apply: W must be S x F")
+    v = np.ascontiguousarray(np.asarray(x, dtype=np.complex64))
+    if v.ndim < 2 or v.shape[-2] != w.shape[1]:
+        raise ValueError("subband_apply: x must be (..., F, m) with F = %d" % w.shape[1])
+    m = v.shape[-1]
+    blocks = v.size // max(w.shape[1] * m, 1)
+    out = np.zeros((w.shape[0],) + v.shape[:-2] + (m,), np.complex64)
+    r = lib().baz_music_subband_apply(m, w.shape[1], w.shape[0], w.view(np.float64).ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                      v.view(np.float32).ctypes.data_as(_f32p), blocks, out.view(np.float32).ctypes.data_as(_f32p))
+    if r != OK:
+        raise ValueError("baz_music_subband_apply: %s" % lib().baz_music_strerror(r).decode())
     return out
 
 

@@ -21,6 +21,7 @@
 #include "calib_kernels.hip.h"
 #include "whiten_kernels.hip.h"
 #include "beamspace_kernels.hip.h"
+#include "subband_kernels.hip.h"
 #include "average_kernels.hip.h"
 #include "spectrum_kernels.hip.h"
 #include "device_buffer.hip.h"
@@ -409,13 +410,25 @@ struct baz_music_ctx {
     // DESIGN.md 8k) is the same construction with a projection kernel where the gather is (kind == FRONT_BEAMSPACE: ms = B beams,
     // Kp = K, the inner context of shape (B, n, B K, res) on the table T^H a).  The two kinds exclude each other; what every forwarder
     // below does for `inner` serves both.
-    enum { FRONT_SMOOTHING = 0, FRONT_BEAMSPACE = 1 };
+    //
+    // The opt-in wideband (subband) mode (baz_music_set_subbands; subband_kernels.hip.h) is a front-end that drives S inner
+    // contexts instead of one (kind == FRONT_SUBBAND): `inner` is subband 0, `sb_more` holds subbands 1 .. S-1, each of shape
+    // (m, n, m K / F, res) on its own table; ms = m and Kp = S K / F, so that Kp ms is the size of a channelised item as it is for
+    // the two other kinds.  The forwarders that serve `inner` serve every subband (each_inner); the pickers run on this context.
+    enum { FRONT_SMOOTHING = 0, FRONT_BEAMSPACE = 1, FRONT_SUBBAND = 2 };
     struct Smoothing {
         baz_music_ctx* inner = nullptr;
         int kind = FRONT_SMOOTHING;              // which front-end feeds `inner` (meaningful while it is set)
         int bs_norm = 0;                         // beamspace: rows of the table T^H a scaled to unit norm
         std::vector<double> bs_T;                // beamspace: T as given (m x B complex128), for get_beamspace and retunes
         DevBuf<double2> dTc;                     // beamspace: conj(T), [m][B], what beamspace_kernel reads
+        std::vector<baz_music_ctx*> sb_more;     // subband: the inner contexts of subbands 1 .. S-1
+        uint32_t sb_F = 0, sb_S = 0;             // subband: block length, used subbands
+        int sb_combine = 0;                      // subband: BAZ_MUSIC_SUBBAND_HARMONIC / _ARITHMETIC
+        std::vector<uint32_t> sb_bins;           // subband: the DFT indices k_s as given
+        DevBuf<double2> dW;                      // subband: the twiddles W, [S][F], what subband_kernel reads
+        DevBuf<float> dPs;                       // subband: the chunk's S private spectra, [s][item][bin]
+        DevBuf<float> dRow;                      // subband: the chunk's combined rows while port 2 is not wired
         uint32_t ms = 0, L = 1, Kp = 0;          // subarray size, subarrays, columns of a re-stacked item
         int fb = 0;
         bazsmooth::Perm perm = {};
@@ -2829,6 +2842,114 @@ int launch_beamspace(baz_music_ctx* c, const float2* d_in, uint32_t columns, flo
 #undef BAZ_CALL
 }
 
+// ---- opt-in wideband (subband) front-end (baz_music_set_subbands; subband_kernels.hip.h) --------------------------------------------
+inline bool subband_on(const baz_music_ctx* c) { return c->sm.inner && c->sm.kind == baz_music_ctx::FRONT_SUBBAND; }
+
+// f(inner context) for every inner context of the front-end in force (one, or the S of the subband mode), until one fails
+template <typename Fn>
+int each_inner(baz_music_ctx* c, Fn f)
+{
+    if (!c->sm.inner) return BAZ_MUSIC_OK;
+    if (const int r = f(c->sm.inner)) return r;
+    for (baz_music_ctx* in : c->sm.sb_more)
+        if (const int r = f(in)) return r;
+    return BAZ_MUSIC_OK;
+}
+
+// W[s][t] = exp(-2 pi i ((k_s t) mod F) / F) / sqrt(F): the quarter points exactly, everything else evaluated in long double and rounded once
+void subband_twiddles_host(uint32_t F, uint32_t S, const uint32_t* bins, double* W_out)
+{
+    const long double two_pi = 6.283185307179586476925286766559005768L;
+    const long double scale = 1.0L / sqrtl((long double)F);
+    for (uint32_t s = 0; s < S; ++s)
+        for (uint32_t t = 0; t < F; ++t) {
+            const uint32_t j = (uint32_t)(((uint64_t)bins[s] * t) % F);
+            long double re, im;
+            if ((4u * j) % F == 0) {
+                static const int qr[4] = {1, 0, -1, 0}, qi[4] = {0, -1, 0, 1};
+                re = (long double)qr[4u * j / F] * scale;
+                im = (long double)qi[4u * j / F] * scale;
+            } else {
+                const long double ph = two_pi * (long double)j / (long double)F;
+                re = cosl(ph) * scale;
+                im = -sinl(ph) * scale;
+            }
+            W_out[2 * ((size_t)s * F + t)] = (double)re;
+            W_out[2 * ((size_t)s * F + t) + 1] = (double)im;
+        }
+}
+
+// `blocks` blocks of F x m complex64 -> out [s][block][r] on the host (the definition's own routine)
+void subband_apply_host(uint32_t m, uint32_t F, uint32_t S, const double* W_ri, const float* in_ri, size_t blocks, float* out_ri)
+{
+    const double2* const w = reinterpret_cast<const double2*>(W_ri);
+    const float2* const x = reinterpret_cast<const float2*>(in_ri);
+    float2* const y = reinterpret_cast<float2*>(out_ri);
+    for (uint32_t s = 0; s < S; ++s)
+        for (size_t b = 0; b < blocks; ++b)
+            for (uint32_t r = 0; r < m; ++r) {
+                double re[1], im[1];
+                bazsubband::subband_entry<1>(w + (size_t)s * F, 1u, x + b * F * m + r, m, F, re, im);
+                y[((size_t)s * blocks + b) * m + r] = make_float2((float)re[0], (float)im[0]);
+            }
+}
+
+template <int SQ>
+int launch_subband_t(baz_music_ctx* c, const float2* d_in, uint32_t columns, float2* d_out)
+{
+    const auto& S = c->sm;
+    const uint32_t tiles = (columns + bazsubband::SB_TILE - 1u) / bazsubband::SB_TILE;
+    const uint32_t blocks = std::min<uint32_t>(tiles, 2u * c->num_cus);      // two workgroups fit a CU's LDS at the largest shape (78 KiB)
+    hipLaunchKernelGGL((bazsubband::subband_kernel<SQ>), dim3(blocks), dim3(bazsubband::SB_THREADS), bazsubband::sb_lds_bytes(c->m, S.sb_F, S.sb_S),
+                       c->stream, d_in, d_out, S.dW.get(), c->m, S.sb_F, S.sb_S, columns);
+    HIP_TRY(c, hipGetLastError());
+    return BAZ_MUSIC_OK;
+}
+
+// the channeliser over `nb` items (c->mtx held, the mode on): d_out is [s][item][q][r]
+int launch_subband(baz_music_ctx* c, const float2* d_in, uint32_t nb, float2* d_out)
+{
+    const auto& S = c->sm;
+    if (!S.dW || !S.sb_F || S.sb_S < 1 || S.sb_S > BAZ_MUSIC_MAX_SUBBANDS || c->K % S.sb_F) return BAZ_MUSIC_E_INVALID;
+    const uint64_t columns = (uint64_t)nb * (c->K / S.sb_F) * c->m;
+    if (columns == 0 || columns * S.sb_F > 0xffffffffull) return BAZ_MUSIC_E_INVALID;
+    switch ((S.sb_S + 3u) / 4u) {
+        case 1: return launch_subband_t<1>(c, d_in, (uint32_t)columns, d_out);
+        case 2: return launch_subband_t<2>(c, d_in, (uint32_t)columns, d_out);
+        case 3: return launch_subband_t<3>(c, d_in, (uint32_t)columns, d_out);
+        case 4: return launch_subband_t<4>(c, d_in, (uint32_t)columns, d_out);
+        case 5: return launch_subband_t<5>(c, d_in, (uint32_t)columns, d_out);
+        case 6: return launch_subband_t<6>(c, d_in, (uint32_t)columns, d_out);
+        case 7: return launch_subband_t<7>(c, d_in, (uint32_t)columns, d_out);
+        case 8: return launch_subband_t<8>(c, d_in, (uint32_t)columns, d_out);
+        default: return BAZ_MUSIC_E_UNSUPPORTED;
+    }
+}
+
+// dynamic LDS beyond 64 KiB needs the attribute; it is per FUNCTION, so it is set for the largest shape, never for one context's
+int subband_lds_attribute(baz_music_ctx* c)
+{
+    int most = 0;
+    for (uint32_t m = 2; m <= BAZ_MUSIC_FAST_M; ++m) most = std::max(most, (int)bazsubband::sb_lds_bytes(m, 64u, BAZ_MUSIC_MAX_SUBBANDS));
+    const void* fn[8] = {reinterpret_cast<const void*>(bazsubband::subband_kernel<1>), reinterpret_cast<const void*>(bazsubband::subband_kernel<2>),
+                         reinterpret_cast<const void*>(bazsubband::subband_kernel<3>), reinterpret_cast<const void*>(bazsubband::subband_kernel<4>),
+                         reinterpret_cast<const void*>(bazsubband::subband_kernel<5>), reinterpret_cast<const void*>(bazsubband::subband_kernel<6>),
+                         reinterpret_cast<const void*>(bazsubband::subband_kernel<7>), reinterpret_cast<const void*>(bazsubband::subband_kernel<8>)};
+    for (const void* f : fn) HIP_TRY(c, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, most));
+    return BAZ_MUSIC_OK;
+}
+
+// the S spectra of a chunk ([s][item][bin]) -> one row per item
+int launch_subband_combine(baz_music_ctx* c, const float* d_ps, uint32_t nb, float* d_row)
+{
+    const size_t total = (size_t)nb * c->res;
+    const uint32_t blocks = (uint32_t)std::min<size_t>((total + bazsubband::SBC_THREADS - 1) / bazsubband::SBC_THREADS, 64u * c->num_cus);
+    hipLaunchKernelGGL(bazsubband::subband_combine_kernel, dim3(blocks), dim3(bazsubband::SBC_THREADS), 0, c->stream, d_ps, d_row,
+                       c->sm.sb_S, total, c->sm.sb_combine);
+    HIP_TRY(c, hipGetLastError());
+    return BAZ_MUSIC_OK;
+}
+
 // ---- opt-in forward-backward averaging / spatial smoothing (baz_music_set_smoothing) ------------------------------------------
 // Structure checks on the fp32 table (include/baz_music_hip.h documents them).  Every product is formed in fp64 from the fp32
 // entries; a relation holds at a bin when its residual is at most SMOOTH_TOL times the bin's scale s = max_k |a_k|^2.
@@ -2953,7 +3074,9 @@ std::vector<float> sub_table(const float* table_ri, uint32_t m, uint32_t res, ui
 // items per chunk: the re-stacked chunk stays within BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES (at least one item)
 uint32_t smooth_chunk(const baz_music_ctx* c, uint32_t batch)
 {
-    const size_t per_item = (size_t)c->sm.Kp * c->sm.ms * sizeof(float2);
+    size_t per_item = (size_t)c->sm.Kp * c->sm.ms * sizeof(float2);
+    if (c->sm.kind == baz_music_ctx::FRONT_SUBBAND)   // (... and so do the S private spectrum rows of an item)
+        per_item = std::max(per_item, (size_t)c->sm.sb_S * c->res * sizeof(float));
     return (uint32_t)std::max<size_t>(1, std::min<size_t>(batch, (size_t)BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES / per_item));
 }
 
@@ -2972,10 +3095,47 @@ int launch_restack(baz_music_ctx* c, const void* d_in, uint32_t nb)
     return BAZ_MUSIC_OK;
 }
 
+// process_device with the subband mode on (c->mtx held): per chunk, the channeliser into dY ([s][item][q][r]: subband s's items are
+// one contiguous batch), inner context s on its batch with its spectrum port wired into dPs, the combine into the caller's spectrum
+// (or the private row), then a picker of THIS context on the combined rows.  An inner context's own ang goes where the picker's will
+// (the same stream: the picker writes last); its lvl port stays unwired.
+int subband_device_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, void* d_ang, void* d_lvl, void* d_spec)
+{
+    auto& S = c->sm;
+    const uint32_t chunk = smooth_chunk(c, batch);
+    const size_t per_sub = (size_t)(c->K / S.sb_F) * c->m;        // complex64 of one subband's item
+    int r = grow(c, S.dY, (size_t)chunk * S.Kp * S.ms);
+    if (r == BAZ_MUSIC_OK) r = grow(c, S.dPs, (size_t)chunk * S.sb_S * c->res);
+    if (r == BAZ_MUSIC_OK && !d_spec) r = grow(c, S.dRow, (size_t)chunk * c->res);
+    baz_music_ctx* failed = nullptr;
+    for (uint32_t done = 0; done < batch && r == BAZ_MUSIC_OK; done += chunk) {
+        const uint32_t nb = std::min(chunk, batch - done);
+        float* const ang = static_cast<float*>(d_ang) + (size_t)done * c->n;
+        float* const row = d_spec ? static_cast<float*>(d_spec) + (size_t)done * c->res : S.dRow.get();
+        r = launch_subband(c, static_cast<const float2*>(d_in) + (size_t)done * c->nsamples, nb, S.dY);
+        uint32_t s = 0;
+        if (r == BAZ_MUSIC_OK)
+            r = each_inner(c, [&](baz_music_ctx* in) {
+                const int ri = baz_music_process_device(in, S.dY + (size_t)s * nb * per_sub, nb, ang, nullptr, S.dPs + (size_t)s * nb * c->res);
+                if (ri) failed = in;
+                ++s;
+                return ri;
+            });
+        if (r == BAZ_MUSIC_OK) r = launch_subband_combine(c, S.dPs, nb, row);
+        if (r == BAZ_MUSIC_OK) {
+            float* const lvl = d_lvl ? static_cast<float*>(d_lvl) + (size_t)done * c->n : nullptr;
+            r = c->peak_mode ? launch_peaks(c, nb, ang, lvl, row) : launch_topn_spec(c, nb, ang, lvl, row);
+        }
+    }
+    if (r == BAZ_MUSIC_E_HIP && failed) snprintf(c->hip_err, sizeof(c->hip_err), "%s", baz_music_last_hip_error(failed));
+    return r;
+}
+
 // process_device with the mode on (c->mtx held): per chunk, re-stack into dY and run the inner context on the same stream
 int smooth_device_locked(baz_music_ctx* c, const void* d_in, uint32_t batch, void* d_ang, void* d_lvl, void* d_spec)
 {
     auto& S = c->sm;
+    if (S.kind == baz_music_ctx::FRONT_SUBBAND) return subband_device_locked(c, d_in, batch, d_ang, d_lvl, d_spec);
     const uint32_t chunk = smooth_chunk(c, batch);
     int r = grow(c, S.dY, (size_t)chunk * S.Kp * S.ms);
     for (uint32_t done = 0; done < batch && r == BAZ_MUSIC_OK; done += chunk) {
@@ -3226,6 +3386,8 @@ void baz_music_destroy(baz_music_ctx* c)
     DeviceGuard guard(c->device);
     if (c->sm.inner) baz_music_destroy(c->sm.inner);   // (drains this context's stream: the inner one launches on it)
     c->sm.inner = nullptr;
+    for (baz_music_ctx* in : c->sm.sb_more) baz_music_destroy(in);   // (the subband mode's other inner contexts)
+    c->sm.sb_more.clear();
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->s_tab) (void)hipStreamSynchronize(c->s_tab);
     for (auto& p : c->prof)
@@ -3244,7 +3406,7 @@ int baz_music_set_table(baz_music_ctx* c, const float* table_ri)
     if (!c || !table_ri) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> tl(c->tab_mtx);   // one retune at a time; work() is held up for the pointer exchange only (retune())
     DeviceGuard guard(c->device);
-    if (!c->sm.inner) return retune(c, table_ri, false);
+    if (!c->sm.inner || c->sm.kind == baz_music_ctx::FRONT_SUBBAND) return retune(c, table_ri, false);   // (subband on: the table "off" returns to)
     if (c->sm.kind == baz_music_ctx::FRONT_BEAMSPACE) {   // beamspace on: a' of the new table under the T in force, forwarded
         const std::vector<float> proj = beamspace_table(c, table_ri);
         const int rb = retune(c, table_ri, false);
@@ -3280,7 +3442,7 @@ int baz_music_set_stream(baz_music_ctx* c, void* hip_stream)
     DeviceGuard guard(c->device);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->own_stream;
-    return c->sm.inner ? baz_music_set_stream(c->sm.inner, c->stream) : BAZ_MUSIC_OK;
+    return each_inner(c, [&](baz_music_ctx* in) { return baz_music_set_stream(in, c->stream); });
 }
 
 int baz_music_sync(baz_music_ctx* c)
@@ -3304,8 +3466,9 @@ int baz_music_reserve(baz_music_ctx* c, uint32_t max_batch)
     }
     if (c->sm.inner) {   // smoothing on: the inner context's workspace for one chunk, and the re-stacked chunk
         const uint32_t chunk = smooth_chunk(c, max_batch);
-        const int rs = grow(c, c->sm.dY, (size_t)chunk * c->sm.Kp * c->sm.ms);
-        return rs ? rs : baz_music_reserve(c->sm.inner, chunk);
+        int rs = grow(c, c->sm.dY, (size_t)chunk * c->sm.Kp * c->sm.ms);
+        if (rs == BAZ_MUSIC_OK && subband_on(c)) rs = grow(c, c->sm.dPs, (size_t)chunk * c->sm.sb_S * c->res);
+        return rs ? rs : each_inner(c, [&](baz_music_ctx* in) { return baz_music_reserve(in, chunk); });
     }
     // averaging: both history buffers and the averaged covariances of the largest launch; whitening: its R' (and the pass between the
     // two products at 17 .. 64 antennas)
@@ -4147,7 +4310,7 @@ int baz_music_set_peak_mode(baz_music_ctx* c, int mode)
     if (!c || (mode != 0 && mode != 1)) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
     if (mode && c->wide && !beamspace_on(c)) return BAZ_MUSIC_E_UNSUPPORTED;   // the opt-in picker exists for the specialised kernels only (beamspace: the inner context runs them)
-    if (c->sm.inner) {   // (the inner context is never wider than this one)
+    if (c->sm.inner && !subband_on(c)) {   // (the inner context is never wider than this one; subband: the picker of THIS context reads the combined row)
         const int r = baz_music_set_peak_mode(c->sm.inner, mode);
         if (r != BAZ_MUSIC_OK) return r;
     }
@@ -4185,7 +4348,7 @@ int baz_music_set_smoothing(baz_music_ctx* c, uint32_t subarray, int forward_bac
     std::lock_guard<std::mutex> tl(c->tab_mtx);   // against set_table: c->hRaw is the table in force while it is held
     DeviceGuard guard(c->device);
     baz_music_ctx* old = nullptr;
-    if (c->sm.inner && c->sm.kind == baz_music_ctx::FRONT_BEAMSPACE)   // (two front-ends would compete for one inner context; sm changes under tab_mtx + mtx)
+    if (c->sm.inner && c->sm.kind != baz_music_ctx::FRONT_SMOOTHING)   // (two front-ends would compete for one inner context; sm changes under tab_mtx + mtx)
         return (subarray == c->m && !fb) ? BAZ_MUSIC_OK : BAZ_MUSIC_E_UNSUPPORTED;
     if (subarray == c->m && !fb) {                // off: the reference
         {
@@ -4245,6 +4408,7 @@ int baz_music_set_order_mode(baz_music_ctx* c, int criterion)
     std::lock_guard<std::mutex> lk(c->mtx);
     if (criterion && c->wide && !beamspace_on(c)) return BAZ_MUSIC_E_UNSUPPORTED;   // the ORDER epilogues exist for the specialised kernels only
     if (criterion && c->estimator) return BAZ_MUSIC_E_UNSUPPORTED;   // (Capon / Bartlett compute no eigenvalues)
+    if (criterion && subband_on(c)) return BAZ_MUSIC_E_UNSUPPORTED;  // (one count per subband: no rule combines them here)
     if (c->sm.inner) {   // (the inner context is never wider than this one)
         const int r = baz_music_set_order_mode(c->sm.inner, criterion);
         if (r != BAZ_MUSIC_OK) return r;
@@ -4303,6 +4467,7 @@ int baz_music_set_refine_mode(baz_music_ctx* c, int mode)
     std::lock_guard<std::mutex> lk(c->mtx);
     if (mode && c->wide && !beamspace_on(c)) return BAZ_MUSIC_E_UNSUPPORTED;   // no peak picker on the run-time-m path: only first entries would move
     if (mode && c->estimator) return BAZ_MUSIC_E_UNSUPPORTED;   // (the fit is on the MUSIC denominator)
+    if (mode && subband_on(c)) return BAZ_MUSIC_E_UNSUPPORTED;  // (the combined row has no single denominator to fit)
     if (c->sm.inner) {   // (the inner context is never wider than this one)
         const int r = baz_music_set_refine_mode(c->sm.inner, mode);
         if (r != BAZ_MUSIC_OK) return r;
@@ -4340,7 +4505,7 @@ int baz_music_set_averaging(baz_music_ctx* c, uint32_t window, double forgetting
     std::lock_guard<std::mutex> lk(c->mtx);
     DeviceGuard guard(c->device);
     if (c->sm.inner) {            // smoothing on: the inner context averages (and keeps the history); this one only remembers the mode
-        const int r = baz_music_set_averaging(c->sm.inner, window, forgetting);
+        const int r = each_inner(c, [&](baz_music_ctx* in) { return baz_music_set_averaging(in, window, forgetting); });   // (subband: each its own stream)
         if (r != BAZ_MUSIC_OK) return r;
     } else if (window > 1) {      // the history buffers, before anything changes: after an error the previous mode and history stay in force
         const int r = ensure_average(c, window, 0);
@@ -4368,7 +4533,7 @@ int baz_music_reset_averaging(baz_music_ctx* c)
     if (!c) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
     c->avg_hist = 0;
-    return c->sm.inner ? baz_music_reset_averaging(c->sm.inner) : BAZ_MUSIC_OK;
+    return each_inner(c, [](baz_music_ctx* in) { return baz_music_reset_averaging(in); });
 }
 
 int baz_music_averaging_weights(uint32_t window, double forgetting, double* w, double* inv_norm, double* n_eff)
@@ -4400,6 +4565,7 @@ int baz_music_set_power_mode(baz_music_ctx* c, int mode)
     if (!c || mode < 0 || mode > 2) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(c->mtx);
     if (mode && c->wide && !beamspace_on(c)) return BAZ_MUSIC_E_UNSUPPORTED;   // (power_kernel is specialised per m, like the pickers it follows)
+    if (mode && subband_on(c)) return BAZ_MUSIC_E_UNSUPPORTED;   // (a power per subband: no single covariance to solve on)
     if (c->sm.inner) {   // (the inner context is never wider than this one)
         const int r = baz_music_set_power_mode(c->sm.inner, mode);
         if (r != BAZ_MUSIC_OK) return r;
@@ -4441,10 +4607,10 @@ int baz_music_set_estimator(baz_music_ctx* c, int kind)
     std::lock_guard<std::mutex> lk(c->mtx);
     if (kind && c->wide && !beamspace_on(c)) return BAZ_MUSIC_E_UNSUPPORTED;   // (spectrum_scan_kernel is specialised per m, like the other modes' kernels)
     // the emitter-count mode needs eigenvalues, refinement fits the MUSIC denominator, smoothing runs an inner MUSIC context
-    if (kind && (c->order_mode || c->refine_mode || (c->sm.inner && !beamspace_on(c)))) return BAZ_MUSIC_E_UNSUPPORTED;
+    if (kind && (c->order_mode || c->refine_mode || (c->sm.inner && !beamspace_on(c) && !subband_on(c)))) return BAZ_MUSIC_E_UNSUPPORTED;
     if (kind && c->wh_want) return BAZ_MUSIC_E_UNSUPPORTED;   // (whitening on: Capon is invariant under the transform, nothing is gained)
-    if (beamspace_on(c)) {   // beamspace: the inner context evaluates the estimator on the projected items
-        const int r = baz_music_set_estimator(c->sm.inner, kind);
+    if (beamspace_on(c) || subband_on(c)) {   // beamspace: the inner context evaluates the estimator on the projected items; subband: all S do
+        const int r = each_inner(c, [&](baz_music_ctx* in) { return baz_music_set_estimator(in, kind); });
         if (r != BAZ_MUSIC_OK) return r;
     }
     c->estimator = kind;
@@ -4901,6 +5067,192 @@ int baz_music_debug_beamspace(baz_music_ctx* c, const void* d_in, uint32_t batch
     return launch_beamspace(c, static_cast<const float2*>(d_in), batch * c->K, static_cast<float2*>(d_out));
 }
 
+// ---- opt-in wideband (subband) front-end: the host side (include/baz_music_hip.h; subband_kernels.hip.h) ---------------------------
+namespace {
+// 2 <= F <= 64, 1 <= S <= BAZ_MUSIC_MAX_SUBBANDS, S distinct bins below F
+bool subband_bins_ok(uint32_t F, uint32_t S, const uint32_t* bins)
+{
+    if (F < 2 || F > 64 || S < 1 || S > BAZ_MUSIC_MAX_SUBBANDS || !bins) return false;
+    uint64_t seen = 0;
+    for (uint32_t s = 0; s < S; ++s) {
+        if (bins[s] >= F || ((seen >> bins[s]) & 1u)) return false;
+        seen |= 1ull << bins[s];
+    }
+    return true;
+}
+
+// Builds the S inner contexts and the twiddles beside the running stream and exchanges them with the setting in force under c->mtx
+// (c->tab_mtx held).  Both setters end here: a batch sees all S old tables or all S new ones.
+int subband_install(baz_music_ctx* c, uint32_t F, uint32_t S, const uint32_t* bins, const float* tables_ri, int combine)
+{
+    const uint32_t Q = c->K / F;
+    const size_t tab_words = (size_t)c->res * c->m * 2;
+    std::vector<baz_music_ctx*> fresh;
+    const auto drop = [&](int rc) {
+        for (baz_music_ctx* in : fresh) baz_music_destroy(in);
+        return rc;
+    };
+    int r = BAZ_MUSIC_OK;
+    for (uint32_t s = 0; s < S && r == BAZ_MUSIC_OK; ++s) {
+        baz_music_ctx* in = nullptr;
+        r = baz_music_create(&in, c->m, c->n, c->m * Q, c->res, tables_ri + (size_t)s * tab_words, c->device);
+        if (r == BAZ_MUSIC_OK) fresh.push_back(in);
+    }
+    if (r != BAZ_MUSIC_OK) return drop(r);
+    DevBuf<double2> w;
+    {
+        std::vector<double> h((size_t)2 * S * F);
+        subband_twiddles_host(F, S, bins, h.data());
+        hipError_t e = w.allocate((size_t)S * F);
+        if (e == hipSuccess) e = hipMemcpy(w.get(), h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return drop(hip_fail(c, e, "subbands: W"));
+    }
+    if ((r = subband_lds_attribute(c)) != BAZ_MUSIC_OK) return drop(r);
+    std::vector<baz_music_ctx*> old;
+    DevBuf<double2> old_w;
+    DevBuf<float2> old_y;
+    DevBuf<float> old_ps, old_row;
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);   // a batch sees the old setting or the new one
+        if (c->order_mode || c->refine_mode || c->power_mode || c->beam_mode) r = BAZ_MUSIC_E_UNSUPPORTED;   // (a setter may have come in between)
+        for (baz_music_ctx* in : fresh) {
+            if (r == BAZ_MUSIC_OK) r = baz_music_set_stream(in, c->stream);
+            if (r == BAZ_MUSIC_OK) r = baz_music_set_estimator(in, c->estimator);
+            if (r == BAZ_MUSIC_OK) r = baz_music_set_averaging(in, c->avg_window, c->avg_beta);   // (a new inner context: an empty history)
+        }
+        if (r == BAZ_MUSIC_OK) {
+            for (baz_music_ctx* in : fresh) in->ord_driven = true;   // (this context opens the call)
+            if (c->sm.inner) old.push_back(c->sm.inner);
+            old.insert(old.end(), c->sm.sb_more.begin(), c->sm.sb_more.end());
+            old_w = std::move(c->sm.dW);
+            old_y = std::move(c->sm.dY); old_ps = std::move(c->sm.dPs); old_row = std::move(c->sm.dRow);   // (sized for the old S and F)
+            c->sm.inner = fresh[0];
+            c->sm.sb_more.assign(fresh.begin() + 1, fresh.end());
+            c->sm.dW = std::move(w);
+            c->sm.kind = baz_music_ctx::FRONT_SUBBAND;
+            c->sm.ms = c->m; c->sm.L = 1; c->sm.Kp = S * Q; c->sm.fb = 0;
+            c->sm.sb_F = F; c->sm.sb_S = S; c->sm.sb_combine = combine;
+            c->sm.sb_bins.assign(bins, bins + S);
+            c->out_beam.on = false;
+            c->out_beam.count = 0;
+            fresh.clear();
+        }
+    }
+    for (baz_music_ctx* in : old) baz_music_destroy(in);   // (drains the stream; the retired W and workspace go after it)
+    return drop(r);
+}
+}  // namespace
+
+int baz_music_subband_twiddles(uint32_t F, uint32_t S, const uint32_t* bins, double* W_out)
+{
+    if (!subband_bins_ok(F, S, bins) || !W_out) return BAZ_MUSIC_E_INVALID;
+    subband_twiddles_host(F, S, bins, W_out);
+    return BAZ_MUSIC_OK;
+}
+
+int baz_music_subband_apply(uint32_t m, uint32_t F, uint32_t S, const double* W_ri, const float* in_ri, uint32_t blocks, float* out_ri)
+{
+    if (m < 2 || m > BAZ_MUSIC_FAST_M || F < 2 || F > 64 || S < 1 || S > BAZ_MUSIC_MAX_SUBBANDS || !W_ri) return BAZ_MUSIC_E_INVALID;
+    if (blocks == 0) return BAZ_MUSIC_OK;
+    if (!in_ri || !out_ri) return BAZ_MUSIC_E_INVALID;
+    subband_apply_host(m, F, S, W_ri, in_ri, blocks, out_ri);
+    return BAZ_MUSIC_OK;
+}
+
+int baz_music_set_subbands(baz_music_ctx* c, uint32_t F, uint32_t S, const uint32_t* bins, const float* tables_ri, int combine)
+{
+    if (!c) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> tl(c->tab_mtx);   // against set_table and the other front-ends: sm changes under tab_mtx + mtx
+    DeviceGuard guard(c->device);
+    if (F == 0) {
+        std::vector<baz_music_ctx*> old;
+        DevBuf<double2> old_w;
+        DevBuf<float2> old_y;                     // the front-end's workspace goes with it (released behind the drain below)
+        DevBuf<float> old_x, old_al, old_spec, old_ps, old_row;
+        {
+            std::lock_guard<std::mutex> lk(c->mtx);
+            if (!subband_on(c)) return BAZ_MUSIC_OK;   // (off and staying off; another front-end, if on, is not this mode's to end)
+            old.push_back(c->sm.inner);
+            old.insert(old.end(), c->sm.sb_more.begin(), c->sm.sb_more.end());
+            c->sm.inner = nullptr;
+            c->sm.sb_more.clear();
+            c->sm.kind = baz_music_ctx::FRONT_SMOOTHING;
+            c->sm.ms = 0; c->sm.L = 1; c->sm.Kp = 0; c->sm.fb = 0;
+            c->sm.sb_F = 0; c->sm.sb_S = 0; c->sm.sb_combine = 0;
+            c->sm.sb_bins.clear();
+            old_w = std::move(c->sm.dW);
+            old_y = std::move(c->sm.dY); old_x = std::move(c->sm.dX); old_al = std::move(c->sm.dAl); old_spec = std::move(c->sm.dSpec);
+            old_ps = std::move(c->sm.dPs); old_row = std::move(c->sm.dRow);
+            c->avg_hist = 0;                      // (averaging: the items of R change, the history starts over)
+        }
+        for (baz_music_ctx* in : old) baz_music_destroy(in);   // (drains the stream first: batches in flight may still use them and W)
+        return BAZ_MUSIC_OK;
+    }
+    if (!subband_bins_ok(F, S, bins) || !tables_ri || (combine != BAZ_MUSIC_SUBBAND_HARMONIC && combine != BAZ_MUSIC_SUBBAND_ARITHMETIC))
+        return BAZ_MUSIC_E_INVALID;
+    if (c->K % F) return BAZ_MUSIC_E_INVALID;
+    for (size_t i = 0; i < (size_t)S * c->res * c->m * 2; ++i)
+        if (!(tables_ri[i] - tables_ri[i] == 0.0f)) return BAZ_MUSIC_E_INVALID;
+    if (c->wide) return BAZ_MUSIC_E_UNSUPPORTED;  // (17 .. 64 antennas: the pickers on a float32 row exist for the specialised kernels only)
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);
+        if (c->sm.inner && !subband_on(c)) return BAZ_MUSIC_E_UNSUPPORTED;   // (smoothing or beamspace on: one front-end at a time)
+        if (c->order_mode || c->refine_mode || c->power_mode || c->beam_mode) return BAZ_MUSIC_E_UNSUPPORTED;
+    }
+    if (c->calib_on || c->wh_on) return BAZ_MUSIC_E_UNSUPPORTED;   // (both change under tab_mtx; their per-subband forms are not offered)
+    return subband_install(c, F, S, bins, tables_ri, combine);
+}
+
+int baz_music_set_subband_tables(baz_music_ctx* c, const float* tables_ri)
+{
+    if (!c || !tables_ri) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> tl(c->tab_mtx);
+    DeviceGuard guard(c->device);
+    uint32_t F, S;
+    int combine;
+    std::vector<uint32_t> bins;
+    {
+        std::lock_guard<std::mutex> lk(c->mtx);
+        if (!subband_on(c)) return BAZ_MUSIC_E_UNSUPPORTED;
+        F = c->sm.sb_F; S = c->sm.sb_S; combine = c->sm.sb_combine; bins = c->sm.sb_bins;
+    }
+    for (size_t i = 0; i < (size_t)S * c->res * c->m * 2; ++i)
+        if (!(tables_ri[i] - tables_ri[i] == 0.0f)) return BAZ_MUSIC_E_INVALID;
+    return subband_install(c, F, S, bins.data(), tables_ri, combine);   // (sm cannot change in between: tab_mtx is held)
+}
+
+int baz_music_get_subbands(const baz_music_ctx* c, uint32_t* F, uint32_t* S, uint32_t* bins_out, int* combine)
+{
+    if (!c) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(const_cast<baz_music_ctx*>(c)->mtx);
+    const bool on = subband_on(c);
+    if (F) *F = on ? c->sm.sb_F : 0;
+    if (S) *S = on ? c->sm.sb_S : 0;
+    if (combine) *combine = on ? c->sm.sb_combine : 0;
+    if (bins_out && on) std::memcpy(bins_out, c->sm.sb_bins.data(), c->sm.sb_bins.size() * sizeof(uint32_t));
+    return BAZ_MUSIC_OK;
+}
+
+int baz_music_debug_subbands(baz_music_ctx* c, const void* d_in, uint32_t batch, void* d_out)
+{
+    if (!c || !d_in || !d_out || d_in == d_out || batch == 0) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    DeviceGuard guard(c->device);
+    if (!subband_on(c)) return BAZ_MUSIC_E_UNSUPPORTED;
+    (void)hipGetLastError();
+    return launch_subband(c, static_cast<const float2*>(d_in), batch, static_cast<float2*>(d_out));
+}
+
+int baz_music_debug_subband_combine(baz_music_ctx* c, const void* d_spectra, uint32_t batch, void* d_out)
+{
+    if (!c || !d_spectra || !d_out || d_spectra == d_out || batch == 0) return BAZ_MUSIC_E_INVALID;
+    std::lock_guard<std::mutex> lk(c->mtx);
+    DeviceGuard guard(c->device);
+    if (!subband_on(c)) return BAZ_MUSIC_E_UNSUPPORTED;
+    (void)hipGetLastError();
+    return launch_subband_combine(c, static_cast<const float*>(d_spectra), batch, static_cast<float*>(d_out));
+}
+
 namespace {
 // R-bar of `batch` items (device memory, or host memory staged chunk by chunk through dCalIn) into Rbar (host, 2 m^2 doubles): the
 // covariance stage debug_cov runs, chunk by chunk through the context's R workspace, cov_mean_kernel over each chunk's runs, one fold.
@@ -5128,7 +5480,7 @@ int baz_music_get_smoothing(const baz_music_ctx* c, uint32_t* subarray, int* for
 {
     if (!c) return BAZ_MUSIC_E_INVALID;
     std::lock_guard<std::mutex> lk(const_cast<baz_music_ctx*>(c)->mtx);
-    const bool on = c->sm.inner && !beamspace_on(c);
+    const bool on = c->sm.inner && c->sm.kind == baz_music_ctx::FRONT_SMOOTHING;
     if (subarray) *subarray = on ? c->sm.ms : c->m;
     if (forward_backward) *forward_backward = on ? c->sm.fb : 0;
     return BAZ_MUSIC_OK;

@@ -352,6 +352,67 @@ std::vector<std::complex<double> > baz_music_doa::beamspace()
     return T;
 }
 
+namespace {
+/* S tables back to back, as baz_music_set_subbands takes them */
+std::vector<float> flatten_subband_tables(const std::vector<array_response_t>& tables, unsigned int m, unsigned int resolution)
+{
+    std::vector<float> flat;
+    flat.reserve(tables.size() * (size_t)resolution * m * 2);
+    for (size_t s = 0; s < tables.size(); ++s) {
+        const std::vector<float> one = flatten_response(tables[s], m, resolution);
+        flat.insert(flat.end(), one.begin(), one.end());
+    }
+    return flat;
+}
+}  // namespace
+
+void baz_music_doa::set_subbands(unsigned int F, const std::vector<unsigned int>& bins, const std::vector<array_response_t>& tables, int combine)
+{
+    if (F == 0) {
+        const int rc = baz_music_set_subbands(d_ctx, 0, 0, NULL, NULL, 0);
+        if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: set_subbands: ") + baz_music_strerror(rc));
+        return;
+    }
+    if (bins.empty() || tables.size() != bins.size())
+        throw std::invalid_argument("music_doa: set_subbands: one table per used subband is required");
+    const std::vector<float> flat = flatten_subband_tables(tables, d_m, d_resolution);
+    const std::vector<uint32_t> k(bins.begin(), bins.end());
+    const int rc = baz_music_set_subbands(d_ctx, F, (uint32_t)k.size(), k.data(), flat.data(), combine);
+    if (rc == BAZ_MUSIC_E_INVALID)
+        throw std::invalid_argument("music_doa: set_subbands: 2 <= F <= 64 dividing nsamples / m, 1 .. 32 distinct bins below F, finite tables "
+                                    "and combine 0 or 1 are required");
+    if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: set_subbands: ") + baz_music_strerror(rc));
+}
+
+void baz_music_doa::set_subband_tables(const std::vector<array_response_t>& tables)
+{
+    uint32_t S = 0;
+    int rc = baz_music_get_subbands(d_ctx, NULL, &S, NULL, NULL);
+    if (rc == BAZ_MUSIC_OK && S && tables.size() != S)
+        throw std::invalid_argument("music_doa: set_subband_tables: one table per used subband is required");
+    if (rc == BAZ_MUSIC_OK) {
+        const std::vector<float> flat = flatten_subband_tables(tables, d_m, d_resolution);
+        rc = flat.empty() ? BAZ_MUSIC_E_INVALID : baz_music_set_subband_tables(d_ctx, flat.data());
+    }
+    if (rc == BAZ_MUSIC_E_INVALID) throw std::invalid_argument("music_doa: set_subband_tables: S finite tables are required");
+    if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: set_subband_tables: ") + baz_music_strerror(rc));
+}
+
+std::vector<unsigned int> baz_music_doa::subbands()
+{
+    uint32_t F = 0, S = 0, bins[BAZ_MUSIC_MAX_SUBBANDS] = {0};
+    int combine = 0;
+    const int rc = baz_music_get_subbands(d_ctx, &F, &S, bins, &combine);
+    if (rc != BAZ_MUSIC_OK) throw std::runtime_error(std::string("music_doa: subbands: ") + baz_music_strerror(rc));
+    std::vector<unsigned int> out;
+    if (F) {
+        out.push_back(F);
+        out.push_back((unsigned int)combine);
+        out.insert(out.end(), bins, bins + S);
+    }
+    return out;
+}
+
 void baz_music_doa::whiten_next(unsigned int items)
 {
     if (items == 0) throw std::invalid_argument("music_doa: whiten_next: items > 0 is required");

@@ -131,6 +131,17 @@ public:
     void set_beamspace(const std::vector<std::complex<double> >& T, unsigned int B, bool normalise = false);
     double set_beamspace_sector(unsigned int bin_lo, unsigned int bin_count, unsigned int B, bool normalise = false);
     std::vector<std::complex<double> > beamspace();
+    /* Extension, off by default (not in the reference): wideband (subband) MUSIC -- every item is cut into blocks of F samples, an
+     * F-point DFT per antenna separates the used subbands `bins` (distinct DFT indices below F), the estimator runs per subband on
+     * tables[s] and the spectra are combined (0: harmonic, the sum of the MUSIC denominators; 1: arithmetic) into the row the pickers
+     * read (baz_music_set_subbands, include/baz_music_hip.h).  F = 0 is off.  set_subband_tables retunes all tables at once.
+     * subbands(): F, combine, then the bins in force (empty while off).  Up to 16 antennas; not available while smoothing, beamspace,
+     * a calibration, noise pre-whitening, the emitter-count mode, refinement, power mode or the beam mode is on.  Throws
+     * std::invalid_argument unless 2 <= F <= 64 divides nsamples / m, the 1 .. 32 bins are distinct and below F, the tables are finite
+     * and combine is 0 or 1. */
+    void set_subbands(unsigned int F, const std::vector<unsigned int>& bins, const std::vector<array_response_t>& tables, int combine = 0);
+    void set_subband_tables(const std::vector<array_response_t>& tables);
+    std::vector<unsigned int> subbands();
 
     /* Page-locking of the scheduler's stream buffers (baz_music_set_host_pinning, include/baz_music_hip.h): work()
      * registers the ranges it is handed the first time it sees them, stop() and the destructor release them.  On by

@@ -279,6 +279,12 @@ PYBIND11_MODULE(_baz_music, mod)
                  return h.blk->set_beamspace_sector(bin_lo, bin_count, B, normalise);
              }, py::arg("bin_lo"), py::arg("bin_count"), py::arg("B"), py::arg("normalise") = false)
         .def("beamspace", [](music_doa_handle& h) { return h.blk->beamspace(); })
+        .def("set_subbands", [](music_doa_handle& h, unsigned int F, const std::vector<unsigned int>& bins,
+                                const std::vector<array_response_t>& tables, int combine) { h.blk->set_subbands(F, bins, tables, combine); },
+             py::arg("F"), py::arg("bins"), py::arg("tables"), py::arg("combine") = 0)
+        .def("set_subband_tables", [](music_doa_handle& h, const std::vector<array_response_t>& tables) { h.blk->set_subband_tables(tables); },
+             py::arg("tables"))
+        .def("subbands", [](music_doa_handle& h) { return h.blk->subbands(); })
         .def("last_orders",
              [](music_doa_handle& h, unsigned int count) {
                  const std::vector<unsigned char> v = h.blk->last_orders(count);

@@ -738,6 +738,72 @@ BAZ_MUSIC_API int baz_music_beamspace_apply(uint32_t m, uint32_t B, const double
                                             float* out_ri);
 BAZ_MUSIC_API int baz_music_beamspace_design(uint32_t m, uint32_t resolution, const float* table_ri, uint32_t bin_lo, uint32_t bin_count,
                                              uint32_t B, double* T_out, double* captured_out);
+/* OPT-IN extension, NOT reference behaviour: WIDEBAND (SUBBAND) MUSIC.  One steering table is right at one wavelength.
+ * Behind a wide front end every item is cut into blocks of F samples, an F-point DFT per antenna separates S used subbands, the
+ * estimator runs per subband on THAT subband's table, and the S spectra are combined into one row the pickers read (incoherent wideband
+ * MUSIC).  With K = nsamples / m time columns per item, Q = K / F blocks.  The library never learns the sample rate: the caller lists
+ * the DFT indices to use and supplies one table per index.  F == 0 switches the mode off (the default; off is the reference).
+ *   PARAMETERS  2 <= F <= 64, F divides K; 1 <= S <= BAZ_MUSIC_MAX_SUBBANDS distinct DFT indices bins[s] = k_s in [0, F), used in the
+ *               order given; tables_ri: S tables of resolution x m complex64 (the layout of baz_music_create's), table s for k_s;
+ *               combine: BAZ_MUSIC_SUBBAND_HARMONIC or BAZ_MUSIC_SUBBAND_ARITHMETIC.
+ *   TWIDDLES    W[s][t] = exp(-2 pi i ((k_s t) mod F) / F) / sqrt(F), complex128, computed once on the host: every component within
+ *               2 ulp of the exact value, and the values 0 and +-fl64(1 / sqrt(F)) at (k_s t) mod F a multiple of F / 4 exactly those.
+ *               baz_music_subband_twiddles returns them ([S][F], re / im interleaved).  Everything below is defined in terms of the W in
+ *               force, so the device, baz_music_subband_apply and a restatement that takes W from the library agree bit for bit.
+ *   CHANNELISER for item i, block q < Q, antenna r, with x(i, c, r) = in[i*nsamples + c*m + r]:
+ *                 y_s(i, q, r) = fl32(sum_{t = 0 .. F-1} W[s][t] x(i, q F + t, r))
+ *               x widened exactly; the sum in fp64 from (+0, +0) with t ascending; each term the four fused multiply-adds
+ *                 re = fma(wr, xr, re); re = fma(-wi, xi, re); im = fma(wr, xi, im); im = fma(wi, xr, im)
+ *               with wr = Re W[s][t], wi = Im W[s][t] (the chain of the noise pre-whitening and of the beamspace projection, along time
+ *               instead of across antennas); one round-to-nearest conversion per component.  Device layout [s][item][q][r]: the items
+ *               of subband s are one contiguous batch of ordinary items of shape (m, m Q).  A (block, antenna) pair reads no other, so
+ *               a non-finite sample turns exactly the S outputs of its own (block, antenna) non-finite.
+ *   PER SUBBAND an inner context of shape (m, n, m Q, resolution) on table s runs the fast path on subband s's items, its spectrum port
+ *               wired: P_s(i, b), float32, what a plain context of that shape gives for those items bit for bit.
+ *   COMBINE     harmonic:   P(i, b) = fl32(S / sum_s (1.0 / (double)P_s(i, b)))     (the sum of the subbands' MUSIC denominators)
+ *               arithmetic: P(i, b) = fl32((sum_s (double)P_s(i, b)) / S)          (meant for the Capon / Bartlett powers)
+ *               both sums from +0 with s ascending in plain IEEE fp64 additions, one division at the end; zeros, infinities and NaNs
+ *               do what IEEE does with these formulas.
+ *   PORTS       ang / lvl are picked from the combined float32 row: peak mode 0 by the reference's top-n rule (the strongest n bins by
+ *               value, the earlier bin first on ties, a value reported only if > 0), peak mode 1 by the local-maximum picker;
+ *               ang = bin*360/resolution, lvl = the combined word itself.  Port 2, where wired, carries the combined row.
+ *   VALIDITY    2 <= m <= BAZ_MUSIC_FAST_M (17 .. BAZ_MUSIC_MAX_M antennas: BAZ_MUSIC_E_UNSUPPORTED); F, S, bins as above, finite tables,
+ *               combine 0 or 1: BAZ_MUSIC_E_INVALID otherwise; what baz_music_create refuses for the shape (m, n, m Q, resolution)
+ *               comes back as create's code.  The setting in force stays after any error.
+ *   WHEN        both setters build the S inner contexts beside the running stream and exchange them under the batch lock: a batch sees
+ *               all S old tables or all S new ones, never a mixture.  set_subband_tables keeps F, the bins and the rule and is a fresh
+ *               set_subbands with the new tables (covariance-averaging histories start over); BAZ_MUSIC_E_UNSUPPORTED while off.
+ *               baz_music_set_table while the mode is on replaces only this context's own table, the one "off" returns to.
+ *   COMPOSES    peak mode acts on the combined row (the inner contexts stay at mode 0).  The estimator kind is forwarded to every inner
+ *               context; so are covariance averaging with its weights and window, and its reset: each subband averages its own stream.
+ *               reserve, sync, set_stream, host_register / set_host_pinning work; every call is cut into chunks whose channelised items
+ *               and whose S private spectrum rows each fit BAZ_MUSIC_SMOOTH_WORKSPACE_BYTES (at least one item per chunk), and the
+ *               host-fed baz_music_process stages the same chunks through device buffers: the same bits as the device path.
+ *   REFUSES     with BAZ_MUSIC_E_UNSUPPORTED, in both orders, the setting in force staying: smoothing, beamspace, calibration, noise
+ *               pre-whitening, the emitter-count mode, refinement, power mode and beam mode.  profile, stage_ms, refined_values /
+ *               refined_items and the debug_ taps that run stages return BAZ_MUSIC_E_UNSUPPORTED and stage_name returns "" while the
+ *               mode is on, as under smoothing.
+ *   OFF         never set, set to off, or switched on and off again: the kernels, launch counts and every port of a context before the
+ *               mode existed, bit for bit; nothing is allocated.
+ * get_subbands: *F = *S = 0 while off, else the setting in force; bins_out (S words, may be NULL, untouched while off), *combine.
+ * debug_subbands runs the channeliser alone with the W in force: d_in (batch items) -> d_out (S batch Q m complex64, [s][item][q][r]),
+ * device memory, not overlapping; BAZ_MUSIC_E_UNSUPPORTED while the mode is off.  debug_subband_combine runs the combine alone under the S and
+ * the rule in force: d_spectra (S batch resolution float32, [s][item][bin]) -> d_out (batch resolution float32), likewise.
+ * HOST FUNCTIONS (no device needed):
+ *   subband_twiddles  W_out[S][F] complex128 for the bins given; BAZ_MUSIC_E_INVALID for F, S or bins out of range or repeated.
+ *   subband_apply     the channeliser over `blocks` blocks of F x m complex64 (in_ri: [block][t][r]) with the W given (any S x F
+ *                     complex128: a block window is a change of W) -> out_ri [s][block][r]; the kernel runs the same text. */
+#define BAZ_MUSIC_MAX_SUBBANDS 32u
+#define BAZ_MUSIC_SUBBAND_HARMONIC 0
+#define BAZ_MUSIC_SUBBAND_ARITHMETIC 1
+BAZ_MUSIC_API int baz_music_set_subbands(baz_music_ctx* ctx, uint32_t F, uint32_t S, const uint32_t* bins, const float* tables_ri, int combine);
+BAZ_MUSIC_API int baz_music_set_subband_tables(baz_music_ctx* ctx, const float* tables_ri);
+BAZ_MUSIC_API int baz_music_get_subbands(const baz_music_ctx* ctx, uint32_t* F, uint32_t* S, uint32_t* bins_out, int* combine);
+BAZ_MUSIC_API int baz_music_debug_subbands(baz_music_ctx* ctx, const void* d_in, uint32_t batch, void* d_out);
+BAZ_MUSIC_API int baz_music_debug_subband_combine(baz_music_ctx* ctx, const void* d_spectra, uint32_t batch, void* d_out);
+BAZ_MUSIC_API int baz_music_subband_twiddles(uint32_t F, uint32_t S, const uint32_t* bins, double* W_out);
+BAZ_MUSIC_API int baz_music_subband_apply(uint32_t m, uint32_t F, uint32_t S, const double* W_ri, const float* in_ri, uint32_t blocks,
+                                          float* out_ri);
 /* Statistic: how many (item, bin) values of the LAST process call were recomputed in the reference's literal form
  * ||G^H a||^2 because the projector form a^H Q a put them at or below ~m 1e-8 max||a||^2 (near-nulls of the noise
  * subspace, SNR >~ 55 dB); blocks until that call is done (a host-fed call cut into chunks reports their sum).
